@@ -10,14 +10,17 @@ rank order, RCCL all-gather); `--exchange sum` is the plain SUM all-reduce basel
 `--update hogwild` the collective-free IPC parameter server.  Inputs (the HBM-resident RGB frame
 pool) are on the device before the timed region.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
 
-Rank 0 prints ONE JSON line (value = all GPUs' env-steps / max-over-ranks wall time), with the
-dominant kernel's roofline (live in-graph launch spans, plus HIP-event timing of that kernel alone
-on its live buffers) and the CPU baseline: oracle/ps_worker.py, the reference's ps/worker
-algorithm restated in numpy (shared-memory PS, unlocked RMSProp workers) on host cores, bounded
-sample.
+Rank 0 prints ONE JSON line (value = all GPUs' env-steps / max-over-ranks wall time; ms_per_step
+= the wall time of one timed step).  A plain run sets up, runs W warm-up steps, times exactly K
+steps, writes the engine's outputs of the last step under --dump-outputs, and prints the line.
+`--full` adds what takes runs of its own: K-step windows repeated over --min-seconds (value =
+the median window), the dominant kernel's roofline (live in-graph launch spans, plus HIP-event
+timing of that kernel alone on its live buffers) and the CPU baseline: oracle/ps_worker.py, the
+reference's ps/worker algorithm restated in numpy (shared-memory PS, unlocked RMSProp workers) on
+host cores, bounded sample.
 """
 import argparse
 import json
@@ -85,22 +88,40 @@ def parse():
                          'default: the push of rollout k-1 and the pull overlap rollout k (staleness 1)')
     ap.add_argument('--hogwild-memory', default='fine', choices=['fine', 'coarse', 'uncached'],
                     help='--update hogwild: allocation kind of the IPC-shared shards (DESIGN §7 memory model)')
-    ap.add_argument('--cpu-seconds', type=float, default=12.0)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--cpu-seconds', type=float, default=12.0, help='--full: length of the CPU baseline sample')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baseline')
     ap.add_argument('--backend', default='nccl', choices=['nccl', 'gloo'],
                     help='process group backend for N > 1 (nccl = RCCL over xGMI; gloo only to rehearse the '
                          'multi-rank path with several ranks on one GPU)')
-    ap.add_argument('--no-kernel-timing', action='store_true')
+    ap.add_argument('--no-kernel-timing', action='store_true', help='--full without the per-kernel timings')
     ap.add_argument('--exchange', default='sequential', choices=['sequential', 'sum'],
                     help='N > 1 sync/overlap: sequential = partitioned PS (all-to-all, every worker\'s clipped '
                          'gradient its own RMSProp step in rank order, all-gather: the reference PS rule); '
                          'sum = one SUM all-reduce + one step (plain data parallel)')
-    ap.add_argument('--min-seconds', type=float, default=2.0,
+    ap.add_argument('--full', action='store_true',
+                    help='beside the headline figure: the CPU baseline (before the GPU is initialised), the '
+                         'live launch spans, the per-kernel timings and the roofline of the dominant kernel, and '
+                         'K-step windows repeated over --min-seconds (default 2 s).  A plain run sets up, warms '
+                         'up, times exactly --steps steps and prints the line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps write what the last step left in the engine (parameters, '
+                         'gradient, loss, each rollout slot\'s logits / actions / rewards / returns) as '
+                         'DIR/<name>.npy, float32; exactly --steps steps are timed, so two builds run with the '
+                         'same arguments can be compared output for output')
+    ap.add_argument('--min-seconds', type=float, default=None,
                     help='repeat the K-step timed window until at least this much time is measured (a short '
-                         'K leaves a few ms of GPU time per window); value = median window rate, spread reported')
+                         'K leaves a few ms of GPU time per window); value = median window rate, spread reported. '
+                         'Default: 0 (one window of exactly --steps steps), 2.0 with --full')
     ap.add_argument('--max-windows', type=int, default=100000,
                     help='upper bound on the window count (the default never binds before --min-seconds)')
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:                  # a plain run measures the headline figure alone
+        args.no_cpu_baseline = args.no_kernel_timing = True
+    if args.dump_outputs:              # the dumped step is step --steps of the run, whatever the clock says
+        args.min_seconds = 0.0
+    elif args.min_seconds is None:
+        args.min_seconds = 2.0 if args.full else 0.0
+    return args
 
 
 def host_cpu():
@@ -307,6 +328,31 @@ def nature_roofline(eng, _lib, E, n, iter_ms, spans=None):
     return roofline, kernels
 
 
+DUMP_BYTES = 64 << 20      # --dump-outputs: upper bound on what one run writes
+
+
+def dump_outputs(eng, path, rank=0, world=1):
+    """--dump-outputs: what an Engine.iterate() caller holds after the last timed step, as
+    <name>.npy (float32): the parameters, the last gradient and loss, and every rollout slot's
+    logits / values z, actions, rewards, terminals and returns (overlap engines have two slots).
+    An array over its share of DUMP_BYTES is cut to a fixed, seeded sample of its elements."""
+    import numpy as np
+    arrays = {'params': eng.params, 'grads': eng.grads, 'loss': eng.loss}
+    for k in range(2 if eng.overlap else 1):
+        s = eng.slot(k)
+        for name in ('z', 'actions', 'rewards', 'terminals', 'returns'):
+            arrays[f'slot{k}_{name}'] = s[name]
+    arrays = {k: v.detach().cpu().numpy().astype(np.float32) for k, v in arrays.items()}
+    over = sum(a.nbytes for a in arrays.values()) > DUMP_BYTES
+    cap = DUMP_BYTES // (4 * len(arrays))          # elements per array, were all of them large
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        if over and a.size > cap:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, cap, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ('' if world == 1 else f'_rank{rank}') + '.npy'), a)
+
+
 def dist_record(args, torch, dist, local):
     """What the process group saw: backend, world size, launcher, every rank's device (index, name,
     PCI bus id) and the RCCL version torch was built against."""
@@ -442,8 +488,9 @@ def main():
         step()
     barrier()
     torch.cuda.synchronize()
-    live = not host and not nature and (eng.overlap or args.update == 'sync')
-    live_nat = nature and not host
+    timing = not args.no_kernel_timing          # (--full) the spans feed the kernel table alone
+    live = timing and not host and not nature and (eng.overlap or args.update == 'sync')
+    live_nat = timing and nature and not host
     if live or live_nat:          # live launch spans of the dominant kernels, recorded in-graph
         eng.span_stats(0, reset=True)
         eng.span_stats(1, reset=True)
@@ -454,6 +501,8 @@ def main():
     while sum(windows) < args.min_seconds and len(windows) < args.max_windows:
         windows.append(timed_window())
     el = float(np.median(windows))
+    if args.dump_outputs:         # before the kernel timings, which run on the live buffers
+        dump_outputs(eng, args.dump_outputs, rank, world)
     spans = {}
     if live_nat:                  # the nature trunk's per-state conv kernel (k_nat_conv23)
         spans['nat_conv123_fwd'] = eng.span_stats(1)

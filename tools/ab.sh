@@ -8,7 +8,7 @@ REPS=${AB_REPS:-3}
 for rep in $(seq 1 "$REPS"); do
   for cfg in "$@"; do
     for u in $MODES; do
-      if [ -n "$KT" ]; then kt=""; else kt="--no-kernel-timing"; fi
+      if [ -n "$KT" ]; then kt="--full"; else kt="--min-seconds 2"; fi
       env $cfg timeout -k 10 200 python3 bench.py --no-cpu-baseline $kt --steps 400 --update $u $AB_ARGS > gpurun_out/ab.json || exit 1
       python3 -c "
 import json;d=json.load(open('gpurun_out/ab.json'))

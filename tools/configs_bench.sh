@@ -4,7 +4,7 @@ set -o pipefail
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 cd "$ROOT"
 O=gpurun_out/configs; mkdir -p $O
-run() { name=$1; shift; timeout -k 10 240 python3 bench.py --no-cpu-baseline --no-kernel-timing "$@" > $O/$name.json 2> $O/$name.err || { echo "$name failed"; tail -5 $O/$name.err; return 1; }
+run() { name=$1; shift; timeout -k 10 240 python3 bench.py --full --no-cpu-baseline --no-kernel-timing "$@" > $O/$name.json 2> $O/$name.err || { echo "$name failed"; tail -5 $O/$name.err; return 1; }
   python3 -c "import json;d=json.load(open('$O/$name.json'));print('%-12s %12.1f' % ('$name', d['value']))"; }
 run default && run m2_frames84 --frames84 && run sync --update sync && run c3_breakout --game Breakout-v0 && run c4_512 --envs 512 && \
 run c4_hogwild --envs 512 --update hogwild && run c5_lstm --lstm --game SpaceInvaders-v0 && run e1024 --envs 1024 && \

@@ -8,4 +8,4 @@ timeout -k 10 900 python3 -u -m pytest tests -m gpu -x -v --timeout 300 --timeou
 rc=$?
 tail -15 $O/pytest.log
 [ $rc -ne 0 ] && exit $rc
-timeout -k 10 300 python3 -u bench.py --no-cpu-baseline --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err && cat $O/bench.json
+timeout -k 10 300 python3 -u bench.py --full --no-cpu-baseline --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err && cat $O/bench.json

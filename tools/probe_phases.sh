@@ -11,4 +11,4 @@ A3C_LIB=$V/cbp/liba3c_hip.so timeout -k 10 180 python3 -u tools/cb_phases.py > $
 echo "[probe] hs_phases overlap" && \
 A3C_LIB=$V/hst/liba3c_hip.so HS_KER=5 HS_OVERLAP=1 timeout -k 10 180 python3 -u tools/hs_phases.py > $O/hs1.txt 2>&1 && cat $O/hs1.txt && \
 echo "[probe] bench" && \
-timeout -k 10 300 python3 -u bench.py --no-cpu-baseline --steps 400 > $O/bench.json 2> $O/bench.err && cat $O/bench.json
+timeout -k 10 300 python3 -u bench.py --full --no-cpu-baseline --steps 400 > $O/bench.json 2> $O/bench.err && cat $O/bench.json

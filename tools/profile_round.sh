@@ -9,7 +9,7 @@ mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 cd "$ROOT"
 echo "[profile] bench" && \
-timeout -k 10 400 python3 bench.py "$@" > "$OUT/bench.json" 2> "$OUT/bench.err" && cat "$OUT/bench.json" && \
+timeout -k 10 400 python3 bench.py --full "$@" > "$OUT/bench.json" 2> "$OUT/bench.err" && cat "$OUT/bench.json" && \
 echo "[profile] kernel trace" && \
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o run --output-format csv -- \
     python3 bench.py --steps 100 --no-cpu-baseline "$@" > "$OUT/trace.log" 2>&1 && \
