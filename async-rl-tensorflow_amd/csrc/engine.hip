@@ -13,6 +13,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <utility>
 #include <vector>
 #include "env.h"
 #include "net_bwd.h"
@@ -50,6 +51,31 @@ struct Slot {
   // bootstrap-step h, c [E][U]
   float *lh, *lc, *lhp, *lcp, *lg, *lhb, *lcb;
   float* lwt;              // LSTM gate matrix of P, transposed for the forward (rollout start)
+};
+
+// Agent.play (agent.py:351-391) on the engine: a context of its own, allocated by the first
+// a3c_engine_play and zeroed there and by a3c_engine_reset (lives = 0: the first new_random_game
+// resets).  Nothing here aliases the training state; only the frame pool is shared, read-only.
+struct PlayCtx {
+  bool ready;
+  int R;                   // ring slots (HIST + 1: a step reads tau-3 .. tau and writes tau + 1)
+  uint8_t* ring;           // [E][R][PLANE]
+  int64_t* counters;       // [0] the play tau
+  EnvBufs env;             // [2][E] each; both parity copies are kept equal
+  PlayBook bk;             // ret / len / term [E], frozen [2][E]
+  float* rraw;             // [E] the step's act() rewards, unclipped
+  uint8_t* terms;          // [E] the step's terminals
+  int32_t* frames;         // [E] the step's post-act frame indices
+  int32_t* actions;        // [E] the step's actions (without a trace buffer)
+  float* z;                // [E][zs] the step's head rows (without a trace buffer)
+  float* eps;              // [E] test epsilon per env
+  int32_t* active;         // envs still playing after the last step
+  float *a1, *a2, *a3, *a4;   // one step's activations (a1, a4: nature trunk only)
+  uint8_t* prep;           // forward weights of the live parameters, prepared once per call
+  float* nat_fws;          // nature trunk: the fc's split-K slabs
+  float *lh, *lc;          // LSTM head: h, c [2][E][U], step t reads copy t & 1 and writes the other
+  float* lwt;
+  std::vector<std::pair<void*, size_t>> state;   // what "zeroed" covers
 };
 
 // graphs: 0 sync rollout+grad; 1, 2 rollout of slot 0, 1; 3, 4 grad of slot 0, 1; and with the
@@ -127,6 +153,7 @@ struct a3c_engine {
   bool grad_ready;         // the last rollout_grad call computed a gradient
   bool grad_applied;       // ... and a3c_engine_iterate already applied it (apply is then a no-op)
   bool reset_done;
+  PlayCtx play;            // a3c_engine_play's context (lazy)
 };
 
 // k_fc_part_fold's ticket words: one per 32-row x 64-column tile of the E-row fc
@@ -1120,6 +1147,7 @@ extern "C" int a3c_engine_reset(a3c_engine* e, const float* host_params, void* s
   A3C_CHECK(hipMemsetAsync(e->xflags, 0, 64, s));
   if (e->ext) A3C_CHECK(hipMemsetAsync(e->counters, 0, 64, s));   // ext_begin sets them
   A3C_CHECK(hipMemsetAsync(e->ep_acc, 0, (size_t)e->E * 8, s));
+  for (const auto& x : e->play.state) A3C_CHECK(hipMemsetAsync(x.first, 0, x.second, s));   // (empty before the first play)
   hipLaunchKernelGGL(k_stats_reset, dim3(1), dim3(A3C_STATS_N), 0, s, e->stats);
   A3C_CHECK(hipGetLastError());
   A3C_CHECK(hipStreamSynchronize(s));
@@ -1632,6 +1660,259 @@ extern "C" int a3c_engine_advance(a3c_engine* e, void* stream) {
 
 extern "C" int a3c_engine_get_buffers(a3c_engine* e, a3c_engine_buffers* b) {
   return a3c_engine_slot_buffers(e, 0, b);
+}
+
+// ---- Agent.play (agent.py:351-391): batched evaluation without learning --------------------------
+extern "C" void a3c_play_config_default(a3c_play_config* c) {
+  c->n_episode = 100;      // agent.py:351
+  c->n_step = 10000;
+  c->greedy = 0;
+  c->test_ep = -1.0f;
+  c->poll_every = 64;
+}
+
+// One launch per play step, behind the step's head kernel.  Block 0: ep_reward += reward
+// (agent.py:377, unclipped, the terminal step's too), length += 1, a terminal ends the episode
+// (agent.py:378-379); the frozen flags of the next step's parity; the count of envs still playing by
+// a fixed-order tree reduction; tau += 1.  Blocks 1 .. E (LSTM head): a frozen env's h, c go
+// unchanged into the copy the next step reads.  (They read the flags of this step's parity, which
+// block 0 does not write, and no block but 0 reads tau.)
+__global__ void __launch_bounds__(256) k_play_observe(PlayBook bk, int E, int par, const float* __restrict__ rraw,
+                                                      const uint8_t* __restrict__ terms, int32_t* __restrict__ active,
+                                                      int64_t* __restrict__ counters, const float* __restrict__ h_src,
+                                                      const float* __restrict__ c_src, float* __restrict__ h_dst,
+                                                      float* __restrict__ c_dst) {
+  if (blockIdx.x > 0) {
+    const int e = blockIdx.x - 1;
+    if (!bk.frozen[(int64_t)par * E + e]) return;
+    for (int i = threadIdx.x; i < LSTM_U; i += 256) {
+      h_dst[(int64_t)e * LSTM_U + i] = h_src[(int64_t)e * LSTM_U + i];
+      c_dst[(int64_t)e * LSTM_U + i] = c_src[(int64_t)e * LSTM_U + i];
+    }
+    return;
+  }
+  __shared__ int red[256];
+  int cnt = 0;
+  for (int e = threadIdx.x; e < E; e += 256) {
+    uint8_t fz = bk.frozen[(int64_t)par * E + e];
+    if (!fz) {
+      bk.ret[e] += rraw[e];
+      bk.len[e] += 1;
+      if (terms[e]) {
+        bk.term[e] = 1;
+        fz = 1;
+      }
+    }
+    bk.frozen[(int64_t)(par ^ 1) * E + e] = fz;
+    cnt += fz ? 0 : 1;
+  }
+  red[threadIdx.x] = cnt;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    *active = red[0];
+    counters[0] += 1;
+  }
+}
+
+static int play_alloc(a3c_engine* e, hipStream_t s) {
+  PlayCtx& c = e->play;
+  if (c.ready) return 0;
+  const NetLayout& L = e->L;
+  const int64_t E = e->E;
+  c.R = HIST + 1;
+  c.state.clear();         // (a failed earlier attempt)
+  int rc = 0;
+  // st: part of the state a3c_engine_reset zeroes
+#define PALLOC(ptr, bytes, st) do { void* _p; if ((rc = dalloc(e, &_p, (size_t)(bytes)))) return rc; \
+    ptr = (decltype(ptr))_p; if (st) c.state.emplace_back(_p, (size_t)(bytes)); } while (0)
+  PALLOC(c.ring, E * c.R * PLANE, true);
+  PALLOC(c.counters, 64, true);
+  PALLOC(c.env.episode, 2 * E * 4, true);
+  PALLOC(c.env.ep_step, 2 * E * 4, true);
+  PALLOC(c.env.ep_len, 2 * E * 4, true);
+  PALLOC(c.env.lives, 2 * E * 4, true);
+  PALLOC(c.env.frame, 2 * E * 4, true);
+  PALLOC(c.env.reward, 2 * E * 4, true);
+  PALLOC(c.env.terminal, 2 * E, true);
+  PALLOC(c.bk.ret, E * 4, true);
+  PALLOC(c.bk.len, E * 4, true);
+  PALLOC(c.bk.term, E, true);
+  PALLOC(c.bk.frozen, 2 * E, true);
+  PALLOC(c.rraw, E * 4, false);
+  PALLOC(c.terms, E, false);
+  PALLOC(c.frames, E * 4, false);
+  PALLOC(c.actions, E * 4, false);
+  PALLOC(c.z, E * L.zs * 4, false);
+  PALLOC(c.eps, E * 4, false);
+  PALLOC(c.active, 64, false);
+  if (e->nat) {
+    PALLOC(c.a1, E * NT_A1 * 4, false);
+    PALLOC(c.a2, E * NT_A2 * 4, false);
+    PALLOC(c.a3, E * NT_FLAT * 4, false);
+    PALLOC(c.a4, E * NT_FC * 4, false);
+    PALLOC(c.nat_fws, a3c_nat_fwd_ws_floats(E) * 4, false);
+  } else {
+    PALLOC(c.a2, E * FLAT * 4, false);
+    PALLOC(c.a3, E * FC * 4, false);
+  }
+  PALLOC(c.prep, PREP_BYTES, false);
+  if (L.lstm) {
+    PALLOC(c.lh, 2 * E * LSTM_U * 4, true);
+    PALLOC(c.lc, 2 * E * LSTM_U * 4, true);
+    PALLOC(c.lwt, (int64_t)LSTM_K * LSTM_G * 4, false);
+  }
+#undef PALLOC
+  for (const auto& x : c.state) A3C_CHECK(hipMemsetAsync(x.first, 0, x.second, s));
+  A3C_CHECK(hipStreamSynchronize(s));
+  c.ready = true;
+  return 0;
+}
+
+// play step t of a wave (agent.py:371-377): forward of s_tau on the play ring, action draw, act
+// with is_training = false, screen -- the play form of the step's tail -- then k_play_observe
+static int enqueue_play_step(a3c_engine* e, int mode, int t, int32_t* actions, float* z, hipStream_t s) {
+  const PlayCtx& c = e->play;
+  const NetLayout& L = e->L;
+  const int E = e->E, par = t & 1;
+  HeadSelect sel = {};
+  sel.mode = mode;
+  sel.k0 = e->k0; sel.k1 = e->k1;
+  sel.tau_ptr = c.counters; sel.tau_add = 0;
+  sel.env_ids = nullptr; sel.env_id_base = e->cfg.env_id_base; sel.E = E;
+  sel.eps = c.eps;
+  sel.actions = actions;
+  sel.env_on = 1;
+  sel.par_E = E;
+  sel.envp = e->envp;
+  sel.envb = c.env;
+  sel.rewards_raw = c.rraw;
+  sel.terms = c.terms;
+  sel.frames_out = c.frames;
+  sel.pool = e->pool;
+  sel.ring = c.ring;
+  sel.R = c.R;
+  sel.frame84 = e->frame84;
+  StateAddr sa = ring_addr(e, 0, c.counters);
+  sa.base = c.ring;
+  sa.env_stride = (int64_t)c.R * PLANE;
+  sa.R = c.R;
+  const uint8_t* frozen = c.bk.frozen + (int64_t)par * E;
+  const int64_t hc = (int64_t)E * LSTM_U;
+  int rc;
+  if (e->nat) {
+    rc = a3c_nat_forward_launch(L, e->params, sa, E, c.a1, c.a2, c.a3, c.a4, z, sel, (const uint16_t*)c.prep,
+                                c.nat_fws, s, frozen);
+  } else {
+    LstmStep ls = {};
+    if (L.lstm) {
+      ls.wt = c.lwt;
+      ls.h_src = c.lh + par * hc; ls.c_src = c.lc + par * hc;
+      ls.h = c.lh + (par ^ 1) * hc; ls.c = c.lc + (par ^ 1) * hc;
+    }
+    rc = a3c_forward_launch(L, e->params, c.prep, sa, E, nullptr, c.a2, c.a3, z, sel, s, L.lstm ? &ls : nullptr,
+                            false, nullptr, nullptr, nullptr, frozen);
+  }
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_play_observe, dim3(L.lstm ? 1 + E : 1), dim3(256), 0, s, c.bk, E, par, c.rraw, c.terms,
+                     c.active, c.counters, L.lstm ? c.lh + par * hc : nullptr, L.lstm ? c.lc + par * hc : nullptr,
+                     L.lstm ? c.lh + (par ^ 1) * hc : nullptr, L.lstm ? c.lc + (par ^ 1) * hc : nullptr);
+  A3C_CHECK(hipGetLastError());
+  return 0;
+}
+
+static int play_impl(a3c_engine* e, const a3c_play_config& pc, float* returns, int32_t* lengths,
+                     uint8_t* terminated, int32_t* trace_actions, float* trace_z, hipStream_t s) {
+  PlayCtx& c = e->play;
+  const NetLayout& L = e->L;
+  const int E = e->E;
+  const bool q = L.algo == A3C_ALGO_Q;
+  // the action draw (mode, per-env epsilon)
+  const int mode = q || pc.greedy ? 1 : 0;
+  if (q && pc.test_ep < 0.f) {
+    A3C_CHECK(hipMemcpyAsync(c.eps, e->ep_end, (size_t)E * 4, hipMemcpyDeviceToDevice, s));
+  } else if (int rc = a3c_fill_launch(c.eps, E, pc.test_ep > 0.f ? pc.test_ep : 0.f, s)) {
+    return rc;
+  }
+  // forward weights of the live parameters, once per call
+  int rc = e->nat ? a3c_nat_prep_launch(L, e->params, (uint16_t*)c.prep, nullptr, nullptr, nullptr, s)
+                  : a3c_prep_fwd_launch(L, e->params, c.prep, s);
+  if (!rc && L.lstm) rc = a3c_lstm_transpose_launch(e->params + L.off[T_LW], c.lwt, s);
+  if (rc) return rc;
+  const int waves = (pc.n_episode + E - 1) / E;
+  std::vector<float> ret(E);
+  std::vector<int32_t> len(E);
+  std::vector<uint8_t> term(E);
+  for (int w = 0; w < waves; ++w) {
+    const int n_act = pc.n_episode - w * E < E ? pc.n_episode - w * E : E;
+    const int64_t tau = (HIST - 1) + (int64_t)w * ((int64_t)pc.n_step + HIST);
+    rc = a3c_play_begin_launch(e->envp, c.env, E, n_act, tau, c.bk, e->pool, c.ring, c.R, c.counters, e->frame84, s);
+    if (rc) return rc;
+    if (L.lstm) {
+      A3C_CHECK(hipMemsetAsync(c.lh, 0, (size_t)2 * E * LSTM_U * 4, s));
+      A3C_CHECK(hipMemsetAsync(c.lc, 0, (size_t)2 * E * LSTM_U * 4, s));
+    }
+    for (int t = 0; t < pc.n_step;) {
+      const int stop = pc.n_step - t < pc.poll_every ? pc.n_step : t + pc.poll_every;
+      for (; t < stop && !rc; ++t) {
+        const int64_t o = ((int64_t)w * pc.n_step + t) * E;
+        rc = enqueue_play_step(e, mode, t, trace_actions ? trace_actions + o : c.actions,
+                               trace_z ? trace_z + o * L.zs : c.z, s);
+      }
+      if (rc) return rc;
+      int32_t active = 0;
+      A3C_CHECK(hipMemcpyAsync(&active, c.active, 4, hipMemcpyDeviceToHost, s));
+      A3C_CHECK(hipStreamSynchronize(s));
+      if (active == 0) break;
+    }
+    A3C_CHECK(hipMemcpyAsync(ret.data(), c.bk.ret, (size_t)E * 4, hipMemcpyDeviceToHost, s));
+    A3C_CHECK(hipMemcpyAsync(len.data(), c.bk.len, (size_t)E * 4, hipMemcpyDeviceToHost, s));
+    A3C_CHECK(hipMemcpyAsync(term.data(), c.bk.term, (size_t)E, hipMemcpyDeviceToHost, s));
+    A3C_CHECK(hipStreamSynchronize(s));
+    for (int i = 0; i < n_act; ++i) {
+      returns[(int64_t)w * E + i] = ret[i];
+      lengths[(int64_t)w * E + i] = len[i];
+      terminated[(int64_t)w * E + i] = term[i];
+    }
+  }
+  return 0;
+}
+
+extern "C" int a3c_engine_play(a3c_engine* e, const a3c_play_config* cfg, float* returns, int32_t* lengths,
+                               uint8_t* terminated, int32_t* trace_actions, float* trace_z, void* stream) {
+  if (!e || !cfg || !returns || !lengths || !terminated)
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_play", "null");
+  if (e->ext)
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_play", "host-stepped envs are played by the host (no device env)");
+  if (cfg->n_episode < 1 || cfg->n_step < 1 || cfg->poll_every < 1)
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_play", "n_episode, n_step and poll_every must be >= 1");
+  if (!e->reset_done) return a3c_set_error(A3C_ERR_STATE, "a3c_engine_play", "call a3c_engine_reset first");
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = play_alloc(e, s)) return rc;
+  // overlap: a training rollout may be in flight on the rollout stream -> the small-footprint forms
+  a3c_set_shared_gpu(e->overlap != 0);
+  int rc = play_impl(e, *cfg, returns, lengths, terminated, trace_actions, trace_z, s);
+  a3c_set_shared_gpu(false);
+  if (rc) return rc;
+  A3C_CHECK(hipStreamSynchronize(s));
+  return 0;
+}
+
+extern "C" int a3c_engine_play_buffers(a3c_engine* e, a3c_play_buffers* b) {
+  if (!e || !b) return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_play_buffers", "null");
+  if (e->ext) return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_play_buffers", "no device env");
+  if (int rc = play_alloc(e, nullptr)) return rc;
+  const PlayCtx& c = e->play;
+  memset(b, 0, sizeof(*b));
+  b->frame_ring = c.ring; b->ring_slots = c.R; b->tau = c.counters;
+  b->env_frame = c.env.frame; b->env_lives = c.env.lives; b->env_episode = c.env.episode;
+  b->env_step = c.env.ep_step; b->env_len = c.env.ep_len;
+  b->returns = c.bk.ret; b->lengths = c.bk.len; b->terminated = c.bk.term; b->frozen = c.bk.frozen;
+  b->lstm_h = c.lh; b->lstm_c = c.lc;
+  return 0;
 }
 
 // ---- profiling hook: average duration of one engine kernel, HIP events on the caller's stream ----

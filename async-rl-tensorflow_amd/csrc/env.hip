@@ -107,6 +107,78 @@ int a3c_env_init_screens_launch(const EnvBufs& b, int E, const uint8_t* pool, ui
   return 0;
 }
 
+// ---- Agent.play (agent.py:351-391): start of a wave of evaluation episodes --------------------
+// new_random_game (agent.py:363, environment.py:35-40) of the wave's envs e < n_active only: the
+// emulator continues where the env's previous episode stopped (it resets only when lives == 0).
+// The play context keeps both parity copies of an env's state equal, so the state is read from
+// copy 0 and written to both.  Zeroes the wave's return / length / terminated words, freezes the
+// envs without an episode (both parity copies of the flag) and sets the play tau.
+__global__ void k_play_begin(EnvParams p, EnvBufs b, int E, int n_active, int64_t tau, PlayBook bk,
+                             int64_t* __restrict__ counters) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e == 0) counters[0] = tau;
+  if (e >= E) return;
+  const bool active = e < n_active;
+  bk.frozen[e] = bk.frozen[E + e] = active ? 0 : 1;
+  bk.ret[e] = 0.f;
+  bk.len[e] = 0;
+  bk.term[e] = 0;
+  if (!active) return;
+  EnvState s = env_load(b, e);
+  env_new_random_game(s, p, (uint32_t)(p.env_id_base + e));
+  env_store(b, e, s);
+  env_store(b, (int64_t)E + e, s);
+}
+
+// the first screen of every active env into its HIST newest ring slots, (tau - 3 .. tau) mod R
+// (agent.py:366-367); grid (parts, E) as k_env_init_screens, frozen envs' rings untouched
+__global__ void __launch_bounds__(256) k_play_begin_screens(EnvBufs b, const uint8_t* __restrict__ frozen,
+                                                            const uint8_t* __restrict__ pool,
+                                                            uint8_t* __restrict__ ring, int R, int64_t tau, PreGeom g) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  const int e = blockIdx.y;
+  if (frozen[e]) return;
+  const int32_t f = b.frame[e];
+  uint8_t* base = ring + (int64_t)e * R * PLANE;
+  const int64_t fb = (int64_t)g.in_h * g.in_w * 3;
+  for (int c = 0; c < HIST; ++c) {
+    a3c_preprocess_part(pool + (int64_t)f * fb, base + ((tau - (HIST - 1) + c) % R) * PLANE, g, blockIdx.x, smem);
+    __syncthreads();
+  }
+}
+
+// the same for pre-sized 84x84 pool frames (cfg.frame84): a copy (grid E)
+__global__ void __launch_bounds__(256) k_play_begin_copy84(EnvBufs b, const uint8_t* __restrict__ frozen,
+                                                           const uint8_t* __restrict__ pool,
+                                                           uint8_t* __restrict__ ring, int R, int64_t tau) {
+  const int e = blockIdx.x;
+  if (frozen[e]) return;
+  const int32_t f = b.frame[e];
+  const uint4* src = (const uint4*)(pool + (int64_t)f * PLANE);
+  uint8_t* base = ring + (int64_t)e * R * PLANE;
+  for (int i = threadIdx.x; i < PLANE / 16; i += blockDim.x) {
+    const uint4 v = src[i];
+    for (int c = 0; c < HIST; ++c) ((uint4*)(base + ((tau - (HIST - 1) + c) % R) * PLANE))[i] = v;
+  }
+}
+
+int a3c_play_begin_launch(const EnvParams& p, const EnvBufs& b, int E, int n_active, int64_t tau, const PlayBook& bk,
+                          const uint8_t* pool, uint8_t* ring, int R, int64_t* counters, int frame84, hipStream_t s) {
+  if (E < 1 || n_active < 1 || n_active > E || tau < HIST - 1 || R < HIST + 1)
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_play_begin", "bad argument");
+  hipLaunchKernelGGL(k_play_begin, dim3((E + 63) / 64), dim3(64), 0, s, p, b, E, n_active, tau, bk, counters);
+  A3C_CHECK(hipGetLastError());
+  if (frame84) {
+    hipLaunchKernelGGL(k_play_begin_copy84, dim3(E), dim3(256), 0, s, b, bk.frozen, pool, ring, R, tau);
+  } else {
+    PreGeom g = a3c_make_geom(SCREEN_H, SCREEN_W, IMG_OUT, IMG_OUT);
+    hipLaunchKernelGGL(k_play_begin_screens, dim3(g.parts, E), dim3(256), a3c_pre_smem_bytes(g), s, b, bk.frozen, pool,
+                       ring, R, tau, g);
+  }
+  A3C_CHECK(hipGetLastError());
+  return 0;
+}
+
 int a3c_screen_rows();
 
 template <int ROWS>

@@ -1672,9 +1672,11 @@ int a3c_nat_prep_launch(const NetLayout& L, const float* P, uint16_t* w1t, const
 // ---------------------------------------------------------------------------------------
 int a3c_nat_forward_launch(const NetLayout& L, const float* P, const StateAddr& sa, int64_t B, float* l1, float* l2,
                            float* l3, float* l4, float* z, const HeadSelect& sel, const uint16_t* w1t, float* ws,
-                           hipStream_t s) {
+                           hipStream_t s, const uint8_t* play_frozen) {
   if (L.trunk != A3C_TRUNK_NATURE || B <= 0 || B * NT1_P > 0x7fffffffLL)
     return a3c_set_error(A3C_ERR_INVALID, "a3c_nat_forward", "nature trunk, 0 < B, B * 400 < 2^31");
+  if (play_frozen && !(sel.mode >= 0 && sel.env_on && sel.pool))
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_nat_forward", "the play step runs with the device env and the fused screen");
   if (!w1t) {   // one-off forward: the weight terms into the workspace's tail first
     uint16_t* t = (uint16_t*)(ws + nat_fwd_slab_floats(B));
     if (int rc = nat_w1_terms_launch(L, P, t, s)) return rc;
@@ -1682,7 +1684,8 @@ int a3c_nat_forward_launch(const NetLayout& L, const float* P, const StateAddr& 
   }
   const bool step_tail = sel.mode >= 0 && sel.env_on && sel.pool;   // the engine's rollout step
   const int fcs = fc_split(B);
-  const bool fold_in_head = step_tail && fcs > 1 && !nat_bf(NAT_FCF) && nat_fold_head();
+  // (the play step keeps the fc's own fold: its tail is the 512-wide play head alone)
+  const bool fold_in_head = step_tail && fcs > 1 && !nat_bf(NAT_FCF) && nat_fold_head() && !play_frozen;
   for (int pass = NAT_C1F; pass <= (fold_in_head ? NAT_C3F : NAT_FCF); ++pass) {
     const int rc = a3c_nat_pass_launch(pass, L, P, sa, B, l1, l2, l3, l4, w1t, ws, nullptr, s);
     if (rc) return rc;
@@ -1699,6 +1702,9 @@ int a3c_nat_forward_launch(const NetLayout& L, const float* P, const StateAddr& 
     return a3c_head_screen_fold_launch(ws, fcs, P + L.off[N_FCB], l4, P + L.off[N_HW], P + L.off[N_HB],
                                        P + L.off[N_VW], P + L.off[N_VB], L.A, L.zs, B, z, sel, s);
   }
+  if (play_frozen)   // Agent.play's step tail (agent.py:371-377)
+    return a3c_head_screen_play_launch(NT_FC, l4, P + L.off[N_HW], P + L.off[N_HB], P + L.off[N_VW], P + L.off[N_VB],
+                                       L.A, L.zs, B, z, sel, play_frozen, s);
   if (step_tail)   // head + act + Environment.screen
     return a3c_head_screen_wide_launch(l4, P + L.off[N_HW], P + L.off[N_HB], P + L.off[N_VW], P + L.off[N_VB], L.A,
                                        L.zs, B, z, sel, s);

@@ -181,10 +181,18 @@ struct Conv12Next {
   uint32_t* l2m;            // nullable: act_l2's ReLU mask as bits [b][81] (the backward's dl2 epilogue)
 };
 // ls (LSTM head, C5): the cell step runs on act_l3 and the heads read ls->h
+// play_frozen (a3c_engine_play, Agent.play agent.py:351-391): the step's tail is the play form of the
+// head + act + screen kernel -- act with is_training = false, no new game on a terminal, and envs
+// with play_frozen[e] != 0 left untouched (no z row, action, env state or ring slot written)
 int a3c_forward_launch(const NetLayout& L, const float* params, const uint8_t* prep, const StateAddr& sa,
                        int64_t B, float* act_l1, float* act_l2, float* act_l3, float* z, const HeadSelect& sel,
                        hipStream_t s, const LstmStep* ls = nullptr, bool skip_conv12 = false,
-                       const Conv12Next* next = nullptr, float* fc_part = nullptr, uint32_t* l2m = nullptr);
+                       const Conv12Next* next = nullptr, float* fc_part = nullptr, uint32_t* l2m = nullptr,
+                       const uint8_t* play_frozen = nullptr);
+// the play step's tail alone: W = FC (NIPS trunk / LSTM head rows) or NT_FC (nature trunk)
+int a3c_head_screen_play_launch(int W, const float* h, const float* Wp, const float* bp, const float* Wv,
+                                const float* bv, int A, int zs, int64_t B, float* z, const HeadSelect& sel,
+                                const uint8_t* frozen, hipStream_t s);
 // fc layer as FC_NS K-slice partials part[x][M][FC] (folded by k_head_screen_conv12's head)
 // adv_ptr: the launch also advances the device tau counter by adv_n (thread 0 of block 0; the fc
 // reads no tau) -- the rollout's last kernel when the bootstrap head runs on the backward stream

@@ -499,16 +499,25 @@ __global__ void __launch_bounds__(256) k_head_fwd(const float* __restrict__ h3, 
 // runs the env act up to the frame (env_act_pre: nothing but the frame depends on the action);
 // returns the post-act frame (pool index) of env b
 // (W: the width of the layer below the heads -- FC, or NT_FC for the nature trunk)
-template <int W = FC>
+// PLAY (Agent.play, agent.py:351-391; k_head_screen_play only): the act runs with is_training =
+// false (agent.py:373: a lost life is no terminal and costs no -1), a terminal starts no new game
+// (the env is done), only the unclipped reward is recorded (agent.py:377), and the env state goes
+// to both parity copies, so an env that is frozen afterwards needs no copy across the (tau & 1)
+// double buffer.  frozen[e] != 0: env e is done or has no episode in this wave -- nothing of it is
+// touched and -1 is returned (the whole workgroup, before any barrier).
+template <int W = FC, bool PLAY = false>
 __device__ inline int32_t head_act_env(const float* __restrict__ h3, const float* __restrict__ Wp,
                                        const float* __restrict__ bp, const float* __restrict__ Wv,
                                        const float* __restrict__ bv, int A, int zs, float* __restrict__ z,
                                        const HeadSelect& sel, int64_t b, int64_t tau, uint64_t* dbg,
-                                       const float* hrow = nullptr) {
+                                       const float* hrow = nullptr, const uint8_t* frozen = nullptr) {
   __shared__ int32_t s_act;
   __shared__ uint32_t s_draw, s_term;
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int e = (int)b;
+  if constexpr (PLAY) {
+    if (frozen[e]) return -1;
+  }
   const int64_t nxt = ((tau + 1) & 1) * (int64_t)sel.par_E + e;
   if (wid == 0) {
     const float eps = sel_eps(sel, e, tau);
@@ -539,17 +548,23 @@ __device__ inline int32_t head_act_env(const float* __restrict__ h3, const float
     const int64_t cur = (tau & 1) * (int64_t)sel.par_E + e;
     const uint32_t id = (uint32_t)(sel.env_id_base + e);
     EnvState s = env_load(sel.envb, cur);
-    const uint32_t draw = env_act_pre(s, sel.envp, id, true);
-    sel.rewards[e] = fmaxf(-1.0f, fminf(1.0f, s.reward));   // observe clip, agent.py:154
+    const uint32_t draw = env_act_pre(s, sel.envp, id, !PLAY);
+    if constexpr (!PLAY) sel.rewards[e] = fmaxf(-1.0f, fminf(1.0f, s.reward));   // observe clip, agent.py:154
     if (sel.rewards_raw) sel.rewards_raw[e] = s.reward;
     sel.terms[e] = (uint8_t)s.terminal;
     s_draw = draw;
-    s_term = s.terminal;
-    if (s.terminal) {
-      env_new_random_game(s, sel.envp, id);                  // agent.py:66-67
-      env_store(sel.envb, nxt, s);
+    if constexpr (PLAY) {
+      s_term = 0;                                            // (the post-act frame is the env's frame)
+      env_store(sel.envb, nxt, s, false);
+      env_store(sel.envb, cur, s, false);
     } else {
-      env_store(sel.envb, nxt, s, false);                    // frame: after the action draw
+      s_term = s.terminal;
+      if (s.terminal) {
+        env_new_random_game(s, sel.envp, id);                  // agent.py:66-67
+        env_store(sel.envb, nxt, s);
+      } else {
+        env_store(sel.envb, nxt, s, false);                    // frame: after the action draw
+      }
     }
     if (dbg) dbg[17] = __builtin_readcyclecounter();
   }
@@ -563,6 +578,7 @@ __device__ inline int32_t head_act_env(const float* __restrict__ h3, const float
     if (threadIdx.x == 0) {
       sel.frames_out[e] = frame;
       if (!s_term) sel.envb.frame[nxt] = frame;
+      if constexpr (PLAY) sel.envb.frame[(tau & 1) * (int64_t)sel.par_E + e] = frame;
     }
   } else {
     frame = sel.frames_out[b];                               // last frame (no env act)
@@ -597,6 +613,29 @@ __global__ void __launch_bounds__(HS_THREADS) k_head_screen(const float* __restr
   else
     atari::screen_frame<HS_THREADS>(sel.pool + (int64_t)frame * (atari::IH * atari::IW * 3), slot, smem, dbg);
   WG_T1(z + b * zs);
+}
+
+// The play form of k_head_screen (a3c_engine_play): one step of Agent.play's loop for env b
+// (agent.py:371-377: predict with the fixed test epsilon, act with is_training = false, history
+// add) -- or nothing at all when the env is frozen.
+template <int HS_THREADS, int W>
+__global__ void __launch_bounds__(HS_THREADS) k_head_screen_play(const float* __restrict__ h3,
+                                                                 const float* __restrict__ Wp,
+                                                                 const float* __restrict__ bp,
+                                                                 const float* __restrict__ Wv,
+                                                                 const float* __restrict__ bv, int A, int zs,
+                                                                 float* __restrict__ z, HeadSelect sel,
+                                                                 const uint8_t* __restrict__ frozen) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  const int64_t b = blockIdx.x;
+  const int64_t tau = *sel.tau_ptr + sel.tau_add;
+  const int32_t frame = head_act_env<W, true>(h3, Wp, bp, Wv, bv, A, zs, z, sel, b, tau, nullptr, nullptr, frozen);
+  if (frame < 0) return;
+  uint8_t* slot = sel.ring + b * sel.R * PLANE + ((tau + 1) % sel.R) * PLANE;
+  if (sel.frame84)
+    atari::copy_frame84<HS_THREADS>(sel.pool + (int64_t)frame * PLANE, slot);
+  else
+    atari::screen_frame<HS_THREADS>(sel.pool + (int64_t)frame * (atari::IH * atari::IW * 3), slot, smem, nullptr);
 }
 
 // Rollout step t's tail fused with step t+1's head: head + act + Environment.screen of env b
@@ -839,13 +878,37 @@ int a3c_head_screen_wide_launch(const float* l4, const float* Wp, const float* b
   return 0;
 }
 
+int a3c_head_screen_play_launch(int W, const float* h, const float* Wp, const float* bp, const float* Wv,
+                                const float* bv, int A, int zs, int64_t B, float* z, const HeadSelect& sel,
+                                const uint8_t* frozen, hipStream_t s) {
+  if (B <= 0) return 0;
+  if (!frozen || !sel.tau_ptr || !sel.env_on || !sel.ring || !sel.pool || !sel.rewards_raw || !sel.terms ||
+      !sel.frames_out || !sel.actions || sel.mode < 0 || sel.par_E < B || (W != FC && W != 512))
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_head_screen_play", "bad argument");
+  const int nt = a3c_shared_gpu() ? 512 : 1024;
+#define HSP_GO(T, WW) hipLaunchKernelGGL((k_head_screen_play<T, WW>), dim3((unsigned)B), dim3(T), SCREEN_FRAME_SMEM, s, h, \
+                                         Wp, bp, Wv, bv, A, zs, z, sel, frozen)
+  if (W == FC) {
+    if (nt == 1024) HSP_GO(1024, FC);
+    else HSP_GO(512, FC);
+  } else {
+    if (nt == 1024) HSP_GO(1024, 512);
+    else HSP_GO(512, 512);
+  }
+#undef HSP_GO
+  A3C_CHECK(hipGetLastError());
+  return 0;
+}
+
 int a3c_head_screen_conv12_launch(const NetLayout& L, const float* P, const float* act_l3, int64_t B, float* z,
                                   const HeadSelect& sel, const Conv12Next& nx, hipStream_t s);
 int a3c_forward_launch(const NetLayout& L, const float* params, const uint8_t* prep, const StateAddr& sa,
                        int64_t B, float* act_l1, float* act_l2, float* act_l3, float* z, const HeadSelect& sel,
                        hipStream_t s, const LstmStep* ls, bool skip_conv12, const Conv12Next* next,
-                       float* fc_part, uint32_t* l2m) {
+                       float* fc_part, uint32_t* l2m, const uint8_t* play_frozen) {
   if (B <= 0) return 0;
+  if (play_frozen && (next || fc_part || skip_conv12 || sel.mode < 0 || !sel.env_on || !sel.ring))
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_forward", "the play step runs unfused, with the device env and the fused screen");
   if (L.lstm != (ls != nullptr))
     return a3c_set_error(A3C_ERR_INVALID, "a3c_forward", "the LSTM head needs its recurrent state");
   const float* P = params;
@@ -890,6 +953,9 @@ int a3c_forward_launch(const NetLayout& L, const float* params, const uint8_t* p
     return a3c_head_screen_conv12_launch(L, P, head_in, B, z, hs, *next, s);
   }
   if (next) return a3c_set_error(A3C_ERR_INVALID, "a3c_forward", "conv fusion needs the fused env screen");
+  if (play_frozen)
+    return a3c_head_screen_play_launch(FC, head_in, P + L.off[T_HW], P + L.off[T_HB], Wv, bv, L.A, L.zs, B, z, sel,
+                                       play_frozen, s);
   if (sel.mode >= 0 && sel.env_on && sel.ring)
     return a3c_head_screen_launch(L, P, head_in, B, z, sel, s);
   else {
@@ -1002,6 +1068,14 @@ void a3c_conv12_set_smem() {
   (void)hipFuncSetAttribute((const void*)k_head_screen_fold<512, 512>, hipFuncAttributeMaxDynamicSharedMemorySize,
                             SCREEN_FRAME_SMEM);
   (void)hipFuncSetAttribute((const void*)k_head_screen_fold<1024, 512>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            SCREEN_FRAME_SMEM);
+  (void)hipFuncSetAttribute((const void*)k_head_screen_play<512, FC>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            SCREEN_FRAME_SMEM);
+  (void)hipFuncSetAttribute((const void*)k_head_screen_play<1024, FC>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            SCREEN_FRAME_SMEM);
+  (void)hipFuncSetAttribute((const void*)k_head_screen_play<512, 512>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            SCREEN_FRAME_SMEM);
+  (void)hipFuncSetAttribute((const void*)k_head_screen_play<1024, 512>, hipFuncAttributeMaxDynamicSharedMemorySize,
                             SCREEN_FRAME_SMEM);
 }
 

@@ -9,6 +9,7 @@ accepted but the TF ps/worker cluster is replaced by one process per GPU under t
 
   python main.py --mode engine --env_name Pong-v0 --iterations 1000
   python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 main.py --mode engine
+  python main.py --mode engine --is_train false --n_episode 100     evaluate the newest checkpoint
 """
 import argparse
 import json
@@ -82,6 +83,13 @@ def parse_flags(argv=None):
   p.add_argument('--dqn_type', choices=['nips', 'nature'], default='nips',
                  help="conv trunk of network.py:30-50 (Network(DQN_type=...)): nips (fused kernels) or nature "
                       "(implicit-GEMM kernels, nature.hip; --algo a3c)")
+  # evaluation: --mode engine --is_train false (Agent.play, agent.py:351-391)
+  p.add_argument('--n_episode', type=int, default=100, help='play: episodes (agent.py:351)')
+  p.add_argument('--play_steps', type=int, default=10000, help="play: cap on an episode's env steps (agent.py:351 n_step)")
+  p.add_argument('--test_ep', type=float, default=None,
+                 help='play: the fixed epsilon (agent.py:351); default: q -- each env\'s final epsilon (main.py:68), '
+                      'a3c -- the categorical draw, or greedy with --greedy')
+  p.add_argument('--greedy', action='store_true', help='play, a3c: argmax (epsilon-greedy with --test_ep) on the logits')
   p.add_argument('--logdir', default='./logs')
   return p.parse_args(argv)
 
@@ -105,6 +113,67 @@ def engine_options(flags):
   if flags.dqn_type == 'nature':
     kw['dqn_type'] = 'nature'
   return kw
+
+
+def play_options(flags, world=None):
+  """--mode engine --is_train false (Agent.play, agent.py:351-391, as a3c_engine_play): the
+  Engine.play keyword arguments the flags select, or None when training.  Pure -- runs before any
+  device work -- and rejects what play cannot honour, so --is_train is not silently dropped."""
+  if flags.is_train:
+    return None
+  if flags.envs_on != 'device':
+    raise ValueError('--is_train false plays the device envs: --envs_on %s is not supported' % flags.envs_on)
+  if flags.update == 'hogwild':
+    raise ValueError('--is_train false does not update: --update hogwild has no meaning there')
+  world = int(os.environ.get('WORLD_SIZE', '1')) if world is None else int(world)
+  if world > 1:
+    raise ValueError('--is_train false evaluates with one process (WORLD_SIZE = %d)' % world)
+  if flags.n_episode < 1 or flags.play_steps < 1:
+    raise ValueError('--n_episode and --play_steps must be >= 1')
+  if flags.test_ep is not None and flags.test_ep < 0:
+    raise ValueError('--test_ep must be >= 0')
+  if flags.greedy and flags.algo != 'a3c':
+    raise ValueError('--greedy selects the a3c draw; q engines are epsilon-greedy (--test_ep 0 for greedy)')
+  return dict(n_episode=int(flags.n_episode), n_step=int(flags.play_steps), test_ep=flags.test_ep,
+              greedy=bool(flags.greedy))
+
+
+def run_play(config, flags, play_kw):
+  """Evaluate the newest checkpoint (or, with a warning, the initial parameters) on a synchronous
+  engine: one JSON line on stdout and in <logdir>/play.jsonl; nothing is trained or saved."""
+  from src import checkpoint as C
+  from src.base import BaseModel
+  from src.engine import Engine
+  from src.environment import game_spec
+  from src.kernels import param_names_shapes
+  torch.cuda.set_device(int(os.environ.get('LOCAL_RANK', '0')))
+  A, lives = game_spec(config.env_name)
+  eng = Engine(num_envs=flags.num_envs, n_step=flags.n_step, action_size=A, algo=flags.algo, start_lives=lives,
+               num_frames=flags.num_frames, seed=flags.random_seed, overlap=False, **engine_options(flags),
+               random_start=config.random_start, action_repeat=config.action_repeat)
+  ns = param_names_shapes(A, flags.algo, lstm=eng.lstm, dqn_type=eng.dqn_type)
+  ckdir = flags.checkpoint_dir or os.path.join(flags.logdir, BaseModel(config, verbose=False).model_dir)
+  saver = C.Saver(ckdir, max_to_keep=flags.max_to_keep)
+  restored = C.restore_engine(saver, eng, ns) if flags.resume else None
+  if restored is None:
+    print('main.py: no checkpoint in %s: playing the initial parameters' % ckdir, file=sys.stderr, flush=True)
+    eng.reset(initial_params(eng, A, flags.algo, flags.random_seed))
+  torch.cuda.synchronize()
+  t0 = time.time()
+  out = eng.play(**play_kw)
+  dt = time.time() - t0
+  ret, length = out['returns'], out['lengths']
+  rec = dict(mode='play', checkpoint=saver.latest() if restored is not None else None,
+             global_step=int(eng.counters[1].item()), n_episode=int(ret.size), n_step=play_kw['n_step'],
+             test_ep=play_kw['test_ep'], greedy=play_kw['greedy'], best_reward=out['best_reward'],
+             best_idx=out['best_idx'], mean_reward=float(ret.mean()), min_reward=float(ret.min()),
+             max_reward=float(ret.max()), mean_length=float(length.mean()), terminated=int(out['terminated'].sum()),
+             env_steps=int(length.sum()), seconds=dt)
+  print(json.dumps(rec), flush=True)
+  os.makedirs(flags.logdir, exist_ok=True)
+  with open(os.path.join(flags.logdir, 'play.jsonl'), 'a') as f:
+    f.write(json.dumps(rec) + '\n')
+  return eng
 
 
 def initial_params(eng, action_size, algo, seed):
@@ -311,6 +380,9 @@ def main(argv=None):
   config.algo, config.n_step, config.num_envs = flags.algo, flags.n_step, flags.num_envs
   if flags.mode == 'engine':
     engine_options(flags)             # reject unsupported reference options before any device work
+    play_kw = play_options(flags)
+    if play_kw is not None:
+      return run_play(config, flags, play_kw)
     return run_engine(config, flags)
   return run_agent(config, flags)
 

@@ -59,6 +59,19 @@ class EngineBuffers(ctypes.Structure):
                 ('lstm_gates', c_void_p), ('lstm_units', c_int), ('act_l4', c_void_p), ('trunk', c_int)]
 
 
+class PlayConfig(ctypes.Structure):
+    """a3c_play_config (Agent.play's arguments, agent.py:351)."""
+    _fields_ = [('n_episode', c_int), ('n_step', c_int), ('greedy', c_int), ('test_ep', c_float),
+                ('poll_every', c_int)]
+
+
+class PlayBuffers(ctypes.Structure):
+    _fields_ = [('frame_ring', c_void_p), ('ring_slots', c_int), ('tau', c_void_p), ('env_frame', c_void_p),
+                ('env_lives', c_void_p), ('env_episode', c_void_p), ('env_step', c_void_p), ('env_len', c_void_p),
+                ('returns', c_void_p), ('lengths', c_void_p), ('terminated', c_void_p), ('frozen', c_void_p),
+                ('lstm_h', c_void_p), ('lstm_c', c_void_p)]
+
+
 # name -> (restype, argtypes)
 SIGNATURES = {
     'a3c_version': (ctypes.c_char_p, []),
@@ -153,6 +166,10 @@ SIGNATURES = {
     'a3c_rmsprop_range': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_float, c_float,
                                   c_float, c_float, c_void_p]),
     'a3c_engine_time_kernel': (c_int, [c_void_p, c_int, c_int, c_void_p, ctypes.POINTER(c_float)]),
+    'a3c_play_config_default': (None, [ctypes.POINTER(PlayConfig)]),
+    'a3c_engine_play': (c_int, [c_void_p, ctypes.POINTER(PlayConfig), c_void_p, c_void_p, c_void_p, c_void_p,
+                                c_void_p, c_void_p]),
+    'a3c_engine_play_buffers': (c_int, [c_void_p, ctypes.POINTER(PlayBuffers)]),
 }
 
 # diagnostics an A/B build from an earlier commit may lack (every other symbol is required)
@@ -163,7 +180,8 @@ OPTIONAL_IN_OLD_BUILDS = MEASUREMENT_ONLY + ('a3c_engine_exchange_split', 'a3c_e
                                              'a3c_dev_alloc_kind', 'a3c_engine_time_kernel', 'a3c_engine_set_step',
                                              'a3c_engine_stats_accumulate', 'a3c_engine_stats_read',
                                              'a3c_engine_state_bytes', 'a3c_engine_state_save',
-                                             'a3c_engine_state_load')
+                                             'a3c_engine_state_load', 'a3c_play_config_default', 'a3c_engine_play',
+                                             'a3c_engine_play_buffers')
 
 KER_CONV12_FWD, KER_FC_FWD, KER_ENV_STEP, KER_CONV_BWD, KER_HEAD_SCREEN, KER_HEAD_SCREEN_CONV12, KER_FC_PART = 0, 1, 2, 3, 4, 5, 6
 # nature trunk passes (include/a3c_hip.h A3C_KER_NAT_*)

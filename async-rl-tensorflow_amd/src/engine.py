@@ -233,6 +233,65 @@ class Engine:
             exchange(self.grads)
         self.apply()
 
+    # ---------------------------------------------------------------- evaluation (agent.py:351-391)
+    def play(self, n_episode=100, n_step=10000, test_ep=None, greedy=False, poll_every=64, trace=False):
+        """Agent.play (agent.py:351-391) batched: n_episode evaluation episodes of at most n_step
+        env steps each, E at a time (episode w*E + e: env e in wave w), with the live parameters and
+        no learning -- the training state is untouched.  The env steps with is_training=False (a
+        lost life is no terminal and costs no -1, agent.py:373) and the returns are sums of raw
+        rewards (agent.py:377).  test_ep: the fixed epsilon (q: None -> each env's final epsilon,
+        main.py:68; a3c: used with greedy=True only); test_ep=0 is greedy.  Synchronous.
+        Returns {'returns' f32, 'lengths' i32, 'terminated' bool [n_episode], 'best_reward',
+        'best_idx' (agent.py:381-383)}; trace=True adds the device tensors 'actions'
+        [waves, n_step, E] i32 and 'z' [waves, n_step, E, zs] f32, written by the steps' own
+        kernels (entries of frozen envs and of steps not run stay as allocated: -1 / NaN)."""
+        cfg = _lib.PlayConfig()
+        lib().a3c_play_config_default(ctypes.byref(cfg))
+        cfg.n_episode, cfg.n_step, cfg.greedy = int(n_episode), int(n_step), 1 if greedy else 0
+        cfg.test_ep = -1.0 if test_ep is None else float(test_ep)
+        cfg.poll_every = int(poll_every)
+        if test_ep is not None and float(test_ep) < 0:
+            raise ValueError('test_ep must be >= 0 (None: the per-env final epsilon)')
+        n_ep = max(cfg.n_episode, 1)
+        ret = np.zeros(n_ep, np.float32)
+        length = np.zeros(n_ep, np.int32)
+        term = np.zeros(n_ep, np.uint8)
+        acts = zt = None
+        if trace and cfg.n_episode >= 1 and cfg.n_step >= 1:      # (else the call rejects the arguments)
+            waves = -(-cfg.n_episode // self.E)
+            acts = torch.full((waves, cfg.n_step, self.E), -1, dtype=torch.int32, device='cuda')
+            zt = torch.full((waves, cfg.n_step, self.E, self.zs), float('nan'), dtype=torch.float32, device='cuda')
+        check(lib().a3c_engine_play(self._h, ctypes.byref(cfg), ret.ctypes.data_as(ctypes.c_void_p),
+                                    length.ctypes.data_as(ctypes.c_void_p), term.ctypes.data_as(ctypes.c_void_p),
+                                    _lib.ptr(acts), _lib.ptr(zt), _lib.stream_handle()), 'a3c_engine_play')
+        best_reward, best_idx = 0.0, 0                                   # agent.py:361
+        for idx in range(cfg.n_episode):
+            if ret[idx] > best_reward:                                   # agent.py:381-383
+                best_reward, best_idx = float(ret[idx]), idx
+        out = dict(returns=ret, lengths=length, terminated=term.astype(bool), best_reward=best_reward,
+                   best_idx=best_idx)
+        if trace:
+            out.update(actions=acts, z=zt)
+        return out
+
+    def play_buffers(self):
+        """Views of the play context (tests): ring [E, R_play, 84, 84], tau [1], env fields [2, E]
+        (both parity copies equal), the last wave's returns / lengths / terminated [E], frozen [2, E],
+        and lstm_h / lstm_c [2, E, U] with the LSTM head."""
+        b = _lib.PlayBuffers()
+        check(lib().a3c_engine_play_buffers(self._h, ctypes.byref(b)), 'a3c_engine_play_buffers')
+        E = self.E
+        out = dict(ring=_view(b.frame_ring, (E, b.ring_slots, 84, 84), torch.uint8), ring_slots=int(b.ring_slots),
+                   tau=_view(b.tau, (1,), torch.int64), frame=_view(b.env_frame, (2, E), torch.int32),
+                   lives=_view(b.env_lives, (2, E), torch.int32), episode=_view(b.env_episode, (2, E), torch.int32),
+                   ep_step=_view(b.env_step, (2, E), torch.int32), ep_len=_view(b.env_len, (2, E), torch.int32),
+                   returns=_view(b.returns, (E,), torch.float32), lengths=_view(b.lengths, (E,), torch.int32),
+                   terminated=_view(b.terminated, (E,), torch.uint8), frozen=_view(b.frozen, (2, E), torch.uint8))
+        if self.lstm:
+            out.update(lstm_h=_view(b.lstm_h, (2, E, _lib.A3C_LSTM_UNITS), torch.float32),
+                       lstm_c=_view(b.lstm_c, (2, E, _lib.A3C_LSTM_UNITS), torch.float32))
+        return out
+
     # ---------------------------------------------------------------- summaries (agent.py:69-139)
     STATS = ('reward_sum', 'ep_reward_sum', 'ep_reward_max', 'ep_reward_min', 'games', 'loss_sum', 'q_sum',
              'updates', 'env_steps', 'policy_loss_sum', 'value_loss_sum', 'entropy_sum')

@@ -490,6 +490,68 @@ int a3c_engine_get_buffers(a3c_engine* eng, a3c_engine_buffers* out);
  * writes slot k & 1); get_buffers == slot 0 */
 int a3c_engine_slot_buffers(a3c_engine* eng, int slot, a3c_engine_buffers* out);
 
+/* ----------------------------------------------------------------------------
+ * Evaluation: Agent.play (agent.py:351-391) on the engine, without learning.  The engine's E envs
+ * play n_episode episodes in waves of E: episode idx = w * E + e is played by env e in wave w
+ * (ceil(n_episode / E) waves, the last one possibly partial).  A forward-only rollout with a
+ * context of its own (env state, a frame ring of HIST + 1 slots, one step's activations, LSTM
+ * state): no training buffer, counter or env is written, in overlap mode too, and the frame pool
+ * is only read.  The context is allocated and zeroed by the first call, persists across calls and
+ * is zeroed again by a3c_engine_reset.
+ *  parameters: the live ones as they stand on `stream` at the call (agent.py:351: the network
+ *              being trained), prepared once per call.
+ *  wave start: new_random_game of the wave's envs (agent.py:363; the emulator goes on where the
+ *              env's last episode stopped, it resets only at lives == 0), the first screen into
+ *              the HIST newest ring slots (agent.py:366-367), LSTM state zeroed, and the play tau
+ *              of wave w set to (HIST-1) + w * (n_step + HIST) on every call.
+ *  step:       forward, action draw on the (tau, env id) Philox counter the rollout uses
+ *              (agent.py:371), act with is_training = false (agent.py:373: a lost life is no
+ *              terminal and costs no -1), the new screen into the ring (agent.py:375), return +=
+ *              the raw reward, the terminal step's included (agent.py:377), length += 1.  A
+ *              terminal ends the env's episode (agent.py:378-379); no new game follows.
+ *  frozen:     an env that is done, or has no episode in the wave, is frozen: nothing of it
+ *              advances (emulator, ring, LSTM state, trace entries).  A wave ends after n_step
+ *              steps, or once the host -- reading the active count every poll_every steps -- sees
+ *              none active; results do not depend on poll_every.
+ *  draw:       q engines: epsilon-greedy with eps = test_ep for every env, or with the engine's
+ *              per-env final epsilon (main.py:68, the reference's test_ep = self.ep_end) when
+ *              test_ep < 0.  a3c engines: the categorical draw (network.py:72) with greedy = 0;
+ *              with greedy = 1 epsilon-greedy on the logits with eps = max(test_ep, 0).
+ *              test_ep = 0 means greedy.  (The reference's `test_ep or schedule`, agent.py:371 ->
+ *              :142-144, falls back to the training schedule for test_ep = 0; here 0 is honoured.)
+ *  outputs:    host arrays returns / lengths / terminated [n_episode] (terminated: the episode hit
+ *              a terminal before the n_step cap).  The reference's best episode (agent.py:381-383)
+ *              is the first idx, in idx order, whose return is > the best so far, from (0, 0).
+ *              trace_actions [waves][n_step][E] i32 and trace_z [waves][n_step][E][zs] f32:
+ *              optional device buffers written by the steps' own kernels; entries of frozen envs
+ *              and of steps a wave did not run are left untouched.
+ * Synchronous: `stream` is idle when the call returns.  A3C_ERR_INVALID for engines with
+ * host-stepped envs and for n_episode, n_step or poll_every < 1; A3C_ERR_STATE before
+ * a3c_engine_reset. */
+typedef struct a3c_play_config {
+  int n_episode;     /* agent.py:351 n_episode (100)                                     */
+  int n_step;        /* agent.py:351 n_step (10000): the cap on an episode's env steps    */
+  int greedy;        /* a3c engines: 1 = argmax / epsilon-greedy on the logits (0)         */
+  float test_ep;     /* agent.py:351 test_ep; < 0: the per-env final epsilon (-1)          */
+  int poll_every;    /* steps between the host's reads of the active count (64)            */
+} a3c_play_config;
+void a3c_play_config_default(a3c_play_config* cfg);
+int a3c_engine_play(a3c_engine* eng, const a3c_play_config* cfg, float* returns, int32_t* lengths,
+                    uint8_t* terminated, int32_t* trace_actions, float* trace_z, void* stream);
+/* device pointers of the play context (tests; allocates it like the first a3c_engine_play).  The
+ * env fields are [2][E] with both parity copies equal; lstm_h / lstm_c [2][E][U], NULL without the
+ * LSTM head: the current state is copy (steps the last wave ran) & 1. */
+typedef struct a3c_play_buffers {
+  uint8_t* frame_ring;     /* [E][ring_slots][84*84] u8                        */
+  int ring_slots;
+  int64_t* tau;            /* device: the play tau                             */
+  int32_t* env_frame; int32_t* env_lives; uint32_t* env_episode; uint32_t* env_step; uint32_t* env_len;
+  float* returns; int32_t* lengths; uint8_t* terminated;   /* [E]: the last wave's bookkeeping */
+  uint8_t* frozen;         /* [2][E]                                           */
+  float* lstm_h; float* lstm_c;
+} a3c_play_buffers;
+int a3c_engine_play_buffers(a3c_engine* eng, a3c_play_buffers* out);
+
 /* profiling hook: average device time (ms) of `iters` back-to-back launches of one engine
  * kernel on its live buffers, bracketed by HIP events on `stream` (idempotent: each
  * relaunch recomputes the same outputs). */
