@@ -143,6 +143,16 @@ def lstm_bptt(w, x, hp, cp, gates, c, terms, dh):
     return dx, dw, db
 
 
+def _z_rows(z, B, zs, dev):
+    """The head-row buffer of a forward: a fresh [B, zs], or the caller's own [>= B, zs]."""
+    if z is None:
+        return torch.empty((B, zs), dtype=torch.float32, device=dev)
+    _dev(z, torch.float32, 'z')
+    if z.dim() != 2 or int(z.shape[0]) < B or int(z.shape[1]) != zs:
+        raise ValueError(f'z must be [>= {B}, {zs}], got {tuple(z.shape)}')
+    return z[:B]
+
+
 class NatureNet:
     """The nature trunk (network.py:30-42) + A3C heads on the nature.hip kernels: flat parameters
     in the C-ABI layout (include/a3c_hip.h), history_length 4."""
@@ -162,8 +172,9 @@ class NatureNet:
               'a3c_nature_workspace_bytes')
         return torch.empty(int(n.value), dtype=torch.uint8, device=device)
 
-    def forward(self, params, states, workspace=None):
-        """states [B,4,84,84] u8 (oldest frame first).  Returns dict z/l1/l2/l3/l4."""
+    def forward(self, params, states, workspace=None, z=None):
+        """states [B,4,84,84] u8 (oldest frame first).  Returns dict z/l1/l2/l3/l4.
+        z: caller-owned head rows [>= B, zs] to write into (rows past B are left alone)."""
         _dev(params, torch.float32, 'params')
         _dev(states, torch.uint8, 'states')
         B = int(states.shape[0])
@@ -172,7 +183,7 @@ class NatureNet:
                    l2=torch.empty((B, 5184), dtype=torch.float32, device=dev),
                    l3=torch.empty((B, 3136), dtype=torch.float32, device=dev),
                    l4=torch.empty((B, 512), dtype=torch.float32, device=dev),
-                   z=torch.empty((B, self.zs), dtype=torch.float32, device=dev))
+                   z=_z_rows(z, B, self.zs, dev))
         ws = workspace if workspace is not None else self.workspace(B, dev)
         check(lib().a3c_nature_forward(ctypes.byref(self.desc), ptr(params), ptr(states), B, ptr(out['l1']),
                                        ptr(out['l2']), ptr(out['l3']), ptr(out['l4']), ptr(out['z']), ptr(ws),
@@ -236,8 +247,9 @@ class Net:
         return torch.empty(nbytes, dtype=torch.uint8, device=device)
 
     # -- forward (agent.py:217-254 / network.py:43-79) --------------------------------
-    def forward(self, params, states, save_l1=True, workspace=None):
-        """states [B,4,84,84] u8 (oldest frame first).  Returns dict z/l1/l2/l3."""
+    def forward(self, params, states, save_l1=True, workspace=None, z=None):
+        """states [B,4,84,84] u8 (oldest frame first).  Returns dict z/l1/l2/l3.
+        z: caller-owned head rows [>= B, zs] to write into (rows past B are left alone)."""
         _dev(params, torch.float32, 'params')
         _dev(states, torch.uint8, 'states')
         B = int(states.shape[0])
@@ -245,7 +257,7 @@ class Net:
         l1 = torch.empty((B, C1), dtype=torch.float32, device=dev) if save_l1 else None
         l2 = torch.empty((B, FLAT), dtype=torch.float32, device=dev)
         l3 = torch.empty((B, FC), dtype=torch.float32, device=dev)
-        z = torch.empty((B, self.zs), dtype=torch.float32, device=dev)
+        z = _z_rows(z, B, self.zs, dev)
         ws = workspace if workspace is not None else self.workspace(B, dev)
         check(lib().a3c_forward(ctypes.byref(self.desc), ptr(params), ptr(states), B, ptr(l1), ptr(l2), ptr(l3),
                                 ptr(z), ptr(ws), stream_handle()), 'a3c_forward')

@@ -158,11 +158,12 @@ def test_main_engine_host_envs_resume_shortens_the_run(tmp_path):
     assert fresh.worker_step == 40
 
 
-@pytest.mark.parametrize('algo,A,lives,n', [('a3c', 6, 3, 5), ('q', 4, 5, 8)])
+@pytest.mark.parametrize('algo,A,lives,n', [('a3c', 6, 3, 5), ('q', 4, 5, 8), ('q', 18, 3, 4)])
 def test_summaries_match_reference_bookkeeping(algo, A, lives, n):
     """train_with_summary (agent.py:91-131) per env, replayed by hand on the oracle's unclipped
     rewards and terminals: total reward over every step; at a terminal the running episode
-    reward (terminal step excluded) is recorded and restarts; loss and q averaged per update."""
+    reward (terminal step excluded) is recorded and restarts; loss and q averaged per update.
+    ('q', 18): k_stats' mean over 18 actions of rows of stride zs = 20.)"""
     E, iters = 16, 30
     eng, ref, _ = build(algo, A, E, n, lives, seed=71, frames=64, scale=1.0, learning_rate=1e-3,
                         target_q_update_step=100)

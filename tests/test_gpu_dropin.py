@@ -189,14 +189,17 @@ def _net_params(net):
     return {k: v.detach().cpu().numpy().copy() for k, v in net.w.items()}
 
 
-@pytest.mark.parametrize('dqn_type', ['nips', 'nature'])
-def test_network_forward_loss_grads_match_oracle(dqn_type):
+@pytest.mark.parametrize('dqn_type,A', [('nips', 6), ('nature', 6), ('nips', 18), ('nature', 18)],
+                         ids=['nips', 'nature', 'nips-A18', 'nature-A18'])
+def test_network_forward_loss_grads_match_oracle(dqn_type, A):
+    """(A = 18: the wide head_row at W = 256 / 512 and head rows, dz and head GEMM of stride zs = 20
+    behind the drop-in Network.)"""
     from src.network import Network
     with pytest.raises(ValueError):
         Network(None, 'NCWH', 4, 84, 84, 6, DQN_type='nips')
     with pytest.raises(ValueError):
         Network(None, 'NHWC', 4, 84, 84, 6, DQN_type='dense')
-    net = Network(None, 'NHWC', 4, 84, 84, 6, beta=0.01, DQN_type=dqn_type, seed=12)
+    net = Network(None, 'NHWC', 4, 84, 84, A, beta=0.01, DQN_type=dqn_type, seed=12)
     # non-zero biases so the test sees them
     rng = np.random.default_rng(4)
     for k, v in net.w.items():
@@ -215,10 +218,10 @@ def test_network_forward_loss_grads_match_oracle(dqn_type):
     # float NHWC placeholder input (history.get() layout) gives the same values
     out2 = net.forward(torch.as_tensor(states.astype(np.float32)).cuda())
     assert torch.equal(out2['value'], out['value'])
-    pi, logpi, H = R.softmax_stats(fwd['z'][:, :6])
+    pi, logpi, H = R.softmax_stats(fwd['z'][:, :A])
     np.testing.assert_allclose(out['policy'].cpu().numpy(), pi, rtol=1e-4, atol=1e-7)
     np.testing.assert_allclose(out['policy_entropy'].cpu().numpy(), H, rtol=1e-4)
-    actions = rng.integers(0, 6, B)
+    actions = rng.integers(0, A, B)
     Rt = rng.standard_normal(B)
     losses, dz = R.a3c_loss_and_dz(fwd['z'], actions, Rt, 0.01)
     g_ref = R.backward(p, fwd, dz, 'a3c', dqn_type)
@@ -232,7 +235,7 @@ def test_network_forward_loss_grads_match_oracle(dqn_type):
     # and at 1e-4 against the oracle backward on the kernels' own activations (the same ReLU masks)
     fa = {k: v.detach().cpu().numpy().astype(np.float64) for k, v in net.last_forward.items() if v is not None}
     x0 = states.astype(np.float64) / 255.0
-    zs = fa['z'][:, :7]
+    zs = fa['z'][:, :A + 1]
     if dqn_type == 'nature':
         same = dict(z=zs, h3=fa['l4'], flat=fa['l3'], acts=[x0, fa['l1'].reshape(B, 20, 20, 32),
                                                            fa['l2'].reshape(B, 9, 9, 64), fa['l3'].reshape(B, 7, 7, 64)])
@@ -244,7 +247,7 @@ def test_network_forward_loss_grads_match_oracle(dqn_type):
     for (name, shp), o, n in zip(net.names_shapes, net.offsets, net.sizes):
         assert rel_l2(g[o:o + n].reshape(shp), g_same[name]) < 1e-4, (name, rel_l2(g[o:o + n].reshape(shp), g_same[name]))
     acts = net.sample_action(torch.as_tensor(planes).cuda(), seed=1, step=3)
-    assert acts.shape == (B,) and int(acts.min()) >= 0 and int(acts.max()) < 6
+    assert acts.shape == (B,) and int(acts.min()) >= 0 and int(acts.max()) < A
 
 
 def test_network_nchw_nature_matches_torch():

@@ -17,6 +17,7 @@ torch = pytest.importorskip('torch')
 from make_goldens import frame_from_spec  # noqa: E402
 from oracle import philox as px  # noqa: E402
 from oracle import ref_cpu as R  # noqa: E402
+from _net_parity import check_forward, check_loss_backward, cu, make_params  # noqa: E402
 
 
 @pytest.fixture(scope='module')
@@ -30,16 +31,6 @@ def K():
 @pytest.fixture(scope='module')
 def screen_golden(golden_dir):
     return np.load(os.path.join(golden_dir, 'screen_golden.npz'))
-
-
-def cu(x):
-    return torch.as_tensor(np.ascontiguousarray(x)).cuda()
-
-
-def rel_l2(a, b):
-    a = np.asarray(a, np.float64)
-    b = np.asarray(b, np.float64)
-    return np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-30)
 
 
 # ---------------------------------------------------------------------------------- K1
@@ -122,46 +113,9 @@ def test_history_push_get(K, screen_golden, golden_dir):
 
 
 # ---------------------------------------------------------------------------------- net
-def make_params(net, seed=0, scale=1.0):
-    from src.initializers import init_params
-    p = init_params(net.names_shapes, seed=seed, stddev=0.02 * scale)
-    rng = np.random.default_rng(seed + 1)
-    for k in p:
-        if k.endswith('_b'):
-            p[k] = (rng.standard_normal(p[k].shape) * 0.01).astype(np.float32)
-    return p
-
-
 @pytest.mark.parametrize('algo,A,B', [('a3c', 6, 1), ('a3c', 6, 37), ('a3c', 4, 256), ('q', 6, 19), ('q', 4, 64)])
 def test_forward_matches_oracle(K, algo, A, B):
-    net = K.Net(A, algo)
-    p = make_params(net, seed=B, scale=4.0)
-    rng = np.random.default_rng(B)
-    planes = rng.integers(0, 256, (B, 4, 84, 84), dtype=np.uint8)
-    out = net.forward(net.flatten(p), cu(planes))
-    ref = R.forward(p, R.states_nhwc(planes), algo, dtype=np.float64)
-    zw = A + 1 if algo == 'a3c' else A
-    z = out['z'].cpu().numpy()
-    # fp32 accumulation vs fp64: rtol 1e-4, plus an absolute floor of 1e-5 x the tensor's max
-    # (entries that cancel to ~0 after K = 256..2592 products carry absolute, not relative, error)
-    def close(a, b):
-        np.testing.assert_allclose(a, b, rtol=1e-4, atol=1e-5 * max(np.abs(b).max(), 1e-30))
-    close(z[:, :zw], ref['z'])
-    assert not z[:, zw:].any()
-    close(out['l1'].cpu().numpy().reshape(B, 20, 20, 16), ref['acts'][1])
-    close(out['l2'].cpu().numpy(), ref['flat'])
-    close(out['l3'].cpu().numpy(), ref['h3'])
-
-
-def oracle_fwd_from_gpu(planes, fwd, zw):
-    """The oracle's forward record built from the GPU activations, so the oracle backward uses
-    exactly the GPU's ReLU masks (a pre-activation within fp32 rounding of 0 may flip a mask
-    between an fp64 and an fp32 forward; that is forward, not backward, error)."""
-    B = planes.shape[0]
-    l1 = fwd['l1'].cpu().numpy().astype(np.float64).reshape(B, 20, 20, 16)
-    l2 = fwd['l2'].cpu().numpy().astype(np.float64)
-    return dict(z=fwd['z'].cpu().numpy().astype(np.float64)[:, :zw], h3=fwd['l3'].cpu().numpy().astype(np.float64),
-                flat=l2, acts=[R.states_nhwc(planes).astype(np.float64) / 255.0, l1, l2.reshape(B, 9, 9, 32)])
+    check_forward(K, algo, A, B)
 
 
 def test_select_action_categorical_and_eps_greedy(K):
@@ -206,43 +160,7 @@ def test_returns_and_td_target_bit_exact(K):
 @pytest.mark.parametrize('algo,A,B,literal', [('a3c', 6, 40, False), ('a3c', 6, 300, False),
                                               ('a3c', 4, 13, True), ('q', 6, 64, False), ('q', 4, 7, False)])
 def test_loss_backward_matches_oracle(K, algo, A, B, literal):
-    net = K.Net(A, algo)
-    p = make_params(net, seed=B + 11, scale=4.0)
-    rng = np.random.default_rng(B + 7)
-    planes = rng.integers(0, 256, (B, 4, 84, 84), dtype=np.uint8)
-    actions = rng.integers(0, A, B).astype(np.int32)
-    target = rng.standard_normal(B).astype(np.float32)
-    flat = net.flatten(p)
-    states = cu(planes)
-    fwd = net.forward(flat, states)
-    grads, loss = net.loss_backward(flat, states, fwd, cu(actions), cu(target), beta=0.01, literal_adv=literal)
-    zw = A + 1 if algo == 'a3c' else A
-
-    def oracle(ref_f):
-        if algo == 'a3c':
-            losses, dz = R.a3c_loss_and_dz(ref_f['z'], actions, target.astype(np.float64), 0.01, literal)
-            ref_loss = [losses['policy'], losses['value'], losses['entropy'], losses['total']]
-        else:
-            l, dz = R.q_loss_and_dz(ref_f['z'], actions, target.astype(np.float64))
-            ref_loss = [l, ref_f['z'][np.arange(B), actions].mean()]
-        return R.backward(p, ref_f, dz, algo), ref_loss
-
-    gv = net.unflatten(grads)
-    lg = loss.cpu().numpy()
-    # (1) backward arithmetic: oracle on the GPU's activations -> 1e-4 relative per tensor
-    g_ref, ref_loss = oracle(oracle_fwd_from_gpu(planes, fwd, zw))
-    for name, _ in net.names_shapes:
-        err = rel_l2(gv[name].cpu().numpy(), g_ref[name].reshape(gv[name].shape))
-        assert err < 1e-4, (name, err)
-    for i, r in enumerate(ref_loss):
-        assert abs(lg[i] - r) <= 1e-5 * max(1.0, abs(r)), (i, lg[i], r)
-    # (2) fully independent fp64 oracle: losses 1e-4 (north star 1e-3); grads 2e-2 (ReLU mask flips)
-    g_ref, ref_loss = oracle(R.forward(p, R.states_nhwc(planes), algo, dtype=np.float64))
-    for name, _ in net.names_shapes:
-        err = rel_l2(gv[name].cpu().numpy(), g_ref[name].reshape(gv[name].shape))
-        assert err < 2e-2, (name, err)
-    for i, r in enumerate(ref_loss):
-        assert abs(lg[i] - r) <= 1e-4 * max(1.0, abs(r)), (i, lg[i], r)
+    check_loss_backward(K, algo, A, B, literal)
 
 
 def test_clip_rmsprop_matches_oracle(K):

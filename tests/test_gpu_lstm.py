@@ -122,8 +122,10 @@ def same_act_grads(slot, planes, P, A, n, E, tgt, terms):
     return losses, {k: np.asarray(v, np.float32).reshape(P[k].shape) for k, v in g.items()}
 
 
-@pytest.mark.parametrize('A,E,n,lives', [(6, 8, 5, 3), (4, 20, 3, 5)])
+@pytest.mark.parametrize('A,E,n,lives', [(6, 8, 5, 3), (4, 20, 3, 5), (18, 8, 3, 3)])
 def test_engine_lstm_matches_oracle(A, E, n, lives):
+    """(A = 18: the LSTM head on h through the wide head_row at W = 256 and the wide categorical
+    select_with, rows of stride zs = 20 through k_head_bwd and the head GEMM.)"""
     eng, ref, ns = build(A, E, n, lives, seed=300 + E, learning_rate=2e-3)
     for it in range(4):
         Pk = unflat(eng, ns, eng.params)

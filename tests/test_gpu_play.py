@@ -90,9 +90,12 @@ def test_play_life_loss_is_no_terminal():
 
 # ------------------------------------------------------------------ 6. small and odd shapes
 @pytest.mark.parametrize('E,n_episode,n_step,kw', [(6, 9, 16, {}), (6, 9, 16, dict(frame84=1)), (1, 3, 16, {}),
-                                                   (37, 37, 6, {})])
+                                                   (37, 37, 6, {}), (6, 9, 16, dict(A=18))])
 def test_play_small_shapes(E, n_episode, n_step, kw):
-    eng, ref, _ = build('a3c', 4, E, 5, lives=0, seed=40 + E, **kw)
+    """(A = 18: the play tail's head with the wide head_row and the wide select_with, traced rows of
+    stride zs = 20.)"""
+    kw = dict(kw)
+    eng, ref, _ = build('a3c', kw.pop('A', 4), E, 5, lives=0, seed=40 + E, **kw)
     check_play(eng, ref_like(ref), n_episode, n_step, tag=(E, n_episode, kw))
 
 
