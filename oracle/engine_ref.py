@@ -18,6 +18,14 @@ from .synthetic_env import SyntheticAtari, pool_frame, pool_frame84
 EP_END_CHOICES = np.array([0.1, 0.01, 0.5], np.float32)   # main.py:68
 
 
+def acts_batch(fwd):
+    """Layer outputs of a ref_cpu.forward(keep=True) result as float32: l1, l2, (l3,) NHWC conv
+    outputs and h3, the fc output (b = t*E + e)."""
+    ab = {f'l{i}': np.asarray(a, np.float32) for i, a in enumerate(fwd['acts']) if i > 0}
+    ab['h3'] = np.asarray(fwd['h3'], np.float32)
+    return ab
+
+
 class EngineRef:
     def __init__(self, params, num_envs, n_step, action_size, algo='a3c', start_lives=0, num_frames=64,
                  seed=123, env_id_base=0, world_size=1, random_start=30, action_repeat=1,
@@ -139,7 +147,9 @@ class EngineRef:
         """One iteration; returns a dict of everything the GPU engine exposes.  grads=False stops
         after the rollout and its targets (no batch forward / backward: for callers that
         back-propagate the engine's own saved activations instead); grads='losses' adds the
-        independent batch forward and its losses, without the backward."""
+        independent batch forward and its losses, without the backward.  Whenever the batch
+        forward runs, out['acts_batch'] holds its layer outputs as float32 (l1, l2, (l3,) h3; the
+        LSTM sequence is out['lstm'])."""
         E, n, A, h = self.E, self.n, self.A, self.h
         acts = np.zeros((n, E), np.int32)
         sampled = np.zeros((n, E), np.int32)
@@ -202,6 +212,10 @@ class EngineRef:
             out['lstm'] = fwd['lstm']
         else:
             fwd = R.forward(self.params, states, self.algo, self.dqn_type, dtype=self.dtype)
+        # the independent forward's layer outputs (b = t*E + e, NHWC), for comparison with the
+        # engine's saved activations; float32 and without the normalised input fwd['acts'][0],
+        # which at 8,192 samples is 1.8 GB in fp64 (the outputs: about 0.3 GB per rollout)
+        out['acts_batch'] = acts_batch(fwd)
         flat_acts = acts.reshape(-1)
         if self.algo == 'a3c':
             losses, dz = R.a3c_loss_and_dz(fwd['z'], flat_acts, target.reshape(-1).astype(self.dtype),

@@ -9,14 +9,48 @@ own action draws, then asserts:
   * losses within 1e-4 of max(1, |loss|) (north star: 1e-3);
   * gradients within 1e-4 relative-L2 of the fp64 oracle backward on the engine's own saved
     activations (same ReLU masks), and within 2e-2 of the fully independent fp64 forward+backward;
+  * the saved activations themselves (act_l*, and the LSTM sequence) within 1e-4 of the oracle's
+    independent fp64 batch forward (assert_saved_acts);
   * parameters after clip + RMSProp within 1e-5 over the iterations.
+
+Three legs, because no two of them see everything:
+  1. same-activation gradients (1e-4): pins the backward kernels, but believes whatever the engine
+     saved -- a stale or misplaced sample in act_l* passes it trivially;
+  2. independent gradients (2e-2; the bound leaves room for ReLU-mask flips at fp32): pins the
+     whole update against an fp64 forward + backward that never saw the engine's buffers, but the
+     gradient is a sum over the batch in which a sample weighs as much as its dz (a3c: its
+     advantage R - V), so one wrong sample can be diluted below the bound.  Measured with the
+     oracle alone (nips trunk, A = 6, init stddev 0.08, seed 131, the first rollout): sample b's
+     saved l1 / l2 / h3 replaced by sample b+1's and back-propagated, the largest rel-L2 change
+     over the weight tensors, per replaced sample:
+
+       batch                          min      median   max      under 2e-2     that sample's l1
+       a3c, B = 40   (E = 8,   n = 5) 0.007    0.086    0.75     3 of 40        off by >= 0.35
+       a3c, B = 1280 (E = 256, n = 5) 0.0001   0.0022   0.050    37 of 40 (*)   off by >= 0.35
+       q,   B = 40                    0.0002   0.042    0.061    5 of 40        off by >= 0.32
+                                                   (*) every 32nd sample      (layer max 1.0)
+
+     (a3c, B = 40, two updates later: 21 of 40 under 2e-2.)  At the shapes the bench runs, a whole
+     stale sample passes the 2e-2 check nine times in ten; at the small shapes, whenever its
+     advantage is small (tests/test_parity_checks_cpu.py asserts that for the least-advantage
+     sample);
+  3. saved activations against the independent forward (1e-4, the bound of assert_z for the same
+     class of arithmetic): a stale sample misses it by more than three orders of magnitude.  This
+     is the failure the overlap pipeline is exposed to -- a slot is written by the rollout stream
+     and read one iteration later by the backward stream, and the fused kernel writes step t+1's
+     l1 / l2 from step t's launch, across the slot boundary -- so the overlap checks run it on slot
+     k-1 after iterate() k, the buffer the backward just consumed.
+Every check_* asserts all three plus the independent loss.  Q-learning on the overlap pipeline
+forms its TD targets late (with the target network as it stands after rollout k), so its
+independent leg is q_independent on those late targets, not the rollout-time oracle batch.
+The largest independent rel-L2 a check saw is printed at its end and kept in INDEPENDENT_MAX.
 Reference: agent.py:141-207 (act / observe / batch_update), agent.py:306-321 (loss, clip, apply),
 network.py:60-94 + assets/a3c.png (A3C losses, n-step returns), main.py:63-65 (RMSProp)."""
 import numpy as np
 import torch
 
 from oracle import ref_cpu as Rc
-from oracle.engine_ref import EngineRef
+from oracle.engine_ref import EngineRef, acts_batch
 
 
 def rel_l2(a, b):
@@ -79,6 +113,66 @@ def same_act_grads(slot, planes, P, algo, A, n, E, tgt):
         losses = dict(loss=loss)
     gr = Rc.backward(P, fwd, dz, algo, 'nature' if nature else 'nips')
     return losses, {k: np.asarray(v, np.float32).reshape(P[k].shape) for k, v in gr.items()}
+
+
+def assert_saved_acts(slot, out, n, E, tag, rtol=1e-4):
+    """A slot's saved trunk activations (and, with the LSTM head, its sequence buffers) against
+    the oracle's independent fp64 batch forward out['acts_batch'] (/ out['lstm']), in the layouts
+    same_act_grads assumes (NHWC rows, b = t*E + e).  Bound: assert_z's, for the same class of
+    arithmetic (fp32 MFMA sums against fp64); lstm_h keeps its own rtol 1e-4 / atol 2e-5."""
+    g = (lambda k: slot[k]) if isinstance(slot, dict) else (lambda k: getattr(slot, k))
+    ab = out['acts_batch']
+    layers = [k for k in ('l1', 'l2', 'l3') if k in ab] + ['h3']
+    nature = ('act_l4' in slot) if isinstance(slot, dict) else getattr(slot, 'dqn_type', 'nips') == 'nature'
+    assert len(layers) == (4 if nature else 3), (tag, layers, nature)
+    B = n * E
+    for i, k in enumerate(layers):
+        a = g(f'act_l{i + 1}').cpu().numpy()
+        r = ab[k].reshape(B, -1)
+        assert a.size == r.size, (tag, k, a.shape, r.shape)
+        np.testing.assert_allclose(a.reshape(B, -1), r, rtol=rtol, atol=rtol * max(1.0, float(np.abs(r).max())),
+                                   err_msg=str((tag, f'act_l{i + 1}')))
+    if 'lstm' in out:
+        seq = out['lstm']
+        np.testing.assert_allclose(g('lstm_h').cpu().numpy(), seq['H'], rtol=1e-4, atol=2e-5,
+                                   err_msg=str((tag, 'lstm_h')))
+        for key, rk in (('lstm_c', 'C'), ('lstm_gates', 'G')):
+            r = np.asarray(seq[rk])
+            np.testing.assert_allclose(g(key).cpu().numpy(), r, rtol=rtol,
+                                       atol=rtol * max(1.0, float(np.abs(r).max())), err_msg=str((tag, key)))
+
+
+INDEPENDENT_MAX = {}     # label of a check -> the largest independent rel-L2 it saw
+
+
+def assert_independent_grads(G, ref_grads, names, tag, worst=None, bound=2e-2):
+    """Every gradient tensor within `bound` relative-L2 of the fully independent fp64 forward +
+    backward (ReLU-mask flips at fp32 allowed); worst: a dict collecting the per-tensor maxima."""
+    for name in names:
+        r = float(rel_l2(G[name], ref_grads[name]))
+        if worst is not None:
+            worst[name] = max(worst.get(name, 0.0), r)
+        assert r < bound, (tag, name, r)
+
+
+def report_independent(label, worst):
+    """Log the headroom of a check's 2e-2 assertions (run pytest with -s to see it)."""
+    top = max(worst.values()) if worst else 0.0
+    INDEPENDENT_MAX[label] = top
+    print(f'independent rel-L2 max {label}: {top:.3e} ' +
+          ' '.join(f'{k}={v:.1e}' for k, v in sorted(worst.items())))
+    return top
+
+
+def q_independent(P, planes, actions, want):
+    """The independent leg of Q-learning for given (late) TD targets: the oracle's own fp64 forward
+    of the rollout's states with parameters P, its loss against `want` and its backward.
+    Returns (losses, z [B, A], gradients, acts_batch)."""
+    fwd = Rc.forward(P, Rc.states_nhwc(planes), 'q')
+    loss, dz = Rc.q_loss_and_dz(fwd['z'], np.asarray(actions).reshape(-1), np.asarray(want, np.float64).reshape(-1))
+    ab = acts_batch(fwd)
+    g = Rc.backward(P, fwd, dz, 'q')
+    return dict(loss=loss), fwd['z'], {k: np.asarray(v, np.float32).reshape(P[k].shape) for k, v in g.items()}, ab
 
 
 def rollout_planes(ref, n):
@@ -178,6 +272,7 @@ def check_sync_vs_oracle(algo, A, E, n, lives, iters=3, seed=None, frames=48, sc
     if pool is None:
         assert np.array_equal(eng.env_frame.cpu().numpy(), ref.env.frame.astype(np.int32))
     R = eng.ring_slots
+    worst = {}
     ring = eng.frame_ring.cpu().numpy()
     for c in range(4):
         assert np.array_equal(ring[:, c % R], ref.ring[:, c % R])
@@ -194,6 +289,7 @@ def check_sync_vs_oracle(algo, A, E, n, lives, iters=3, seed=None, frames=48, sc
         z_eng = eng.z.cpu().numpy()[:n].reshape(n, E, -1)
         assert_draws_explained(acts, out, algo, A, it, z_eng=z_eng)
         assert_z(z_eng, out['z'], zw, it)
+        assert_saved_acts(eng, out, n, E, ('saved', it))
         assert np.array_equal(eng.rewards.cpu().numpy(), out['rewards']), it
         assert np.array_equal(eng.terminals.cpu().numpy(), out['terminals']), it
         gr = eng.frame_ring.cpu().numpy()
@@ -208,8 +304,8 @@ def check_sync_vs_oracle(algo, A, E, n, lives, iters=3, seed=None, frames=48, sc
         _, g_same = same_act_grads(eng, planes, Pk, algo, A, n, E, tgt)
         for name, _ in ns:
             assert rel_l2(G[name], g_same[name]) < 1e-4, (it, name, rel_l2(G[name], g_same[name]))
-            if independent:     # fully independent fp64 oracle: ReLU-mask flips allowed
-                assert rel_l2(G[name], out['grads'][name]) < 2e-2, (it, name)
+        if independent:     # fully independent fp64 oracle: ReLU-mask flips allowed
+            assert_independent_grads(G, out['grads'], [name for name, _ in ns], it, worst)
         eng.apply()
         torch.cuda.synchronize()
         ss = eng.sumsq.cpu().numpy()
@@ -229,18 +325,23 @@ def check_sync_vs_oracle(algo, A, E, n, lives, iters=3, seed=None, frames=48, sc
                 np.testing.assert_allclose(T[name], ref.tparams[name], rtol=1e-5, atol=1e-6)
     if pool is not None:
         pool.close()
+    report_independent(f'sync {algo} A={A} E={E} n={n} {eng.dqn_type}', worst)
     return eng, ref
 
 
 def check_overlap_vs_oracle(A, E, n, lives, rollouts=5, seed=77, frames=48, scale=4.0, algo='a3c', hogwild=False,
-                            grads=True, **kw):
+                            **kw):
     """Overlap (stale-1) pipeline: rollout k uses the parameters after update k-2.  The oracle is
     replayed in that order with the engine's own actions and activations.  algo='q': the TD targets
     of rollout k-1 are formed by its backward, after rollout k, with the target network as it
     stands then (synced by apply k-2 at the latest), so the replay recomputes them from the
     rollout's next-state planes with the oracle's target parameters at that point.
     hogwild=True: the engine runs Engine.iterate_hogwild on a one-shard HogwildPS (the clipped
-    gradient of rollout k-1 pushed and the shard pulled under rollout k): the same stale-1 replay."""
+    gradient of rollout k-1 pushed and the shard pulled under rollout k): the same stale-1 replay.
+    After iterate() k, slot k-1 -- the buffer the backward just consumed -- is held against the
+    independent forward of rollout k-1 (assert_saved_acts), and the engine's loss, head rows and
+    gradient against the independent leg (q: q_independent on the late targets; hogwild: the
+    clipped independent gradient, the engine's buffer being clipped in place)."""
     if algo == 'q':
         kw.setdefault('target_q_update_step', 40)
     eng, ref, ns = build(algo, A, E, n, lives, seed=seed, frames=frames, scale=scale, overlap=True, **kw)
@@ -249,6 +350,8 @@ def check_overlap_vs_oracle(A, E, n, lives, rollouts=5, seed=77, frames=48, scal
         from src.hogwild import HogwildPS
         ps = HogwildPS(eng.params)
     hist = []                  # per rollout: (oracle params used, planes, oracle out)
+    worst = {}
+    names = [name for name, _ in ns]
     for k in range(rollouts):
         if ps is not None:
             eng.iterate_hogwild(ps)
@@ -257,7 +360,8 @@ def check_overlap_vs_oracle(A, E, n, lives, rollouts=5, seed=77, frames=48, scal
         torch.cuda.synchronize()
         sl = eng.slot(k & 1)
         Pk = {kk: v.copy() for kk, v in ref.params.items()}
-        out = ref.iterate(forced_actions=sl['actions'].cpu().numpy(), grads=grads)
+        # (q: the batch forward + backward wait for the late targets, see q_independent below)
+        out = ref.iterate(forced_actions=sl['actions'].cpu().numpy(), grads=algo != 'q')
         planes = rollout_planes(ref, n)
         if algo == 'q':                                 # s_{t+1} of every step, for the late TD target
             out['next_states'] = np.concatenate([ref.states(ref.tau + t + 1) for t in range(n)])
@@ -293,19 +397,25 @@ def check_overlap_vs_oracle(A, E, n, lives, rollouts=5, seed=77, frames=48, scal
         np.testing.assert_allclose(tgt, want, rtol=1e-5, atol=1e-5)
         losses, g_same = same_act_grads(slp, planes_p, Pp, algo, A, n, E, tgt)
         assert_losses(eng.loss.cpu().numpy(), losses, algo, k)
-        if algo == 'a3c':
-            # independent: the oracle's own fp64 batch forward of rollout k-1 (its logits, values
-            # and bootstrap targets), not the engine's saved activations
-            assert_losses(eng.loss.cpu().numpy(), out_p['losses'], algo, ('independent', k))
-            assert_z(slp['z'].cpu().numpy()[:n].reshape(n * E, -1), out_p['z_batch'], A + 1, ('z_batch', k))
+        # independent: the oracle's own fp64 batch forward of rollout k-1 (its logits, values and
+        # bootstrap targets / q rows), not the engine's saved activations.  q: formed here, with the
+        # late targets (the rollout-time oracle targets are not the ones the backward used)
+        if algo == 'q':
+            ind_losses, z_ind, g_ind, out_p['acts_batch'] = q_independent(Pp, planes_p, out_p['actions'], want)
+        else:
+            ind_losses, z_ind, g_ind = out_p['losses'], out_p['z_batch'], out_p['grads']
+        assert_saved_acts(slp, out_p, n, E, ('saved', k))
+        assert_losses(eng.loss.cpu().numpy(), ind_losses, algo, ('independent', k))
+        assert_z(slp['z'].cpu().numpy()[:n].reshape(n * E, -1), z_ind, zw, ('z_batch', k))
         G = unflat(eng, ns, eng.grads)
         if ps is not None:     # (hogwild clips the buffer in place before its push)
             g_same_c = {kk: Rc.clip_by_norm(v, 40.0) for kk, v in g_same.items()}
-        for name, _ in ns:
+            g_ind = {kk: Rc.clip_by_norm(v, 40.0) for kk, v in g_ind.items()}
+        for name in names:
             want_g = g_same_c[name] if ps is not None else g_same[name]
             assert rel_l2(G[name], want_g) < 1e-4, (k, name, rel_l2(G[name], want_g))
-            if algo == 'a3c' and ps is None:    # (q: the rollout-time oracle targets are not the late ones)
-                assert rel_l2(G[name], out_p['grads'][name]) < 2e-2, (k, name)
+        assert_independent_grads(G, g_ind, names, k, worst)
+        out_p.pop('acts_batch', None)       # (checked; the replay keeps every rollout's out alive)
         ref.apply({kk: Rc.clip_by_norm(v, 40.0) for kk, v in g_same.items()}, advance_tau=False, tau=out_p['tau'])
         assert_params(eng, ns, ref, k)
         if ps is not None:
@@ -317,6 +427,7 @@ def check_overlap_vs_oracle(A, E, n, lives, rollouts=5, seed=77, frames=48, scal
                 np.testing.assert_allclose(T[name], ref.tparams[name], rtol=1e-5, atol=1e-6)
     if ps is not None:
         ps.close()
+    report_independent(f"overlap{'-hogwild' if hogwild else ''} {algo} A={A} E={E} n={n} {eng.dqn_type}", worst)
     return eng, ref
 
 
@@ -328,23 +439,33 @@ def check_hogwild1_vs_oracle(A, E, n, lives, iters=3, seed=91, frames=48, scale=
     algo = 'a3c'
     eng, ref, ns = build(algo, A, E, n, lives, seed=seed, frames=frames, scale=scale, **kw)
     ps = HogwildPS(eng.params)
+    worst = {}
+    names = [name for name, _ in ns]
     try:
         for it in range(iters):
             Pk = unflat(eng, ns, eng.params)
             eng.iterate_hogwild(ps)
             torch.cuda.synchronize()
-            out = ref.iterate(forced_actions=eng.actions.cpu().numpy())
+            acts = eng.actions.cpu().numpy()
+            out = ref.iterate(forced_actions=acts)
             planes = rollout_planes(ref, n)
+            z_eng = eng.z.cpu().numpy()[:n].reshape(n, E, -1)
+            assert_draws_explained(acts, out, algo, A, it, z_eng=z_eng)
+            assert_z(z_eng, out['z'], A + 1, it)
+            assert_saved_acts(eng, out, n, E, ('saved', it))
             assert np.array_equal(eng.rewards.cpu().numpy(), out['rewards']), it
             assert np.array_equal(eng.terminals.cpu().numpy(), out['terminals']), it
             tgt = eng.returns.cpu().numpy()
             np.testing.assert_allclose(tgt, out['target'], rtol=1e-5, atol=1e-5)
             losses, g_same = same_act_grads(eng, planes, Pk, algo, A, n, E, tgt)
             assert_losses(eng.loss.cpu().numpy(), losses, algo, it)
+            assert_losses(eng.loss.cpu().numpy(), out['losses'], algo, ('independent', it))
             clipped = {k: Rc.clip_by_norm(v, 40.0) for k, v in g_same.items()}
             G = unflat(eng, ns, eng.grads)        # the engine's buffer holds the clipped gradient
-            for name, _ in ns:
+            for name in names:
                 assert rel_l2(G[name], clipped[name]) < 1e-4, (it, name)
+            assert_independent_grads(G, {k: Rc.clip_by_norm(v, 40.0) for k, v in out['grads'].items()}, names, it,
+                                     worst)
             ref.apply(clipped)
             assert_params(eng, ns, ref, it)
             assert torch.equal(ps.gather(), eng.params)
@@ -352,4 +473,5 @@ def check_hogwild1_vs_oracle(A, E, n, lives, iters=3, seed=91, frames=48, scale=
             assert cnt[0] == ref.tau and cnt[1] == ref.global_step
     finally:
         ps.close()
+    report_independent(f'hogwild-sync a3c A={A} E={E} n={n}', worst)
     return eng, ref

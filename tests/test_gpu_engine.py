@@ -8,8 +8,8 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip('torch')
 
-from _engine_parity import (build, check_overlap_vs_oracle, check_sync_vs_oracle,  # noqa: E402
-                            rel_l2)
+from _engine_parity import (build, check_hogwild1_vs_oracle, check_overlap_vs_oracle,  # noqa: E402
+                            check_sync_vs_oracle, rel_l2)
 
 
 @pytest.mark.parametrize('algo,A,E,n,lives', [('a3c', 6, 8, 5, 0), ('a3c', 4, 6, 3, 5), ('q', 6, 4, 8, 3),
@@ -170,6 +170,19 @@ def test_double_q_matches_oracle(overlap):
                                 target_q_update_step=100, double_q=1)
     else:
         check_sync_vs_oracle('q', 6, 4, 8, 3, iters=4, learning_rate=3e-3, double_q=1)
+
+
+@pytest.mark.parametrize('E', [8, 37])
+@pytest.mark.parametrize('mode', ['overlap', 'sync'])
+def test_hogwild_world1_matches_oracle(mode, E):
+    """Hogwild at world 1 (src/hogwild.py: per-worker clip, unlocked RMSProp push into the sharded
+    PS, pull) at small shapes, overlapped with the next rollout at staleness 1 or after each rollout:
+    every bar of the plain update modes, the saved activations and the clipped independent gradient
+    included (E = 37: a ragged row block, as in the a3c overlap test)."""
+    if mode == 'overlap':
+        check_overlap_vs_oracle(6, E, 5, 0, rollouts=5, seed=81, learning_rate=3e-3, hogwild=True)
+    else:
+        check_hogwild1_vs_oracle(6, E, 5, 0, iters=3, seed=83, learning_rate=3e-3)
 
 
 def test_stream_ordering_modes_are_bit_identical(monkeypatch):

@@ -23,8 +23,9 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip('torch')
 
-from _engine_parity import (assert_draws_explained, check_hogwild1_vs_oracle, check_overlap_vs_oracle,  # noqa: E402
-                            check_sync_vs_oracle)
+from _engine_parity import (assert_draws_explained, assert_independent_grads, assert_saved_acts,  # noqa: E402
+                            check_hogwild1_vs_oracle, check_overlap_vs_oracle, check_sync_vs_oracle,
+                            report_independent)
 
 
 FRAMES = 512     # pool frames: more than the envs, so every env reads its own frames
@@ -85,11 +86,14 @@ def test_c4_512_env_shard_matches_oracle(mode):
 def test_c5_lstm_shard_matches_oracle():
     """C5 per GPU: SpaceInvaders (A=6, 3 lives), LSTM head, 256 envs, n=5, synchronous engine,
     against the restated oracle (the reference has no recurrent code: parity unpinned against
-    a reference execution)."""
+    a reference execution).  The per-step head rows, the saved trunk activations and
+    LSTM sequence, the losses and the gradients (2e-2) are held against the oracle's independent
+    fp64 forward + backward as at the small shapes (tests/test_gpu_lstm.py)."""
     from test_gpu_lstm import build, same_act_grads, unflat, rel_l2
     from oracle import ref_cpu as Rc
     A, E, n = 6, 256, 5
     eng, ref, ns = build(A, E, n, 3, seed=55, frames=FRAMES, scale=2.0, learning_rate=2e-3)
+    worst = {}
     for it in range(2):
         Pk = unflat(eng, ns, eng.params)
         eng.rollout_grad()
@@ -101,7 +105,10 @@ def test_c5_lstm_shard_matches_oracle():
         assert np.array_equal(eng.rewards.cpu().numpy(), out['rewards'])
         terms = eng.terminals.cpu().numpy()
         assert np.array_equal(terms, out['terminals'])
+        z = eng.z.cpu().numpy()[:n, :, :A + 1]
+        np.testing.assert_allclose(z, out['z'][:, :, :A + 1], rtol=1e-4, atol=2e-5)
         np.testing.assert_allclose(eng.lstm_h.cpu().numpy(), out['lstm']['H'], rtol=1e-4, atol=2e-5)
+        assert_saved_acts(eng.slot(0), out, n, E, ('saved', it))
         tgt = eng.returns.cpu().numpy()
         np.testing.assert_allclose(tgt, out['target'], rtol=1e-4, atol=2e-5)
         losses, g_same = same_act_grads(eng.slot(0), planes, Pk, A, n, E, tgt, terms)
@@ -114,6 +121,7 @@ def test_c5_lstm_shard_matches_oracle():
         G = unflat(eng, ns, eng.grads)
         for name, _ in ns:
             assert rel_l2(G[name], g_same[name]) < 1e-4, (it, name, rel_l2(G[name], g_same[name]))
+        assert_independent_grads(G, out['grads'], [name for name, _ in ns], it, worst)
         eng.apply()
         ref.apply({k: Rc.clip_by_norm(v, 40.0) for k, v in g_same.items()})
         torch.cuda.synchronize()
@@ -121,6 +129,7 @@ def test_c5_lstm_shard_matches_oracle():
         for name, _ in ns:
             d = np.abs(P[name] - ref.params[name]).max()
             assert d <= 1e-5 * max(1.0, np.abs(ref.params[name]).max()), (it, name, d)
+    report_independent('c5 lstm sync E=256', worst)
 
 
 @pytest.mark.timeout(900)

@@ -13,7 +13,8 @@ torch = pytest.importorskip('torch')
 
 from oracle import ref_cpu as Rc  # noqa: E402
 from oracle.engine_ref import EngineRef  # noqa: E402
-from _engine_parity import assert_draws_explained  # noqa: E402
+from _engine_parity import (assert_draws_explained, assert_independent_grads, assert_saved_acts,  # noqa: E402
+                            report_independent)
 
 U = 256
 
@@ -144,6 +145,8 @@ def test_engine_lstm_matches_oracle(A, E, n, lives):
         z = eng.z.cpu().numpy()[:n, :, :A + 1]
         np.testing.assert_allclose(z, out['z'][:, :, :A + 1], rtol=1e-4, atol=2e-5)
         np.testing.assert_allclose(eng.lstm_h.cpu().numpy(), out['lstm']['H'], rtol=1e-4, atol=2e-5)
+        # the saved trunk activations and LSTM sequence vs the independent fp64 batch forward
+        assert_saved_acts(eng.slot(0), out, n, E, ('saved', it))
         tgt = eng.returns.cpu().numpy()
         np.testing.assert_allclose(tgt, out['target'], rtol=1e-4, atol=2e-5)
         planes = np.concatenate([np.transpose(ref.states(ref.tau + t), (0, 3, 1, 2)) for t in range(n)])
@@ -233,17 +236,22 @@ def test_engine_lstm_overlap_matches_oracle(E, frames):
     """The pipelined C5 engine (bench.py --lstm: rollout k on the parameters after update k-2) against
     the oracle replayed in that order with the engine's own actions: per-step outputs, returns,
     losses, gradients on the engine's own saved activations and LSTM sequence, and parameters.  The
-    fc arrives at the cell as K-slice partials folded by k_lstm_fwd (act_l3 written there)."""
+    fc arrives at the cell as K-slice partials folded by k_lstm_fwd (act_l3 written there).
+    After iterate() k, slot k-1 (the buffers the backward just consumed) is held against the oracle's
+    independent fp64 forward of rollout k-1: trunk activations, lstm_h / lstm_c / lstm_gates, losses
+    and gradients (2e-2, the bound of the synchronous test)."""
     from _engine_parity import rollout_planes
     A, n = 6, 5
     eng, ref, ns = build(A, E, n, 3, seed=60 + E, frames=frames, scale=2.0, learning_rate=2e-3, overlap=True)
     hist = []
+    worst = {}
+    names = [name for name, _ in ns]
     for k in range(4):
         eng.iterate()
         torch.cuda.synchronize()
         sl = eng.slot(k & 1)
         Pk = {kk: v.copy() for kk, v in ref.params.items()}
-        out = ref.iterate(forced_actions=sl['actions'].cpu().numpy(), grads='losses')
+        out = ref.iterate(forced_actions=sl['actions'].cpu().numpy())
         planes = rollout_planes(ref, n)
         ref.tau += n
         assert np.array_equal(sl['rewards'].cpu().numpy(), out['rewards']), k
@@ -260,6 +268,8 @@ def test_engine_lstm_overlap_matches_oracle(E, frames):
         tgt = slp['returns'].cpu().numpy()
         np.testing.assert_allclose(tgt, out_p['target'], rtol=1e-4, atol=2e-5)
         terms = slp['terminals'].cpu().numpy()
+        np.testing.assert_allclose(slp['lstm_h'].cpu().numpy(), out_p['lstm']['H'], rtol=1e-4, atol=2e-5)
+        assert_saved_acts(slp, out_p, n, E, ('saved', k))
         losses, g_same = same_act_grads(slp, planes_p, Pp, A, n, E, tgt, terms)
         loss = eng.loss.cpu().numpy()
         for i, key in enumerate(('policy', 'value', 'entropy', 'total')):
@@ -270,8 +280,10 @@ def test_engine_lstm_overlap_matches_oracle(E, frames):
         G = unflat(eng, ns, eng.grads)
         for name, _ in ns:
             assert rel_l2(G[name], g_same[name]) < 1e-4, (k, name, rel_l2(G[name], g_same[name]))
+        assert_independent_grads(G, out_p['grads'], names, k, worst)
         ref.apply({kk: Rc.clip_by_norm(v, 40.0) for kk, v in g_same.items()}, advance_tau=False, tau=out_p['tau'])
         P = unflat(eng, ns, eng.params)
         for name, _ in ns:
             d = np.abs(P[name] - ref.params[name]).max()
             assert d <= 1e-5 * max(1.0, np.abs(ref.params[name]).max()), (k, name, d)
+    report_independent(f'lstm overlap E={E}', worst)
