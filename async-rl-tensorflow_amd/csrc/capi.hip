@@ -124,6 +124,17 @@ extern "C" int a3c_returns(const float* rewards, const uint8_t* terminals, const
   return a3c_returns_launch(rewards, terminals, bootstrap, 1, n, E, gamma, R, (hipStream_t)stream);
 }
 
+extern "C" int a3c_gae_returns(const float* rewards, const uint8_t* terminals, const float* values,
+                               int64_t value_stride, const float* bootstrap, int n, int64_t E, double gamma,
+                               double lambda, float* R, float* adv, void* stream) {
+  if (!rewards || !terminals || !values || !bootstrap || !R || n < 1 || E < 0 || value_stride < 1)
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_gae_returns", "bad argument");
+  if (!(lambda >= 0.0 && lambda <= 1.0))
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_gae_returns", "lambda must be in [0, 1]");
+  return a3c_gae_launch(rewards, terminals, values, value_stride, bootstrap, 1, n, E, gamma, lambda, R, adv,
+                        (hipStream_t)stream);
+}
+
 extern "C" int a3c_td_target(const float* rewards, const uint8_t* terminals, const float* q_next, int64_t B,
                              int A, int zs, double discount, float* target, void* stream) {
   if (!rewards || !terminals || !q_next || !target || B < 0 || A < 1 || zs < A)

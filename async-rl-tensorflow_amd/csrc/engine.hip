@@ -206,6 +206,7 @@ extern "C" void a3c_engine_config_default(a3c_engine_config* c) {
   c->learn_start = 32;
   c->target_q_update_step = 40000LL;
   c->discount = 0.99;
+  c->gae_lambda = 1.0f;    // the n-step return (GAE(1)); DESIGN §4f
   c->split_exchange = 1;   // several GPUs: the fc / head exchange under the conv backward
 }
 
@@ -252,6 +253,19 @@ extern "C" int a3c_engine_create(const a3c_engine_config* cfg, a3c_engine** out)
   if (cfg->double_q && cfg->net.algo != A3C_ALGO_Q) {
     delete e;
     return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_create", "double_q is a Q-learning option (agent.py:176-184)");
+  }
+  if (!(cfg->gae_lambda >= 0.f && cfg->gae_lambda <= 1.f)) {
+    delete e;
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_create", "gae_lambda must be in [0, 1]");
+  }
+  if (cfg->gae_lambda != 1.f && cfg->net.algo != A3C_ALGO_A3C) {
+    delete e;
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_create", "gae_lambda != 1 is an a3c option (algo q has one-step TD targets)");
+  }
+  if (cfg->gae_lambda != 1.f && cfg->literal_adv) {
+    delete e;
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_create",
+                         "gae_lambda != 1 with literal_adv: the lambda-return is a constant of the gradient");
   }
   a3c_init_once();
   const NetLayout& L = e->L;
@@ -1010,6 +1024,9 @@ static int enqueue_grad_impl(a3c_engine* e, const Slot& sl, hipStream_t s) {
   if (!q) {   // n-step returns computed inside the head backward (assets/a3c.png)
     ra.rewards = sl.rewards; ra.terms = sl.terms; ra.boot = sl.z + e->nE * zs + L.A; ra.boot_stride = zs;
     ra.n = n; ra.E = E; ra.gamma = c.gamma; ra.R_out = sl.R_buf;
+    if (c.gae_lambda != 1.f) {   // GAE(lambda): the rollout's own V rows z[:, A]
+      ra.values = sl.z + L.A; ra.value_stride = zs; ra.lambda = (double)c.gae_lambda;
+    }
   }
   static const bool fork_env = A3C_AB_KNOB("A3C_BWD_FORK", 0) != 0;  // measured slower
   const bool fork = fork_env && !L.lstm;

@@ -75,6 +75,10 @@ struct ReturnsArgs {
   int64_t E;
   double gamma;
   float* R_out;              // [n*E] the returns (inspection)
+  // GAE(lambda) (values != nullptr): the target is the lambda-return A_t + V_t of k_gae
+  const float* values;       // V(s_i) of env e at values[(i*E + e) * value_stride]: the rollout's own
+  int64_t value_stride;
+  double lambda;
 };
 
 // C5 LSTM head: the rollout's sequence buffers (engine slot) for the truncated BPTT; the
@@ -98,6 +102,9 @@ int a3c_backward_launch(const NetLayout& L, const float* params, const StateAddr
                         const SplitBwd* sp = nullptr, const uint32_t* l2m = nullptr);
 int a3c_returns_launch(const float* rewards, const uint8_t* terms, const float* boot, int64_t boot_stride,
                        int n, int64_t E, double gamma, float* R, hipStream_t s);
+int a3c_gae_launch(const float* rewards, const uint8_t* terms, const float* values, int64_t vstride,
+                   const float* boot, int64_t boot_stride, int n, int64_t E, double gamma, double lambda, float* R,
+                   float* adv, hipStream_t s);
 // qsel != nullptr: double Q-learning -- the value of qn's row at qsel's row argmax (agent.py:176-184)
 int a3c_td_target_launch(const float* rewards, const uint8_t* terms, const float* qn, int64_t B, int A,
                          int zs, double discount, float* target, hipStream_t s, const float* qsel = nullptr);

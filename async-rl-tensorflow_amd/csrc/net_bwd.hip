@@ -4,6 +4,8 @@
 //
 //  k_returns     n-step return per env in float64 (assets/a3c.png Algorithm S3).
 //  k_td_target   agent.py:186-190 in float64.
+//  k_gae         GAE(lambda) advantage and lambda-return per env in float64 (at the
+//                end of the file with k_head_bwd's GAE instantiations).
 //  k_head_bwd    one wave per sample: softmax/log-softmax/entropy, network.py:81-94 losses
 //                (A11 fixes) or agent.py:310-314 MSE, dz, dl3 = (W_h dz) * (l3 > 0).
 //  fc layer      gemm.hip: dW = l2^T dl3 (+colsum -> db), dl2 = (dl3 W^T) * (l2 > 0),
@@ -65,7 +67,9 @@ __global__ void k_td_target(const float* __restrict__ rewards, const uint8_t* __
 
 // ---------------------------------------------------------------------------------------
 // W: the head's input width (FC = 256, NIPS trunk; NT_FC = 512, nature trunk)
-template <int W>
+// GAE: the fused target is the lambda-return of k_gae (ra.values set) instead of the n-step return;
+// a separate instantiation, so the lambda = 1 kernel is the one without it
+template <int W, bool GAE>
 __global__ void __launch_bounds__(256) k_head_bwd(const float* __restrict__ z, int zs, int A, int algo,
                                                   const int32_t* __restrict__ actions,
                                                   const float* __restrict__ target,
@@ -82,7 +86,21 @@ __global__ void __launch_bounds__(256) k_head_bwd(const float* __restrict__ z, i
   const float myz = lane < zs ? z[b * zs + lane] : 0.f;
   const int a = actions[b];
   float tgt;
-  if (ra.rewards) {
+  if constexpr (GAE) {
+    // lambda-return of sample (t, e), float64 like k_gae: the rollout's own V rows
+#pragma clang fp contract(off)
+    const int64_t t = b / ra.E, e = b - t * ra.E;
+    double vn = (double)ra.boot[e * ra.boot_stride], adv = 0.0, v = 0.0;
+    for (int64_t i = ra.n - 1; i >= t; --i) {
+      const double nt = ra.terms[i * ra.E + e] ? 0.0 : 1.0;
+      v = (double)ra.values[(i * ra.E + e) * ra.value_stride];
+      const double delta = (double)ra.rewards[i * ra.E + e] + ra.gamma * nt * vn - v;
+      adv = delta + ra.gamma * ra.lambda * nt * adv;
+      vn = v;
+    }
+    tgt = (float)(adv + v);
+    if (lane == 0) ra.R_out[b] = tgt;
+  } else if (ra.rewards) {
     // n-step return of sample (t, e) (assets/a3c.png), float64 like k_returns
 #pragma clang fp contract(off)
     const int64_t t = b / ra.E, e = b - t * ra.E;
@@ -882,19 +900,30 @@ __global__ void __launch_bounds__(256) k_finalize(FinalizeSegs fs, const float* 
   sumsq_chunk(fs.dst, fs.tt, t, c, fs.part, fs.tt.pb_first[t] + c);
 }
 
+// the GAE instantiations of k_head_bwd and k_gae are emitted at the end of this file, behind the
+// kernels of the lambda = 1 path, whose places in the code object they leave as they were
+static int head_bwd_gae_launch(int width, const NetLayout& L, const float* z, const int32_t* actions,
+                               const float* target, const float* h, const float* Wp, const float* Wv, float beta,
+                               int literal, int64_t B, float* dz, float* dh, float* terms, const ReturnsArgs& ra,
+                               int relu, hipStream_t s);
+
 // host launchers shared with the nature trunk's backward (nature.hip)
 int a3c_head_bwd_launch(int width, const NetLayout& L, const float* z, const int32_t* actions, const float* target,
                         const float* h, const float* Wp, const float* Wv, float beta, int literal, int64_t B,
                         float* dz, float* dh, float* terms, const ReturnsArgs& ra, int relu, hipStream_t s) {
   const dim3 grid((unsigned)((B + 3) / 4));
+  const float invB = 1.0f / (float)B;
+  const bool gae = ra.values != nullptr;
+  if (width != FC && width != 512) return a3c_set_error(A3C_ERR_INVALID, "a3c_head_bwd_launch", "head width");
+  if (gae && (!ra.rewards || !ra.terms || !ra.boot || !ra.R_out || ra.n < 1 || ra.E < 1 || B != ra.n * ra.E))
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_head_bwd_launch", "GAE needs the rollout's rewards, terminals and values");
+  if (gae) return head_bwd_gae_launch(width, L, z, actions, target, h, Wp, Wv, beta, literal, B, dz, dh, terms, ra, relu, s);
   if (width == FC)
-    hipLaunchKernelGGL(k_head_bwd<FC>, grid, dim3(256), 0, s, z, L.zs, L.A, L.algo, actions, target, h, Wp, Wv, beta,
-                       literal, 1.0f / (float)B, B, dz, dh, terms, ra, relu);
-  else if (width == 512)
-    hipLaunchKernelGGL(k_head_bwd<512>, grid, dim3(256), 0, s, z, L.zs, L.A, L.algo, actions, target, h, Wp, Wv, beta,
-                       literal, 1.0f / (float)B, B, dz, dh, terms, ra, relu);
+    hipLaunchKernelGGL((k_head_bwd<FC, false>), grid, dim3(256), 0, s, z, L.zs, L.A, L.algo, actions, target, h, Wp,
+                       Wv, beta, literal, invB, B, dz, dh, terms, ra, relu);
   else
-    return a3c_set_error(A3C_ERR_INVALID, "a3c_head_bwd_launch", "head width");
+    hipLaunchKernelGGL((k_head_bwd<512, false>), grid, dim3(256), 0, s, z, L.zs, L.A, L.algo, actions, target, h, Wp,
+                       Wv, beta, literal, invB, B, dz, dh, terms, ra, relu);
   A3C_CHECK(hipGetLastError());
   return 0;
 }
@@ -1122,10 +1151,9 @@ int a3c_backward_launch(const NetLayout& L, const float* params, const StateAddr
     return a3c_set_error(A3C_ERR_INVALID, "a3c_loss_backward", "the LSTM head needs its rollout sequence");
   // head input: the fc ReLU output, or the LSTM's h (C5)
   const float* head_in = lb ? lb->h : act_l3;
-  hipLaunchKernelGGL(k_head_bwd<FC>, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, s, z, L.zs, L.A, L.algo,
-                     actions, target, head_in, P + L.off[T_HW], a3c ? P + L.off[T_VW] : nullptr, beta,
-                     literal, 1.0f / (float)B, B, dz, lb ? lb->dh : dh3, terms, ra, lb ? 0 : 1);
-  A3C_CHECK(hipGetLastError());
+  int rch = a3c_head_bwd_launch(FC, L, z, actions, target, head_in, P + L.off[T_HW], a3c ? P + L.off[T_VW] : nullptr,
+                                beta, literal, B, dz, lb ? lb->dh : dh3, terms, ra, lb ? 0 : 1, s);
+  if (rch) return rch;
   if (lb) {
     // truncated BPTT: dL/dh_t -> dl3 (masked by the fc ReLU) + the gate-matrix gradients
     LstmSeq q = {act_l3, lb->hp, lb->cp, lb->gates, lb->c, ra.terms};
@@ -1393,6 +1421,64 @@ void a3c_conv_bwd_set_smem() {
   (void)hipFuncSetAttribute((const void*)k_conv_bwd<false, 4, false>, (hipFuncAttribute)a, cb_smem(CB_SMEM_COMPACT));
   (void)hipFuncSetAttribute((const void*)k_conv_bwd<false, 4, true>, (hipFuncAttribute)a, cb_smem(CB_SMEM_COMPACT_LX));
   (void)hipFuncSetAttribute((const void*)k_conv_bwd<false, 8, true>, (hipFuncAttribute)a, cb_smem(CB_SMEM_COMPACT_LX));
+}
+
+// ---------------------------------------------------------------------------------------
+// GAE(lambda): the stand-alone kernel and the GAE launches of k_head_bwd
+// ---------------------------------------------------------------------------------------
+// Schulman et al.: delta_i = r_i + gamma nt_i V_{i+1} - V_i, A_i = delta_i +
+// gamma lambda nt_i A_{i+1} (A_n = 0, V_n = boot), lambda-return G_i = A_i + V_i.  V_i =
+// values[(i E + e) vstride]; ADV: the advantages are written too.  lambda = 1 is k_returns'
+// n-step return.  One thread per env.
+template <bool ADV>
+__global__ void k_gae(const float* __restrict__ rewards, const uint8_t* __restrict__ terms,
+                      const float* __restrict__ values, int64_t vstride, const float* __restrict__ boot,
+                      int64_t boot_stride, int n, int64_t E, double gamma, double lambda,
+                      float* __restrict__ R, float* __restrict__ adv) {
+#pragma clang fp contract(off)
+  int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= E) return;
+  double vn = (double)boot[e * boot_stride], a = 0.0;
+  for (int i = n - 1; i >= 0; --i) {
+    const double nt = terms[i * E + e] ? 0.0 : 1.0;
+    const double v = (double)values[(i * E + e) * vstride];
+    const double delta = (double)rewards[i * E + e] + gamma * nt * vn - v;
+    a = delta + gamma * lambda * nt * a;
+    R[i * E + e] = (float)(a + v);
+    if constexpr (ADV) adv[i * E + e] = (float)a;
+    vn = v;
+  }
+}
+
+static int head_bwd_gae_launch(int width, const NetLayout& L, const float* z, const int32_t* actions,
+                               const float* target, const float* h, const float* Wp, const float* Wv, float beta,
+                               int literal, int64_t B, float* dz, float* dh, float* terms, const ReturnsArgs& ra,
+                               int relu, hipStream_t s) {
+  const dim3 grid((unsigned)((B + 3) / 4));
+  const float invB = 1.0f / (float)B;
+  if (width == FC)
+    hipLaunchKernelGGL((k_head_bwd<FC, true>), grid, dim3(256), 0, s, z, L.zs, L.A, L.algo, actions, target, h, Wp,
+                       Wv, beta, literal, invB, B, dz, dh, terms, ra, relu);
+  else
+    hipLaunchKernelGGL((k_head_bwd<512, true>), grid, dim3(256), 0, s, z, L.zs, L.A, L.algo, actions, target, h, Wp,
+                       Wv, beta, literal, invB, B, dz, dh, terms, ra, relu);
+  A3C_CHECK(hipGetLastError());
+  return 0;
+}
+
+int a3c_gae_launch(const float* rewards, const uint8_t* terms, const float* values, int64_t vstride,
+                   const float* boot, int64_t boot_stride, int n, int64_t E, double gamma, double lambda, float* R,
+                   float* adv, hipStream_t s) {
+  if (E <= 0) return 0;
+  const dim3 grid((unsigned)((E + 255) / 256));
+  if (adv)
+    hipLaunchKernelGGL(k_gae<true>, grid, dim3(256), 0, s, rewards, terms, values, vstride, boot, boot_stride, n, E,
+                       gamma, lambda, R, adv);
+  else
+    hipLaunchKernelGGL(k_gae<false>, grid, dim3(256), 0, s, rewards, terms, values, vstride, boot, boot_stride, n, E,
+                       gamma, lambda, R, adv);
+  A3C_CHECK(hipGetLastError());
+  return 0;
 }
 
 #ifdef A3C_WGLOG

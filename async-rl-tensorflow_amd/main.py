@@ -56,6 +56,8 @@ def parse_flags(argv=None):
   p.add_argument('--mode', choices=['agent', 'engine'], default='engine')
   p.add_argument('--algo', choices=['a3c', 'q'], default='a3c')
   p.add_argument('--n_step', type=int, default=5)
+  p.add_argument('--gae_lambda', type=float, default=1.0,
+                 help='engine mode, a3c: GAE(lambda) advantages and lambda-returns; 1 = the n-step return (DESIGN §4f)')
   p.add_argument('--num_envs', type=int, default=256)
   p.add_argument('--num_frames', type=int, default=16384)
   p.add_argument('--iterations', type=int, default=1000)
@@ -107,7 +109,13 @@ def engine_options(flags):
     raise ValueError('--double_q is a Q-learning option (agent.py:176-184): use it with --algo q')
   if flags.lstm and flags.algo != 'a3c':
     raise ValueError('--lstm is an A3C policy head: use it with --algo a3c')
+  if not 0.0 <= flags.gae_lambda <= 1.0:
+    raise ValueError('--gae_lambda must be in [0, 1] (got %r)' % flags.gae_lambda)
+  if flags.gae_lambda != 1.0 and flags.algo != 'a3c':
+    raise ValueError('--gae_lambda is an A3C option (algo q has one-step TD targets): use it with --algo a3c')
   kw = dict(lstm=bool(flags.lstm))
+  if flags.gae_lambda != 1.0:
+    kw['gae_lambda'] = float(flags.gae_lambda)
   if flags.double_q:
     kw['double_q'] = True
   if flags.dqn_type == 'nature':
@@ -370,6 +378,8 @@ def run_agent(config, flags):
 
 def main(argv=None):
   flags = parse_flags(argv)
+  if flags.mode == 'agent' and flags.gae_lambda != 1.0:
+    raise ValueError('--gae_lambda is an engine option: --mode agent is the per-step Q-learning loop')
   random.seed(flags.random_seed)
   np.random.seed(flags.random_seed)
   from config import get_config

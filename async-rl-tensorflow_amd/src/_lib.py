@@ -42,7 +42,7 @@ class EngineConfig(ctypes.Structure):
                 ('ep_end', c_float), ('ep_end_t', c_i64), ('learn_start', c_i64),
                 ('target_q_update_step', c_i64), ('discount', c_double), ('overlap', c_int),
                 ('external_env', c_int), ('frame84', c_int), ('split_exchange', c_int),
-                ('double_q', c_int)]
+                ('double_q', c_int), ('gae_lambda', c_float)]
 
 
 class EngineBuffers(ctypes.Structure):
@@ -91,6 +91,8 @@ SIGNATURES = {
     'a3c_select_action': (c_int, [c_int, c_void_p, c_i64, c_int, c_int, c_void_p, c_u64, c_i64, c_void_p,
                                   c_void_p, c_void_p]),
     'a3c_returns': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_i64, c_double, c_void_p, c_void_p]),
+    'a3c_gae_returns': (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_int, c_i64, c_double, c_double,
+                                c_void_p, c_void_p, c_void_p]),
     'a3c_td_target': (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int, c_double, c_void_p,
                               c_void_p]),
     'a3c_loss_backward': (c_int, [ctypes.POINTER(NetDesc), c_void_p, c_void_p, c_i64, c_void_p, c_void_p,
@@ -181,7 +183,7 @@ OPTIONAL_IN_OLD_BUILDS = MEASUREMENT_ONLY + ('a3c_engine_exchange_split', 'a3c_e
                                              'a3c_engine_stats_accumulate', 'a3c_engine_stats_read',
                                              'a3c_engine_state_bytes', 'a3c_engine_state_save',
                                              'a3c_engine_state_load', 'a3c_play_config_default', 'a3c_engine_play',
-                                             'a3c_engine_play_buffers')
+                                             'a3c_engine_play_buffers', 'a3c_gae_returns')
 
 KER_CONV12_FWD, KER_FC_FWD, KER_ENV_STEP, KER_CONV_BWD, KER_HEAD_SCREEN, KER_HEAD_SCREEN_CONV12, KER_FC_PART = 0, 1, 2, 3, 4, 5, 6
 # nature trunk passes (include/a3c_hip.h A3C_KER_NAT_*)

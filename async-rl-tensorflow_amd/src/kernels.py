@@ -323,6 +323,28 @@ def returns(rewards, terminals, bootstrap, gamma=0.99):
     return R
 
 
+def gae_returns(rewards, terminals, values, bootstrap, gamma=0.99, lam=0.95, with_adv=True):
+    """GAE(lambda) over [n,E] in float64 -> float32 (a3c_gae_returns): the lambda-returns G = A + V and, with
+    ``with_adv``, the advantages A.  ``values`` is V(s_i) as an [n,E] tensor or a column view of a row-major
+    [n,E,stride] buffer (``z[..., A]``); ``bootstrap`` [E] is V(s_n).  lam = 1 gives the n-step returns."""
+    _dev(rewards, torch.float32, 'rewards')
+    _dev(terminals, torch.uint8, 'terminals')
+    _dev(bootstrap, torch.float32, 'bootstrap')
+    if values.dtype != torch.float32 or not values.is_cuda:
+        raise TypeError('values: expected a float32 device tensor')
+    n, E = int(rewards.shape[0]), int(rewards.shape[1])
+    if tuple(values.shape) != (n, E):
+        raise ValueError('values: expected shape [n, E]')
+    vs = int(values.stride(1)) if E > 1 else (int(values.stride(0)) if n > 1 else 1)
+    if vs < 1 or (E > 1 and n > 1 and int(values.stride(0)) != E * vs):
+        raise ValueError('values: expected [n, E] or a column of a row-major [n, E, stride] buffer')
+    R = torch.empty((n, E), dtype=torch.float32, device=rewards.device)
+    adv = torch.empty((n, E), dtype=torch.float32, device=rewards.device) if with_adv else None
+    check(lib().a3c_gae_returns(ptr(rewards), ptr(terminals), ptr(values), vs, ptr(bootstrap), n, E, float(gamma),
+                                float(lam), ptr(R), ptr(adv), stream_handle()), 'a3c_gae_returns')
+    return (R, adv) if with_adv else R
+
+
 def td_target(rewards, terminals, q_next, A, discount=0.99):
     """agent.py:186-190."""
     B = int(rewards.shape[0])

@@ -155,6 +155,21 @@ int a3c_td_target(const float* rewards, const uint8_t* terminals, const float* q
                   int A, int zs, double discount, float* target, void* stream);
 
 /* ----------------------------------------------------------------------------
+ * K7b  GAE(lambda) advantages and lambda-returns (Schulman et al.) over [n][E] in float64, with
+ *     V_i = values[(i*E + e) * value_stride] and V_n = bootstrap[e], for i = n-1 .. 0:
+ *       nt    = terminals[i][e] ? 0 : 1
+ *       delta = r_i + gamma*nt*V_{i+1} - V_i
+ *       A_i   = delta + gamma*lambda*nt*A_{i+1}                 (A_n = 0)
+ *       R[i][e] = (float)(A_i + V_i)      adv[i][e] = (float)A_i      (adv nullable)
+ *     lambda = 1: R is the n-step return of a3c_returns (to 1 ulp of float: V_i is added and
+ *     subtracted in float64); lambda = 0: R = r_i + gamma*nt*V_{i+1}.
+ *     A3C_ERR_INVALID: lambda outside [0, 1], n < 1, value_stride < 1, a null pointer (but adv).
+ * -------------------------------------------------------------------------- */
+int a3c_gae_returns(const float* rewards, const uint8_t* terminals, const float* values,
+                    int64_t value_stride, const float* bootstrap, int n, int64_t E, double gamma,
+                    double lambda, float* R, float* adv, void* stream);
+
+/* ----------------------------------------------------------------------------
  * K8+K9  loss + backward (network.py:81-94 with the SURVEY §8 A11 fixes / agent.py:306-317).
  *  target: a3c -> R (n-step return); q -> TD target.
  *  a3c loss per sample  -log pi(a)*stopgrad(R-V) - beta*H + (R-V)^2/2, summed over B
@@ -325,6 +340,11 @@ typedef struct a3c_engine_config {
                         t takes the target net's q of s_{t+1} at the online net's argmax action
                         (the rollout's own q rows, plus one online forward of the bootstrap state
                         s_n) instead of the target net's max.  Default 0.                     */
+  float gae_lambda;   /* a3c only: GAE(lambda) (a3c_gae_returns).  The target of the head backward --
+                        the policy advantage's minuend and the value target -- is the lambda-return
+                        A_t + V(s_t), with the rollout's own V rows.  1 (default): the n-step return
+                        of Algorithm S3, the kernels without GAE.  In [0, 1]; != 1 is rejected with
+                        algo q and with literal_adv.                                          */
 } a3c_engine_config;
 
 void a3c_engine_config_default(a3c_engine_config* cfg);
