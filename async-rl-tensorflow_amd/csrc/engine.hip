@@ -10,6 +10,7 @@
 // All per-iteration varying quantities (tau = frame counter, global env-step count, epsilon)
 // live in device memory, so the whole rollout+backward sequence is captured once into a hipGraph
 // and replayed (no host work per kernel).
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <new>
@@ -75,6 +76,12 @@ struct PlayCtx {
   float* nat_fws;          // nature trunk: the fc's split-K slabs
   float *lh, *lc;          // LSTM head: h, c [2][E][U], step t reads copy t & 1 and writes the other
   float* lwt;
+  PlayRefill rf;           // refill runs: ep_idx [E], tstart [2][E], sched (the per-episode arrays: ep_blk, per call)
+  uint8_t* ep_blk;         // refill runs: the per-episode arrays' block, ep_cap bytes
+  size_t ep_cap;
+  std::vector<int32_t> sched_env;    // the last call's schedule: the env that played episode idx ...
+  std::vector<int64_t> sched_tau0;   // ... and the tau of its first step
+  int64_t last_steps;                // the last call's run steps in which any env was live
   std::vector<std::pair<void*, size_t>> state;   // what "zeroed" covers
 };
 
@@ -1766,6 +1773,9 @@ static int play_alloc(a3c_engine* e, hipStream_t s) {
   PALLOC(c.z, E * L.zs * 4, false);
   PALLOC(c.eps, E * 4, false);
   PALLOC(c.active, 64, false);
+  PALLOC(c.rf.ep_idx, E * 4, true);
+  PALLOC(c.rf.tstart, 2 * E * 4, true);
+  PALLOC(c.rf.sched, 64, true);
   if (e->nat) {
     PALLOC(c.a1, E * NT_A1 * 4, false);
     PALLOC(c.a2, E * NT_A2 * 4, false);
@@ -1790,8 +1800,10 @@ static int play_alloc(a3c_engine* e, hipStream_t s) {
 }
 
 // play step t of a wave (agent.py:371-377): forward of s_tau on the play ring, action draw, act
-// with is_training = false, screen -- the play form of the step's tail -- then k_play_observe
-static int enqueue_play_step(a3c_engine* e, int mode, int t, int32_t* actions, float* z, hipStream_t s) {
+// with is_training = false, screen -- the play form of the step's tail -- then k_play_observe, or
+// with rf (a refill run, t: the run step) k_play_observe_refill and the refilled envs' screens
+static int enqueue_play_step(a3c_engine* e, int mode, int t, int32_t* actions, float* z, hipStream_t s,
+                             const PlayRefill* rf = nullptr) {
   const PlayCtx& c = e->play;
   const NetLayout& L = e->L;
   const int E = e->E, par = t & 1;
@@ -1834,6 +1846,10 @@ static int enqueue_play_step(a3c_engine* e, int mode, int t, int32_t* actions, f
                             false, nullptr, nullptr, nullptr, frozen);
   }
   if (rc) return rc;
+  if (rf)
+    return a3c_play_refill_launch(e->envp, c.env, c.bk, *rf, E, t, (HIST - 1) + (int64_t)t, c.rraw, c.terms, c.counters, e->pool, c.ring, c.R,
+                                  e->frame84, L.lstm ? c.lh + par * hc : nullptr, L.lstm ? c.lc + par * hc : nullptr,
+                                  L.lstm ? c.lh + (par ^ 1) * hc : nullptr, L.lstm ? c.lc + (par ^ 1) * hc : nullptr, s);
   hipLaunchKernelGGL(k_play_observe, dim3(L.lstm ? 1 + E : 1), dim3(256), 0, s, c.bk, E, par, c.rraw, c.terms,
                      c.active, c.counters, L.lstm ? c.lh + par * hc : nullptr, L.lstm ? c.lc + par * hc : nullptr,
                      L.lstm ? c.lh + (par ^ 1) * hc : nullptr, L.lstm ? c.lc + (par ^ 1) * hc : nullptr);
@@ -1841,7 +1857,80 @@ static int enqueue_play_step(a3c_engine* e, int mode, int t, int32_t* actions, f
   return 0;
 }
 
-static int play_impl(a3c_engine* e, const a3c_play_config& pc, float* returns, int32_t* lengths,
+// A refill run (a3c_engine_play_ex, refill = 1): one run, no waves.  Episodes 0 .. min(E, n_episode)-1
+// start as a wave does; from then on k_play_observe_refill hands an env whose episode ended the
+// next unassigned episode in the same step.  The host stops once the device count of unfinished
+// episodes, read every poll_every steps, is 0 -- and at waves * n_step steps at the latest: under
+// in-order list scheduling episode k has started by floor(k / E) * n_step, because every episode
+// j <= k - E has finished by then (induction over k: j started by floor(j / E) * n_step <=
+// (floor(k / E) - 1) * n_step and lasts at most n_step), so at most E - 1 of the episodes before k
+// still run and an env is free; the last episode therefore ends by
+// (floor((n_episode - 1) / E) + 1) * n_step = ceil(n_episode / E) * n_step.
+static int play_refill_impl(a3c_engine* e, const a3c_play_config& pc, int mode, float* returns, int32_t* lengths,
+                            uint8_t* terminated, int32_t* trace_actions, float* trace_z, hipStream_t s) {
+  PlayCtx& c = e->play;
+  const NetLayout& L = e->L;
+  const int E = e->E, N = pc.n_episode;
+  const int n_act = N < E ? N : E;
+  const int64_t bound = (int64_t)((N + E - 1) / E) * pc.n_step;
+  const int64_t tau0 = HIST - 1;
+  if (bound > 0x7fffffff)
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_play", "ceil(n_episode / E) * n_step exceeds 2^31 - 1");
+  // the per-episode arrays: ret | len | env (4 N each), tau0 (8 N), term (N)
+  const size_t o_len = (size_t)N * 4, o_env = (size_t)N * 8, o_tau = ((size_t)N * 12 + 7) & ~(size_t)7;
+  const size_t o_term = o_tau + (size_t)N * 8, bytes = o_term + (size_t)N;
+  if (bytes > c.ep_cap) {                    // kept across calls, grown when a call asks for more episodes
+    void* grown = nullptr;
+    A3C_CHECK(hipMalloc(&grown, bytes));
+    auto it = std::find(e->allocs.begin(), e->allocs.end(), (void*)c.ep_blk);
+    if (it != e->allocs.end()) {
+      (void)hipFree(c.ep_blk);
+      *it = grown;
+    } else {
+      e->allocs.push_back(grown);
+    }
+    c.ep_blk = (uint8_t*)grown;
+    c.ep_cap = bytes;
+  }
+  uint8_t* blk = c.ep_blk;
+  PlayRefill rf = c.rf;
+  rf.ep_ret = (float*)blk; rf.ep_len = (int32_t*)(blk + o_len); rf.ep_env = (int32_t*)(blk + o_env);
+  rf.ep_tau0 = (int64_t*)(blk + o_tau); rf.ep_term = blk + o_term;
+  rf.n_episode = N; rf.n_step = pc.n_step;
+  A3C_CHECK(hipMemsetAsync(blk, 0, bytes, s));
+  int rc = a3c_play_begin_launch(e->envp, c.env, E, n_act, tau0, c.bk, e->pool, c.ring, c.R, c.counters, e->frame84, s);
+  if (!rc) rc = a3c_play_refill_begin_launch(rf, E, n_act, tau0, s);
+  if (rc) return rc;
+  if (L.lstm) {
+    A3C_CHECK(hipMemsetAsync(c.lh, 0, (size_t)2 * E * LSTM_U * 4, s));
+    A3C_CHECK(hipMemsetAsync(c.lc, 0, (size_t)2 * E * LSTM_U * 4, s));
+  }
+  int32_t sched[4] = {0, 0, N, 0};     // next idx (two parities), episodes not finished, steps with a live env
+  for (int64_t t = 0; t < bound;) {
+    const int64_t stop = bound - t < pc.poll_every ? bound : t + pc.poll_every;
+    for (; t < stop && !rc; ++t) {
+      const int64_t o = t * E;
+      rc = enqueue_play_step(e, mode, (int)t, trace_actions ? trace_actions + o : c.actions,
+                             trace_z ? trace_z + o * L.zs : c.z, s, &rf);
+    }
+    if (rc) return rc;
+    A3C_CHECK(hipMemcpyAsync(sched, c.rf.sched, sizeof(sched), hipMemcpyDeviceToHost, s));
+    A3C_CHECK(hipStreamSynchronize(s));
+    if (sched[2] == 0) break;
+  }
+  A3C_CHECK(hipMemcpyAsync(sched, c.rf.sched, sizeof(sched), hipMemcpyDeviceToHost, s));
+  A3C_CHECK(hipMemcpyAsync(returns, rf.ep_ret, (size_t)N * 4, hipMemcpyDeviceToHost, s));
+  A3C_CHECK(hipMemcpyAsync(lengths, rf.ep_len, (size_t)N * 4, hipMemcpyDeviceToHost, s));
+  A3C_CHECK(hipMemcpyAsync(terminated, rf.ep_term, (size_t)N, hipMemcpyDeviceToHost, s));
+  A3C_CHECK(hipMemcpyAsync(c.sched_env.data(), rf.ep_env, (size_t)N * 4, hipMemcpyDeviceToHost, s));
+  A3C_CHECK(hipMemcpyAsync(c.sched_tau0.data(), rf.ep_tau0, (size_t)N * 8, hipMemcpyDeviceToHost, s));
+  A3C_CHECK(hipStreamSynchronize(s));
+  if (sched[2] != 0) return a3c_set_error(A3C_ERR_STATE, "a3c_engine_play", "episodes unfinished at the step bound");
+  c.last_steps = sched[3];
+  return 0;
+}
+
+static int play_impl(a3c_engine* e, const a3c_play_config& pc, int refill, float* returns, int32_t* lengths,
                      uint8_t* terminated, int32_t* trace_actions, float* trace_z, hipStream_t s) {
   PlayCtx& c = e->play;
   const NetLayout& L = e->L;
@@ -1859,6 +1948,10 @@ static int play_impl(a3c_engine* e, const a3c_play_config& pc, float* returns, i
                   : a3c_prep_fwd_launch(L, e->params, c.prep, s);
   if (!rc && L.lstm) rc = a3c_lstm_transpose_launch(e->params + L.off[T_LW], c.lwt, s);
   if (rc) return rc;
+  c.sched_env.assign(pc.n_episode, 0);
+  c.sched_tau0.assign(pc.n_episode, 0);
+  c.last_steps = 0;
+  if (refill) return play_refill_impl(e, pc, mode, returns, lengths, terminated, trace_actions, trace_z, s);
   const int waves = (pc.n_episode + E - 1) / E;
   std::vector<float> ret(E);
   std::vector<int32_t> len(E);
@@ -1893,28 +1986,52 @@ static int play_impl(a3c_engine* e, const a3c_play_config& pc, float* returns, i
       returns[(int64_t)w * E + i] = ret[i];
       lengths[(int64_t)w * E + i] = len[i];
       terminated[(int64_t)w * E + i] = term[i];
+      c.sched_env[(int64_t)w * E + i] = i;
+      c.sched_tau0[(int64_t)w * E + i] = tau;
     }
+    c.last_steps += *std::max_element(len.begin(), len.begin() + n_act);   // the wave's steps with a live env
   }
   return 0;
 }
 
-extern "C" int a3c_engine_play(a3c_engine* e, const a3c_play_config* cfg, float* returns, int32_t* lengths,
-                               uint8_t* terminated, int32_t* trace_actions, float* trace_z, void* stream) {
+extern "C" int a3c_engine_play_ex(a3c_engine* e, const a3c_play_config* cfg, int refill, float* returns,
+                                  int32_t* lengths, uint8_t* terminated, int32_t* trace_actions, float* trace_z,
+                                  void* stream) {
   if (!e || !cfg || !returns || !lengths || !terminated)
     return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_play", "null");
   if (e->ext)
     return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_play", "host-stepped envs are played by the host (no device env)");
   if (cfg->n_episode < 1 || cfg->n_step < 1 || cfg->poll_every < 1)
     return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_play", "n_episode, n_step and poll_every must be >= 1");
+  if (refill != 0 && refill != 1) return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_play", "refill must be 0 or 1");
   if (!e->reset_done) return a3c_set_error(A3C_ERR_STATE, "a3c_engine_play", "call a3c_engine_reset first");
   hipStream_t s = (hipStream_t)stream;
   if (int rc = play_alloc(e, s)) return rc;
   // overlap: a training rollout may be in flight on the rollout stream -> the small-footprint forms
   a3c_set_shared_gpu(e->overlap != 0);
-  int rc = play_impl(e, *cfg, returns, lengths, terminated, trace_actions, trace_z, s);
+  int rc = play_impl(e, *cfg, refill, returns, lengths, terminated, trace_actions, trace_z, s);
   a3c_set_shared_gpu(false);
   if (rc) return rc;
   A3C_CHECK(hipStreamSynchronize(s));
+  return 0;
+}
+
+extern "C" int a3c_engine_play(a3c_engine* e, const a3c_play_config* cfg, float* returns, int32_t* lengths,
+                               uint8_t* terminated, int32_t* trace_actions, float* trace_z, void* stream) {
+  return a3c_engine_play_ex(e, cfg, 0, returns, lengths, terminated, trace_actions, trace_z, stream);
+}
+
+extern "C" int a3c_engine_play_schedule(a3c_engine* e, int32_t* episode_env, int64_t* episode_tau0, int n,
+                                        int64_t* steps) {
+  if (!e || n < 0) return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_play_schedule", "bad argument");
+  const PlayCtx& c = e->play;
+  if ((size_t)n > c.sched_env.size())
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_play_schedule", "n exceeds the last call's n_episode");
+  for (int i = 0; i < n; ++i) {
+    if (episode_env) episode_env[i] = c.sched_env[i];
+    if (episode_tau0) episode_tau0[i] = c.sched_tau0[i];
+  }
+  if (steps) *steps = c.last_steps;
   return 0;
 }
 
@@ -1929,6 +2046,7 @@ extern "C" int a3c_engine_play_buffers(a3c_engine* e, a3c_play_buffers* b) {
   b->env_step = c.env.ep_step; b->env_len = c.env.ep_len;
   b->returns = c.bk.ret; b->lengths = c.bk.len; b->terminated = c.bk.term; b->frozen = c.bk.frozen;
   b->lstm_h = c.lh; b->lstm_c = c.lc;
+  b->episode_idx = c.rf.ep_idx; b->sched = c.rf.sched;
   return 0;
 }
 

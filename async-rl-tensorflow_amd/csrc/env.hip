@@ -179,6 +179,161 @@ int a3c_play_begin_launch(const EnvParams& p, const EnvBufs& b, int E, int n_act
   return 0;
 }
 
+// ---- play with refill: an env whose episode ends takes the next unassigned episode at once ------
+// start of the run, behind k_play_begin: episode e on env e < n_active, starting at tau
+__global__ void k_play_refill_begin(PlayRefill rf, int E, int n_active, int64_t tau) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e == 0) { rf.sched[0] = rf.sched[1] = n_active; rf.sched[2] = rf.n_episode; rf.sched[3] = 0; }
+  if (e >= E) return;
+  rf.ep_idx[e] = e < n_active ? e : -1;
+  rf.tstart[e] = rf.tstart[E + e] = 0;
+  if (e < n_active) { rf.ep_env[e] = e; rf.ep_tau0[e] = tau; }
+}
+
+// One launch per step t of a refill run, behind the step's head kernel, in the place of
+// k_play_observe: workgroup e is env e's observe, refill and first screens.  The play step is
+// launch-bound (~9 us per launch at 256 envs), so the refill adds no launch: instead
+// of one workgroup scanning the envs and a second kernel drawing the screens, every workgroup
+// counts for itself, in chunks of RF_THREADS envs, the envs that end in this step -- those before
+// it in env-id order (its rank) and all of them -- from words no workgroup writes in this launch:
+//   frozen[par], tstart[par] (the run step the env's episode started at; its length after this step
+//   is t + 1 - tstart), sched[par] (the next unassigned index) -- all double-buffered by the step
+//   parity, this launch writes copy par ^ 1 -- and terms (the head kernel's).
+// Counting is exact whatever the order: no atomics, the same indices on every run.  Then, for a
+// live env:
+//  * bookkeeping as k_play_observe (return += raw reward, length += 1, agent.py:377-379); the
+//    episode ends at a terminal or when its own length reaches n_step (terminated = 0 then), and
+//    its words go to the per-episode arrays;
+//  * an env that ended takes index next + rank; if that is < n_episode it is refilled:
+//    new_random_game (agent.py:363; both parity copies of the state), return / length /
+//    terminated zeroed, the schedule record, the frozen flag of the next parity clear, LSTM h, c
+//    zeroed in the copy the next step reads, and the new game's first screen into the HIST newest
+//    ring slots of the next step, (tau+1-3 .. tau+1) mod R, over the post-terminal screen the step
+//    wrote (agent.py:366-367) -- the whole-frame screen of the head kernels (atari::screen_frame,
+//    bit-exact Environment.screen: the band kernel of k_play_begin_screens takes 130 us a frame,
+//    too long for one workgroup inside a 37 us step) into the newest slot, then copied to the
+//    other three; otherwise the env is frozen for good.
+// A frozen env's LSTM h, c are carried into the copy the next step reads.  Workgroup 0 advances
+// sched (next index, episodes not finished, steps with a live env) and tau.  tau is an argument
+// (HIST-1 + t: a refill run's tau has no gaps), since workgroup 0 writes the counter.
+#define RF_THREADS 512
+__global__ void __launch_bounds__(RF_THREADS) k_play_observe_refill(EnvParams p, EnvBufs b, PlayBook bk, PlayRefill rf,
+                                                             int E, int t, int64_t tau,
+                                                             const float* __restrict__ rraw,
+                                                             const uint8_t* __restrict__ terms,
+                                                             int64_t* __restrict__ counters,
+                                                             const uint8_t* __restrict__ pool,
+                                                             uint8_t* __restrict__ ring, int R, int frame84,
+                                                             const float* __restrict__ h_src,
+                                                             const float* __restrict__ c_src, float* __restrict__ h_dst,
+                                                             float* __restrict__ c_dst) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  __shared__ int32_t s_frame;
+  const int e = blockIdx.x, tid = threadIdx.x, par = t & 1;
+  const uint8_t* fz_in = bk.frozen + (int64_t)par * E;
+  const int32_t* ts_in = rf.tstart + (int64_t)par * E;
+  int rank = 0, total = 0, live_any = 0;
+  for (int base = 0; base < E; base += RF_THREADS) {
+    const int j = base + tid;
+    const bool live = j < E && !fz_in[j];
+    const bool ended = live && (terms[j] || t + 1 - ts_in[j] >= rf.n_step);
+    rank += __syncthreads_count(ended && j < e);
+    total += __syncthreads_count(ended);
+    live_any |= __syncthreads_or(live);
+  }
+  const int next = rf.sched[par];
+  if (e == 0 && tid == 0) {
+    rf.sched[par ^ 1] = next + total < rf.n_episode ? next + total : rf.n_episode;
+    rf.sched[2] -= total;
+    rf.sched[3] += live_any ? 1 : 0;
+    counters[0] = tau + 1;
+  }
+  const uint8_t fz = fz_in[e];
+  const int32_t ts = ts_in[e];
+  if (fz) {
+    if (tid == 0) {
+      bk.frozen[(int64_t)(par ^ 1) * E + e] = 1;
+      rf.tstart[(int64_t)(par ^ 1) * E + e] = ts;
+    }
+    if (h_dst)
+      for (int i = tid; i < LSTM_U; i += RF_THREADS) {
+        h_dst[(int64_t)e * LSTM_U + i] = h_src[(int64_t)e * LSTM_U + i];
+        c_dst[(int64_t)e * LSTM_U + i] = c_src[(int64_t)e * LSTM_U + i];
+      }
+    return;
+  }
+  const bool term = terms[e] != 0;
+  const int32_t len = t + 1 - ts;
+  const bool ended = term || len >= rf.n_step;
+  const int idx = next + rank;
+  const bool refill = ended && idx < rf.n_episode;      // (uniform over the workgroup)
+  if (tid == 0) {
+    const float ret = bk.ret[e] + rraw[e];
+    bk.ret[e] = ret;
+    bk.len[e] = len;
+    if (term) bk.term[e] = 1;
+    if (ended) {
+      const int32_t old = rf.ep_idx[e];
+      rf.ep_ret[old] = ret;
+      rf.ep_len[old] = len;
+      rf.ep_term[old] = term ? 1 : 0;
+    }
+    if (refill) {
+      EnvState s = env_load(b, e);
+      env_new_random_game(s, p, (uint32_t)(p.env_id_base + e));
+      env_store(b, e, s);
+      env_store(b, (int64_t)E + e, s);
+      s_frame = s.frame;
+      bk.ret[e] = 0.f;
+      bk.len[e] = 0;
+      bk.term[e] = 0;
+      rf.ep_idx[e] = idx;
+      rf.ep_env[idx] = e;
+      rf.ep_tau0[idx] = tau + 1;
+    }
+    bk.frozen[(int64_t)(par ^ 1) * E + e] = ended && !refill ? 1 : 0;
+    rf.tstart[(int64_t)(par ^ 1) * E + e] = refill ? t + 1 : ts;
+  }
+  if (!refill) return;
+  __syncthreads();
+  if (h_dst)
+    for (int i = tid; i < LSTM_U; i += RF_THREADS) h_dst[(int64_t)e * LSTM_U + i] = c_dst[(int64_t)e * LSTM_U + i] = 0.f;
+  const int32_t f = s_frame;
+  uint8_t* base = ring + (int64_t)e * R * PLANE;
+  uint8_t* newest = base + ((tau + 1) % R) * PLANE;
+  if (frame84)
+    atari::copy_frame84<RF_THREADS>(pool + (int64_t)f * PLANE, newest);
+  else
+    atari::screen_frame<RF_THREADS>(pool + (int64_t)f * (atari::IH * atari::IW * 3), newest, smem, nullptr);
+  __syncthreads();                           // the newest slot is written: copy it to the three before it
+  for (int i = tid; i < PLANE / 16; i += RF_THREADS) {
+    const uint4 v = ((const uint4*)newest)[i];
+    for (int c = 0; c < HIST - 1; ++c) ((uint4*)(base + ((tau + 1 - (HIST - 1) + c) % R) * PLANE))[i] = v;
+  }
+}
+
+int a3c_play_refill_begin_launch(const PlayRefill& rf, int E, int n_active, int64_t tau, hipStream_t s) {
+  if (E < 1 || n_active < 1 || n_active > E || n_active > rf.n_episode || rf.n_step < 1)
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_play_refill_begin", "bad argument");
+  A3C_CHECK(hipFuncSetAttribute((const void*)k_play_observe_refill, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                SCREEN_FRAME_SMEM));
+  hipLaunchKernelGGL(k_play_refill_begin, dim3((E + 63) / 64), dim3(64), 0, s, rf, E, n_active, tau);
+  A3C_CHECK(hipGetLastError());
+  return 0;
+}
+
+int a3c_play_refill_launch(const EnvParams& p, const EnvBufs& b, const PlayBook& bk, const PlayRefill& rf, int E, int t,
+                           int64_t tau, const float* rraw, const uint8_t* terms, int64_t* counters, const uint8_t* pool,
+                           uint8_t* ring, int R, int frame84, const float* h_src, const float* c_src, float* h_dst,
+                           float* c_dst, hipStream_t s) {
+  if (E < 1 || R < HIST + 1 || t < 0 || tau < HIST - 1)
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_play_refill", "bad argument");
+  hipLaunchKernelGGL(k_play_observe_refill, dim3(E), dim3(RF_THREADS), frame84 ? 0 : SCREEN_FRAME_SMEM, s, p, b, bk, rf, E,
+                     t, tau, rraw, terms, counters, pool, ring, R, frame84, h_src, c_src, h_dst, c_dst);
+  A3C_CHECK(hipGetLastError());
+  return 0;
+}
+
 int a3c_screen_rows();
 
 template <int ROWS>

@@ -10,6 +10,7 @@ accepted but the TF ps/worker cluster is replaced by one process per GPU under t
   python main.py --mode engine --env_name Pong-v0 --iterations 1000
   python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 main.py --mode engine
   python main.py --mode engine --is_train false --n_episode 100     evaluate the newest checkpoint
+  python main.py --mode engine --is_train false --play_refill true  ... refilling finished envs (no waves)
 """
 import argparse
 import json
@@ -92,6 +93,8 @@ def parse_flags(argv=None):
                  help='play: the fixed epsilon (agent.py:351); default: q -- each env\'s final epsilon (main.py:68), '
                       'a3c -- the categorical draw, or greedy with --greedy')
   p.add_argument('--greedy', action='store_true', help='play, a3c: argmax (epsilon-greedy with --test_ep) on the logits')
+  p.add_argument('--play_refill', type=str2bool, default=False,
+                 help='play: an env whose episode ends takes the next episode at once (no waves; DESIGN §4e)')
   p.add_argument('--logdir', default='./logs')
   return p.parse_args(argv)
 
@@ -142,8 +145,11 @@ def play_options(flags, world=None):
     raise ValueError('--test_ep must be >= 0')
   if flags.greedy and flags.algo != 'a3c':
     raise ValueError('--greedy selects the a3c draw; q engines are epsilon-greedy (--test_ep 0 for greedy)')
-  return dict(n_episode=int(flags.n_episode), n_step=int(flags.play_steps), test_ep=flags.test_ep,
-              greedy=bool(flags.greedy))
+  kw = dict(n_episode=int(flags.n_episode), n_step=int(flags.play_steps), test_ep=flags.test_ep,
+            greedy=bool(flags.greedy))
+  if flags.play_refill:
+    kw['refill'] = True
+  return kw
 
 
 def run_play(config, flags, play_kw):
@@ -177,6 +183,8 @@ def run_play(config, flags, play_kw):
              best_idx=out['best_idx'], mean_reward=float(ret.mean()), min_reward=float(ret.min()),
              max_reward=float(ret.max()), mean_length=float(length.mean()), terminated=int(out['terminated'].sum()),
              env_steps=int(length.sum()), seconds=dt)
+  if play_kw.get('refill'):
+    rec.update(refill=True, steps=out['steps'])
   print(json.dumps(rec), flush=True)
   os.makedirs(flags.logdir, exist_ok=True)
   with open(os.path.join(flags.logdir, 'play.jsonl'), 'a') as f:

@@ -69,7 +69,7 @@ class PlayBuffers(ctypes.Structure):
     _fields_ = [('frame_ring', c_void_p), ('ring_slots', c_int), ('tau', c_void_p), ('env_frame', c_void_p),
                 ('env_lives', c_void_p), ('env_episode', c_void_p), ('env_step', c_void_p), ('env_len', c_void_p),
                 ('returns', c_void_p), ('lengths', c_void_p), ('terminated', c_void_p), ('frozen', c_void_p),
-                ('lstm_h', c_void_p), ('lstm_c', c_void_p)]
+                ('lstm_h', c_void_p), ('lstm_c', c_void_p), ('episode_idx', c_void_p), ('sched', c_void_p)]
 
 
 # name -> (restype, argtypes)
@@ -172,6 +172,9 @@ SIGNATURES = {
     'a3c_engine_play': (c_int, [c_void_p, ctypes.POINTER(PlayConfig), c_void_p, c_void_p, c_void_p, c_void_p,
                                 c_void_p, c_void_p]),
     'a3c_engine_play_buffers': (c_int, [c_void_p, ctypes.POINTER(PlayBuffers)]),
+    'a3c_engine_play_ex': (c_int, [c_void_p, ctypes.POINTER(PlayConfig), c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_void_p]),
+    'a3c_engine_play_schedule': (c_int, [c_void_p, c_void_p, c_void_p, c_int, ctypes.POINTER(c_i64)]),
 }
 
 # diagnostics an A/B build from an earlier commit may lack (every other symbol is required)
@@ -183,7 +186,8 @@ OPTIONAL_IN_OLD_BUILDS = MEASUREMENT_ONLY + ('a3c_engine_exchange_split', 'a3c_e
                                              'a3c_engine_stats_accumulate', 'a3c_engine_stats_read',
                                              'a3c_engine_state_bytes', 'a3c_engine_state_save',
                                              'a3c_engine_state_load', 'a3c_play_config_default', 'a3c_engine_play',
-                                             'a3c_engine_play_buffers', 'a3c_gae_returns')
+                                             'a3c_engine_play_buffers', 'a3c_gae_returns', 'a3c_engine_play_ex',
+                                             'a3c_engine_play_schedule')
 
 KER_CONV12_FWD, KER_FC_FWD, KER_ENV_STEP, KER_CONV_BWD, KER_HEAD_SCREEN, KER_HEAD_SCREEN_CONV12, KER_FC_PART = 0, 1, 2, 3, 4, 5, 6
 # nature trunk passes (include/a3c_hip.h A3C_KER_NAT_*)

@@ -234,7 +234,7 @@ class Engine:
         self.apply()
 
     # ---------------------------------------------------------------- evaluation (agent.py:351-391)
-    def play(self, n_episode=100, n_step=10000, test_ep=None, greedy=False, poll_every=64, trace=False):
+    def play(self, n_episode=100, n_step=10000, test_ep=None, greedy=False, poll_every=64, trace=False, refill=False):
         """Agent.play (agent.py:351-391) batched: n_episode evaluation episodes of at most n_step
         env steps each, E at a time (episode w*E + e: env e in wave w), with the live parameters and
         no learning -- the training state is untouched.  The env steps with is_training=False (a
@@ -244,7 +244,13 @@ class Engine:
         Returns {'returns' f32, 'lengths' i32, 'terminated' bool [n_episode], 'best_reward',
         'best_idx' (agent.py:381-383)}; trace=True adds the device tensors 'actions'
         [waves, n_step, E] i32 and 'z' [waves, n_step, E, zs] f32, written by the steps' own
-        kernels (entries of frozen envs and of steps not run stay as allocated: -1 / NaN)."""
+        kernels (entries of frozen envs and of steps not run stay as allocated: -1 / NaN).
+        refill=True: no waves -- an env whose episode ends (terminal, or its own n_step steps) takes
+        the next unassigned episode in the same step, in env-id order; the traces are then
+        [waves*n_step, E(, zs)] indexed by run step.  Either way the result carries the schedule,
+        'episode_env' i32 and 'episode_tau0' i64 [n_episode] (the env that played the episode and
+        the tau of its first step), and 'steps', the run steps in which any env was live."""
+        refill = int(refill)                     # (the library rejects anything but 0 / 1)
         cfg = _lib.PlayConfig()
         lib().a3c_play_config_default(ctypes.byref(cfg))
         cfg.n_episode, cfg.n_step, cfg.greedy = int(n_episode), int(n_step), 1 if greedy else 0
@@ -259,17 +265,27 @@ class Engine:
         acts = zt = None
         if trace and cfg.n_episode >= 1 and cfg.n_step >= 1:      # (else the call rejects the arguments)
             waves = -(-cfg.n_episode // self.E)
-            acts = torch.full((waves, cfg.n_step, self.E), -1, dtype=torch.int32, device='cuda')
-            zt = torch.full((waves, cfg.n_step, self.E, self.zs), float('nan'), dtype=torch.float32, device='cuda')
-        check(lib().a3c_engine_play(self._h, ctypes.byref(cfg), ret.ctypes.data_as(ctypes.c_void_p),
-                                    length.ctypes.data_as(ctypes.c_void_p), term.ctypes.data_as(ctypes.c_void_p),
-                                    _lib.ptr(acts), _lib.ptr(zt), _lib.stream_handle()), 'a3c_engine_play')
+            shape = (waves * cfg.n_step, self.E) if refill else (waves, cfg.n_step, self.E)
+            acts = torch.full(shape, -1, dtype=torch.int32, device='cuda')
+            zt = torch.full(shape + (self.zs,), float('nan'), dtype=torch.float32, device='cuda')
+        args = (ret.ctypes.data_as(ctypes.c_void_p), length.ctypes.data_as(ctypes.c_void_p),
+                term.ctypes.data_as(ctypes.c_void_p), _lib.ptr(acts), _lib.ptr(zt), _lib.stream_handle())
+        if refill:
+            check(lib().a3c_engine_play_ex(self._h, ctypes.byref(cfg), refill, *args), 'a3c_engine_play_ex')
+        else:
+            check(lib().a3c_engine_play(self._h, ctypes.byref(cfg), *args), 'a3c_engine_play')
+        ep_env = np.zeros(n_ep, np.int32)
+        ep_tau0 = np.zeros(n_ep, np.int64)
+        steps = _lib.c_i64(0)
+        check(lib().a3c_engine_play_schedule(self._h, ep_env.ctypes.data_as(ctypes.c_void_p),
+                                             ep_tau0.ctypes.data_as(ctypes.c_void_p), cfg.n_episode,
+                                             ctypes.byref(steps)), 'a3c_engine_play_schedule')
         best_reward, best_idx = 0.0, 0                                   # agent.py:361
         for idx in range(cfg.n_episode):
             if ret[idx] > best_reward:                                   # agent.py:381-383
                 best_reward, best_idx = float(ret[idx]), idx
         out = dict(returns=ret, lengths=length, terminated=term.astype(bool), best_reward=best_reward,
-                   best_idx=best_idx)
+                   best_idx=best_idx, episode_env=ep_env, episode_tau0=ep_tau0, steps=int(steps.value))
         if trace:
             out.update(actions=acts, z=zt)
         return out
@@ -277,7 +293,8 @@ class Engine:
     def play_buffers(self):
         """Views of the play context (tests): ring [E, R_play, 84, 84], tau [1], env fields [2, E]
         (both parity copies equal), the last wave's returns / lengths / terminated [E], frozen [2, E],
-        and lstm_h / lstm_c [2, E, U] with the LSTM head."""
+        and lstm_h / lstm_c [2, E, U] with the LSTM head; of refill runs episode_idx [E] and sched [4]
+        (the next unassigned index twice, episodes not finished, steps with a live env)."""
         b = _lib.PlayBuffers()
         check(lib().a3c_engine_play_buffers(self._h, ctypes.byref(b)), 'a3c_engine_play_buffers')
         E = self.E
@@ -286,7 +303,8 @@ class Engine:
                    lives=_view(b.env_lives, (2, E), torch.int32), episode=_view(b.env_episode, (2, E), torch.int32),
                    ep_step=_view(b.env_step, (2, E), torch.int32), ep_len=_view(b.env_len, (2, E), torch.int32),
                    returns=_view(b.returns, (E,), torch.float32), lengths=_view(b.lengths, (E,), torch.int32),
-                   terminated=_view(b.terminated, (E,), torch.uint8), frozen=_view(b.frozen, (2, E), torch.uint8))
+                   terminated=_view(b.terminated, (E,), torch.uint8), frozen=_view(b.frozen, (2, E), torch.uint8),
+                   episode_idx=_view(b.episode_idx, (E,), torch.int32), sched=_view(b.sched, (4,), torch.int32))
         if self.lstm:
             out.update(lstm_h=_view(b.lstm_h, (2, E, _lib.A3C_LSTM_UNITS), torch.float32),
                        lstm_c=_view(b.lstm_c, (2, E, _lib.A3C_LSTM_UNITS), torch.float32))

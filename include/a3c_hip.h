@@ -558,9 +558,47 @@ typedef struct a3c_play_config {
 void a3c_play_config_default(a3c_play_config* cfg);
 int a3c_engine_play(a3c_engine* eng, const a3c_play_config* cfg, float* returns, int32_t* lengths,
                     uint8_t* terminated, int32_t* trace_actions, float* trace_z, void* stream);
+/* Play with refill (continuous batched evaluation): a3c_engine_play_ex(.., refill = 1, ..).  refill
+ * = 0 is a3c_engine_play, bit for bit; other values give A3C_ERR_INVALID.  (The mode is an argument
+ * and not a field of a3c_play_config, so that callers built against the five-field struct stay
+ * valid.)  In a wave an env whose episode ended idles until the wave's slowest env is done; here
+ * it takes the next episode at once, as the reference's one emulator plays its episodes back to
+ * back.  Everything not stated below (parameters, step, draw rules, frozen envs, rejections) is as
+ * in waves mode.
+ *  start:   one run per call, no waves.  tau = HIST-1; episodes idx = 0 .. min(E, n_episode)-1 start
+ *           on envs e = idx exactly as a wave does; the other envs are idle (frozen).
+ *  end of an episode on env e: at a terminal, or when the episode's own length reaches n_step --
+ *           then terminated = 0 and lives > 0, so the emulator goes on, as after a capped wave
+ *           episode.  Its return, length and terminated flag go to per-episode device arrays.
+ *  refill:  in the same step, behind the bookkeeping.  The envs that ended in this step take the
+ *           next unassigned episode indices in env-id order (each env counts the envs in front of
+ *           it that ended: exact whatever the order, no atomics).  An
+ *           env that gets idx < n_episode: new_random_game (agent.py:363), the new game's first
+ *           screen into the HIST newest ring slots of the next step, (tau+1-3 .. tau+1) mod R, over
+ *           the post-terminal screen the step has just written (agent.py:366-367), return and length
+ *           zeroed, LSTM h / c zeroed in the copy the next step reads, frozen flag of the next step
+ *           cleared.  An env that gets none is frozen for good.  Both parity copies of the env state
+ *           stay equal.
+ *  draw:    the (tau, env id) Philox counter; tau advances by 1 per run step without gaps, so no two
+ *           (step, env) share a counter.
+ *  end:     once the host -- reading the device count of unfinished episodes every poll_every
+ *           steps -- sees 0, and after ceil(n_episode / E) * n_step steps at the latest (under
+ *           in-order list scheduling episode k has started by floor(k / E) * n_step).  Results do
+ *           not depend on poll_every.  A3C_ERR_INVALID if that bound exceeds 2^31 - 1.
+ *  traces:  the buffers keep the waves-mode size, read as [waves * n_step][E] (x zs) indexed by run
+ *           step; entries of idle envs and of steps not run are left untouched.
+ * a3c_engine_play_schedule: the last play call's schedule -- for episode idx < n (n <= its
+ * n_episode) the env that played it and the tau of its first step (lengths[idx] gives the rest);
+ * waves mode reports idx % E and the wave's start tau.  *steps: the run steps in which any env was
+ * live (waves mode: summed over the waves).  Any output pointer may be NULL. */
+int a3c_engine_play_ex(a3c_engine* eng, const a3c_play_config* cfg, int refill, float* returns, int32_t* lengths,
+                       uint8_t* terminated, int32_t* trace_actions, float* trace_z, void* stream);
+int a3c_engine_play_schedule(a3c_engine* eng, int32_t* episode_env, int64_t* episode_tau0, int n, int64_t* steps);
 /* device pointers of the play context (tests; allocates it like the first a3c_engine_play).  The
  * env fields are [2][E] with both parity copies equal; lstm_h / lstm_c [2][E][U], NULL without the
- * LSTM head: the current state is copy (steps the last wave ran) & 1. */
+ * LSTM head: the current state is copy (steps the last wave ran) & 1.  episode_idx [E] and sched
+ * (the next unassigned idx in two copies by step parity, episodes not finished, steps with a live
+ * env) belong to refill runs. */
 typedef struct a3c_play_buffers {
   uint8_t* frame_ring;     /* [E][ring_slots][84*84] u8                        */
   int ring_slots;
@@ -569,6 +607,8 @@ typedef struct a3c_play_buffers {
   float* returns; int32_t* lengths; uint8_t* terminated;   /* [E]: the last wave's bookkeeping */
   uint8_t* frozen;         /* [2][E]                                           */
   float* lstm_h; float* lstm_c;
+  int32_t* episode_idx;    /* [E] refill runs: the episode env e plays / played last */
+  int32_t* sched;          /* [4] refill runs: next idx x 2, unfinished, live steps  */
 } a3c_play_buffers;
 int a3c_engine_play_buffers(a3c_engine* eng, a3c_play_buffers* out);
 
