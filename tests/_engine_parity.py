@@ -59,8 +59,10 @@ def rel_l2(a, b):
     return np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-30)
 
 
+# engine options the oracle takes under the same name: a value given to the engine reaches EngineRef
 REF_KEYS = ('target_q_update_step', 'learning_rate', 'frame84', 'double_q', 'ep_start', 'ep_end_t', 'learn_start',
-            'dqn_type')
+            'dqn_type', 'gamma', 'discount', 'beta', 'max_step', 'decay', 'momentum', 'epsilon', 'clip_norm',
+            'literal_adv', 'random_start', 'action_repeat')
 
 
 def build(algo, A, E, n, lives, seed, frames=48, use_graph=False, scale=4.0, **kw):
@@ -85,7 +87,7 @@ def unflat(eng, ns, flat):
     return {name: f[off:off + sz].reshape(shp) for (name, shp), off, sz in zip(ns, eng.offsets, eng.sizes)}
 
 
-def same_act_grads(slot, planes, P, algo, A, n, E, tgt):
+def same_act_grads(slot, planes, P, algo, A, n, E, tgt, beta=0.01, literal_adv=False):
     """oracle loss + backward of one rollout on the engine's saved activations of that rollout
     (slot: Engine.slot(k), or the engine itself in sync mode)."""
     g = (lambda k: slot[k]) if isinstance(slot, dict) else (lambda k: getattr(slot, k))
@@ -107,7 +109,7 @@ def same_act_grads(slot, planes, P, algo, A, n, E, tgt):
                    acts=[x0, l1, l2.reshape(B, 9, 9, 32)])
     acts = g('actions').cpu().numpy().reshape(-1)
     if algo == 'a3c':
-        losses, dz = Rc.a3c_loss_and_dz(z, acts, tgt.reshape(-1).astype(np.float64), 0.01)
+        losses, dz = Rc.a3c_loss_and_dz(z, acts, tgt.reshape(-1).astype(np.float64), beta, bool(literal_adv))
     else:
         loss, dz = Rc.q_loss_and_dz(z, acts, tgt.reshape(-1).astype(np.float64))
         losses = dict(loss=loss)
@@ -255,8 +257,11 @@ def assert_env_state(eng, ref, tag):
 
 
 def check_sync_vs_oracle(algo, A, E, n, lives, iters=3, seed=None, frames=48, scale=4.0, independent=True,
-                         host_pool=None, **kw):
+                         host_pool=None, on_update=None, start=None, **kw):
     """Synchronous engine (rollout_grad + apply): every iteration against the oracle.
+    on_update(it, eng, ref, lr): called after every checked update with the oracle's learning rate
+    of that update (for checks of a case's own: the schedule word, the clip regimes).
+    start(eng, ref): called once before the first rollout (to resume both at a later step).
     host_pool(seed): a host env pool factory -- the engine then runs with external_env and its
     n env steps are driven by Engine.rollout_host."""
     seed = 123 + E if seed is None else seed
@@ -268,6 +273,8 @@ def check_sync_vs_oracle(algo, A, E, n, lives, iters=3, seed=None, frames=48, sc
     if host_pool is not None:
         pool = host_pool(seed)
         eng.begin_host(pool)
+    if start is not None:
+        start(eng, ref)
     torch.cuda.synchronize()
     if pool is None:
         assert np.array_equal(eng.env_frame.cpu().numpy(), ref.env.frame.astype(np.int32))
@@ -301,7 +308,7 @@ def check_sync_vs_oracle(algo, A, E, n, lives, iters=3, seed=None, frames=48, sc
         G = unflat(eng, ns, eng.grads)
         # single GPU: the per-tensor clip is fused into apply, so after rollout_grad the buffer
         # holds the raw gradient
-        _, g_same = same_act_grads(eng, planes, Pk, algo, A, n, E, tgt)
+        _, g_same = same_act_grads(eng, planes, Pk, algo, A, n, E, tgt, ref.h['beta'], ref.h['literal_adv'])
         for name, _ in ns:
             assert rel_l2(G[name], g_same[name]) < 1e-4, (it, name, rel_l2(G[name], g_same[name]))
         if independent:     # fully independent fp64 oracle: ReLU-mask flips allowed
@@ -313,8 +320,10 @@ def check_sync_vs_oracle(algo, A, E, n, lives, iters=3, seed=None, frames=48, sc
             assert np.isclose(ss[i], np.sum(G[name].astype(np.float64) ** 2), rtol=1e-5), (it, name)
         # the oracle optimizer consumes the same-mask gradients so the two parameter
         # trajectories stay comparable at 1e-5 over iterations
-        ref.apply({k: Rc.clip_by_norm(v, 40.0) for k, v in g_same.items()})
+        lr = ref.apply({k: Rc.clip_by_norm(v, ref.h['clip_norm']) for k, v in g_same.items()})
         assert_params(eng, ns, ref, it)
+        if on_update is not None:
+            on_update(it, eng, ref, lr)
         cnt = eng.counters.cpu().numpy()
         assert cnt[0] == ref.tau and cnt[1] == ref.global_step
         if pool is None:
@@ -330,7 +339,7 @@ def check_sync_vs_oracle(algo, A, E, n, lives, iters=3, seed=None, frames=48, sc
 
 
 def check_overlap_vs_oracle(A, E, n, lives, rollouts=5, seed=77, frames=48, scale=4.0, algo='a3c', hogwild=False,
-                            **kw):
+                            on_update=None, **kw):
     """Overlap (stale-1) pipeline: rollout k uses the parameters after update k-2.  The oracle is
     replayed in that order with the engine's own actions and activations.  algo='q': the TD targets
     of rollout k-1 are formed by its backward, after rollout k, with the target network as it
@@ -348,7 +357,7 @@ def check_overlap_vs_oracle(A, E, n, lives, rollouts=5, seed=77, frames=48, scal
     ps = None
     if hogwild:
         from src.hogwild import HogwildPS
-        ps = HogwildPS(eng.params)
+        ps = HogwildPS(eng.params, decay=ref.h['decay'], momentum=ref.h['momentum'], epsilon=ref.h['epsilon'])
     hist = []                  # per rollout: (oracle params used, planes, oracle out)
     worst = {}
     names = [name for name, _ in ns]
@@ -395,7 +404,7 @@ def check_overlap_vs_oracle(A, E, n, lives, rollouts=5, seed=77, frames=48, scal
                 want = Rc.td_target(out_p['rewards'].reshape(-1), out_p['terminals'].reshape(-1),
                                     qn.astype(np.float32), ref.h['discount']).astype(np.float32).reshape(n, E)
         np.testing.assert_allclose(tgt, want, rtol=1e-5, atol=1e-5)
-        losses, g_same = same_act_grads(slp, planes_p, Pp, algo, A, n, E, tgt)
+        losses, g_same = same_act_grads(slp, planes_p, Pp, algo, A, n, E, tgt, ref.h['beta'], ref.h['literal_adv'])
         assert_losses(eng.loss.cpu().numpy(), losses, algo, k)
         # independent: the oracle's own fp64 batch forward of rollout k-1 (its logits, values and
         # bootstrap targets / q rows), not the engine's saved activations.  q: formed here, with the
@@ -409,15 +418,18 @@ def check_overlap_vs_oracle(A, E, n, lives, rollouts=5, seed=77, frames=48, scal
         assert_z(slp['z'].cpu().numpy()[:n].reshape(n * E, -1), z_ind, zw, ('z_batch', k))
         G = unflat(eng, ns, eng.grads)
         if ps is not None:     # (hogwild clips the buffer in place before its push)
-            g_same_c = {kk: Rc.clip_by_norm(v, 40.0) for kk, v in g_same.items()}
-            g_ind = {kk: Rc.clip_by_norm(v, 40.0) for kk, v in g_ind.items()}
+            g_same_c = {kk: Rc.clip_by_norm(v, ref.h['clip_norm']) for kk, v in g_same.items()}
+            g_ind = {kk: Rc.clip_by_norm(v, ref.h['clip_norm']) for kk, v in g_ind.items()}
         for name in names:
             want_g = g_same_c[name] if ps is not None else g_same[name]
             assert rel_l2(G[name], want_g) < 1e-4, (k, name, rel_l2(G[name], want_g))
         assert_independent_grads(G, g_ind, names, k, worst)
         out_p.pop('acts_batch', None)       # (checked; the replay keeps every rollout's out alive)
-        ref.apply({kk: Rc.clip_by_norm(v, 40.0) for kk, v in g_same.items()}, advance_tau=False, tau=out_p['tau'])
+        lr = ref.apply({kk: Rc.clip_by_norm(v, ref.h['clip_norm']) for kk, v in g_same.items()}, advance_tau=False,
+                       tau=out_p['tau'])
         assert_params(eng, ns, ref, k)
+        if on_update is not None:
+            on_update(k, eng, ref, lr)
         if ps is not None:
             assert torch.equal(ps.gather(), eng.params)
         assert int(eng.counters[1].item()) == ref.global_step
@@ -431,14 +443,14 @@ def check_overlap_vs_oracle(A, E, n, lives, rollouts=5, seed=77, frames=48, scal
     return eng, ref
 
 
-def check_hogwild1_vs_oracle(A, E, n, lives, iters=3, seed=91, frames=48, scale=4.0, **kw):
+def check_hogwild1_vs_oracle(A, E, n, lives, iters=3, seed=91, frames=48, scale=4.0, on_update=None, **kw):
     """Hogwild with one worker (src/hogwild.py at world 1): rollout + gradient, per-worker clip,
     unlocked RMSProp push into the sharded PS, pull.  With one worker the push order is fixed, so
     it must equal the oracle's clip + RMSProp step for step."""
     from src.hogwild import HogwildPS
     algo = 'a3c'
     eng, ref, ns = build(algo, A, E, n, lives, seed=seed, frames=frames, scale=scale, **kw)
-    ps = HogwildPS(eng.params)
+    ps = HogwildPS(eng.params, decay=ref.h['decay'], momentum=ref.h['momentum'], epsilon=ref.h['epsilon'])
     worst = {}
     names = [name for name, _ in ns]
     try:
@@ -457,17 +469,19 @@ def check_hogwild1_vs_oracle(A, E, n, lives, iters=3, seed=91, frames=48, scale=
             assert np.array_equal(eng.terminals.cpu().numpy(), out['terminals']), it
             tgt = eng.returns.cpu().numpy()
             np.testing.assert_allclose(tgt, out['target'], rtol=1e-5, atol=1e-5)
-            losses, g_same = same_act_grads(eng, planes, Pk, algo, A, n, E, tgt)
+            losses, g_same = same_act_grads(eng, planes, Pk, algo, A, n, E, tgt, ref.h['beta'], ref.h['literal_adv'])
             assert_losses(eng.loss.cpu().numpy(), losses, algo, it)
             assert_losses(eng.loss.cpu().numpy(), out['losses'], algo, ('independent', it))
-            clipped = {k: Rc.clip_by_norm(v, 40.0) for k, v in g_same.items()}
+            clipped = {k: Rc.clip_by_norm(v, ref.h['clip_norm']) for k, v in g_same.items()}
             G = unflat(eng, ns, eng.grads)        # the engine's buffer holds the clipped gradient
             for name in names:
                 assert rel_l2(G[name], clipped[name]) < 1e-4, (it, name)
-            assert_independent_grads(G, {k: Rc.clip_by_norm(v, 40.0) for k, v in out['grads'].items()}, names, it,
-                                     worst)
-            ref.apply(clipped)
+            g_ind = {k: Rc.clip_by_norm(v, ref.h['clip_norm']) for k, v in out['grads'].items()}
+            assert_independent_grads(G, g_ind, names, it, worst)
+            lr = ref.apply(clipped)
             assert_params(eng, ns, ref, it)
+            if on_update is not None:
+                on_update(it, eng, ref, lr)
             assert torch.equal(ps.gather(), eng.params)
             cnt = eng.counters.cpu().numpy()
             assert cnt[0] == ref.tau and cnt[1] == ref.global_step

@@ -86,7 +86,7 @@ def gap_mask(net):
     return gap
 
 
-def check_loss_backward(K, algo, A, B, literal):
+def check_loss_backward(K, algo, A, B, literal, beta=0.01):
     net = K.Net(A, algo)
     p = make_params(net, seed=B + 11, scale=4.0)
     rng = np.random.default_rng(B + 7)
@@ -99,7 +99,7 @@ def check_loss_backward(K, algo, A, B, literal):
     gap = gap_mask(net)
     assert gap.any()
     grads0 = cu(np.where(gap, np.float32(GUARD), np.float32(0.0)))
-    grads, loss = net.loss_backward(flat, states, fwd, cu(actions), cu(target), beta=0.01, literal_adv=literal,
+    grads, loss = net.loss_backward(flat, states, fwd, cu(actions), cu(target), beta=beta, literal_adv=literal,
                                     grads=grads0)
     zw = A + 1 if algo == 'a3c' else A
     # the gradient buffer between the tensors is not the backward's to write
@@ -107,7 +107,7 @@ def check_loss_backward(K, algo, A, B, literal):
 
     def oracle(ref_f):
         if algo == 'a3c':
-            losses, dz = R.a3c_loss_and_dz(ref_f['z'], actions, target.astype(np.float64), 0.01, literal)
+            losses, dz = R.a3c_loss_and_dz(ref_f['z'], actions, target.astype(np.float64), beta, literal)
             ref_loss = [losses['policy'], losses['value'], losses['entropy'], losses['total']]
         else:
             l, dz = R.q_loss_and_dz(ref_f['z'], actions, target.astype(np.float64))

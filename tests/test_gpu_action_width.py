@@ -75,7 +75,7 @@ def test_loss_backward_matches_oracle_wide(K, algo, A, B, literal):
 
 
 # ------------------------------------------------------------------ 2. nature trunk, per-op
-def nature_case(K, A, B, literal):
+def nature_case(K, A, B, literal, beta=0.01):
     from src.initializers import flatten_host
     net = K.NatureNet(A)
     p = make_params(net, seed=A + B, scale=4.0)
@@ -87,7 +87,7 @@ def nature_case(K, A, B, literal):
     states = cu(planes)
     zbuf = guarded_z(B, net.zs)
     fwd = net.forward(flat, states, z=zbuf)
-    grads, loss = net.loss_backward(flat, states, fwd, cu(actions), cu(target), beta=0.01, literal_adv=literal)
+    grads, loss = net.loss_backward(flat, states, fwd, cu(actions), cu(target), beta=beta, literal_adv=literal)
     return net, p, planes, actions, target, zbuf, fwd, grads, loss
 
 
@@ -99,7 +99,11 @@ def test_nature_forward_loss_backward_match_oracle(K, A, B, literal):
     N = ldb = zs in {8, 12, 20, 32} and the finalize segments at column A (nature.hip).  B = 37
     gives the three dW passes a ragged last K chunk and the head GEMM more than one K tile (split);
     A = 8 at B = 1 is the mixed wide head_row / narrow select width with literal_adv."""
-    net, p, planes, actions, target, zbuf, fwd, grads, loss = nature_case(K, A, B, literal)
+    check_nature_forward_loss_backward(K, A, B, literal)
+
+
+def check_nature_forward_loss_backward(K, A, B, literal, beta=0.01):
+    net, p, planes, actions, target, zbuf, fwd, grads, loss = nature_case(K, A, B, literal, beta)
     zw = A + 1
     assert net.zs == a3c_zs('a3c', A)
     states = R.states_nhwc(planes)
@@ -116,7 +120,7 @@ def test_nature_forward_loss_backward_match_oracle(K, A, B, literal):
     lg = loss.cpu().numpy()
 
     def check(ref_f, gtol, ltol):
-        losses, dz = R.a3c_loss_and_dz(ref_f['z'], actions, target.astype(np.float64), 0.01, literal)
+        losses, dz = R.a3c_loss_and_dz(ref_f['z'], actions, target.astype(np.float64), beta, literal)
         g_ref = R.backward(p, ref_f, dz, 'a3c', 'nature')
         for (name, shp), o, n in zip(net.names_shapes, net.offsets, net.sizes):
             err = rel_l2(g[o:o + n].reshape(shp), g_ref[name].reshape(shp))

@@ -18,10 +18,11 @@ torch = pytest.importorskip('torch')
 W = 4
 
 
-def _engine(split, overlap, E=32, seed=31, **kw):
+def _engine(split, overlap, E=32, seed=31, world=W, frames=128, **kw):
     from _engine_parity import build
-    eng, ref, ns = build('a3c', 6, E, 5, 0, seed=seed, frames=128, scale=4.0, overlap=overlap,
-                         world_size=W, split_exchange=split, learning_rate=3e-3, **kw)
+    kw.setdefault('learning_rate', 3e-3)
+    eng, ref, ns = build('a3c', 6, E, 5, 0, seed=seed, frames=frames, scale=4.0, overlap=overlap,
+                         world_size=world, split_exchange=split, **kw)
     return eng, ref, ns
 
 
@@ -48,17 +49,24 @@ def test_loopback_split_exchange_matches_oracle():
     """Sync engine at world W with the two-phase loopback exchange: every iteration the oracle
     takes its clipped gradient (on the engine's own activations) as W rank-ordered RMSProp
     steps; parameters within 1e-5, the global step advanced by n E W."""
+    check_loopback_vs_oracle(W, 32)
+
+
+def check_loopback_vs_oracle(world, E, iters=3, seed=31, frames=128, on_update=None, **kw):
+    """kw: engine options, given to the oracle under the same names (_engine_parity.REF_KEYS).
+    on_update(it, eng, ref, lr): called after every checked update."""
     from src.distributed import LoopbackPS
     from oracle import ref_cpu as Rc
     from oracle.engine_ref import EngineRef
-    from _engine_parity import same_act_grads, rollout_planes, unflat, rel_l2, assert_params
+    from _engine_parity import REF_KEYS, same_act_grads, rollout_planes, unflat, rel_l2, assert_params
     from src.initializers import init_params
-    eng, ref0, ns = _engine(1, False)
-    ref = EngineRef(init_params(ns, seed=31, stddev=0.08), 32, 5, 6, 'a3c', 0, 128, 31, world_size=W,
-                    learning_rate=3e-3)
+    kw.setdefault('learning_rate', 3e-3)
+    eng, ref0, ns = _engine(1, False, E=E, seed=seed, world=world, frames=frames, **kw)
+    ref = EngineRef(init_params(ns, seed=seed, stddev=0.08), E, 5, 6, 'a3c', 0, frames, seed, world_size=world,
+                    **{k: v for k, v in kw.items() if k in REF_KEYS})
     ref.reset()
-    ps = LoopbackPS(eng.params.numel(), W, split=True)
-    for it in range(3):
+    ps = LoopbackPS(eng.params.numel(), world, split=True)
+    for it in range(iters):
         Pk = unflat(eng, ns, eng.params)
         eng.rollout_grad()
         torch.cuda.synchronize()
@@ -66,13 +74,16 @@ def test_loopback_split_exchange_matches_oracle():
         planes = rollout_planes(ref, 5)
         tgt = eng.returns.cpu().numpy()
         np.testing.assert_allclose(tgt, out['target'], rtol=1e-5, atol=1e-5)
-        _, g = same_act_grads(eng, planes, Pk, 'a3c', 6, 5, 32, tgt)
-        clipped = {k: Rc.clip_by_norm(v, 40.0) for k, v in g.items()}
+        _, g = same_act_grads(eng, planes, Pk, 'a3c', 6, 5, E, tgt, ref.h['beta'], ref.h['literal_adv'])
+        clipped = {k: Rc.clip_by_norm(v, ref.h['clip_norm']) for k, v in g.items()}
         G = unflat(eng, ns, eng.grads)             # world > 1: clipped per worker by the backward
         for name, _ in ns:
             assert rel_l2(G[name], clipped[name]) < 1e-4, (it, name)
         ps.apply(eng)
         torch.cuda.synchronize()
-        ref.apply_sequence([clipped] * W)
+        lr = ref.apply_sequence([clipped] * world)
         assert_params(eng, ns, ref, it)
-        assert int(eng.counters[1].item()) == ref.global_step == (it + 1) * 5 * 32 * W
+        assert int(eng.counters[1].item()) == ref.global_step == (it + 1) * 5 * E * world
+        if on_update is not None:
+            on_update(it, eng, ref, lr)
+    return eng, ref

@@ -13,8 +13,10 @@ torch = pytest.importorskip('torch')
 
 from oracle import ref_cpu as Rc  # noqa: E402
 from oracle.engine_ref import EngineRef  # noqa: E402
-from _engine_parity import (assert_draws_explained, assert_independent_grads, assert_saved_acts,  # noqa: E402
-                            report_independent)
+from _engine_parity import (REF_KEYS, assert_draws_explained, assert_independent_grads,  # noqa: E402
+                            assert_saved_acts, report_independent)
+
+NOT_LSTM = ('dqn_type', 'double_q', 'target_q_update_step')     # options of the other heads / of Q-learning
 
 U = 256
 
@@ -95,7 +97,7 @@ def build(A, E, n, lives, seed, frames=48, scale=4.0, **kw):
     p = init_params(ns, seed=seed, stddev=0.02 * scale)
     eng.reset(flatten_host(ns, eng.offsets, eng.params.numel(), p))
     ref = EngineRef(p, E, n, A, 'a3c', lives, frames, seed, lstm=True,
-                    **{k: v for k, v in kw.items() if k in ('learning_rate',)})
+                    **{k: v for k, v in kw.items() if k in REF_KEYS and k not in NOT_LSTM})
     ref.reset()
     return eng, ref, ns
 
@@ -105,7 +107,7 @@ def unflat(eng, ns, flat):
     return {name: f[off:off + sz].reshape(shp) for (name, shp), off, sz in zip(ns, eng.offsets, eng.sizes)}
 
 
-def same_act_grads(slot, planes, P, A, n, E, tgt, terms):
+def same_act_grads(slot, planes, P, A, n, E, tgt, terms, beta=0.01, literal_adv=False):
     """oracle backward (heads, BPTT, trunk) on the engine's own saved activations and LSTM sequence."""
     B = n * E
     l1 = slot['act_l1'].cpu().numpy().astype(np.float64).reshape(B, 20, 20, 16)
@@ -118,7 +120,7 @@ def same_act_grads(slot, planes, P, A, n, E, tgt, terms):
     fwd = dict(z=z, h3=h3, flat=l2, lstm=seq, x_seq=h3.reshape(n, E, -1),
                acts=[Rc.states_nhwc(planes).astype(np.float64) / 255.0, l1, l2.reshape(B, 9, 9, 32)])
     acts = slot['actions'].cpu().numpy().reshape(-1)
-    losses, dz = Rc.a3c_loss_and_dz(z, acts, tgt.reshape(-1).astype(np.float64), 0.01)
+    losses, dz = Rc.a3c_loss_and_dz(z, acts, tgt.reshape(-1).astype(np.float64), beta, bool(literal_adv))
     g = Rc.lstm_a3c_backward(P, fwd, dz, terms)
     return losses, {k: np.asarray(v, np.float32).reshape(P[k].shape) for k, v in g.items()}
 
@@ -127,8 +129,14 @@ def same_act_grads(slot, planes, P, A, n, E, tgt, terms):
 def test_engine_lstm_matches_oracle(A, E, n, lives):
     """(A = 18: the LSTM head on h through the wide head_row at W = 256 and the wide categorical
     select_with, rows of stride zs = 20 through k_head_bwd and the head GEMM.)"""
-    eng, ref, ns = build(A, E, n, lives, seed=300 + E, learning_rate=2e-3)
-    for it in range(4):
+    check_lstm_sync_vs_oracle(A, E, n, lives, learning_rate=2e-3)
+
+
+def check_lstm_sync_vs_oracle(A, E, n, lives, iters=4, on_update=None, **kw):
+    """The synchronous LSTM engine against the oracle, every iteration; the hyperparameters in kw
+    reach both.  on_update(it, eng, ref, lr): called after every checked update."""
+    eng, ref, ns = build(A, E, n, lives, seed=300 + E, **kw)
+    for it in range(iters):
         Pk = unflat(eng, ns, eng.params)
         eng.rollout_grad()
         torch.cuda.synchronize()
@@ -150,7 +158,8 @@ def test_engine_lstm_matches_oracle(A, E, n, lives):
         tgt = eng.returns.cpu().numpy()
         np.testing.assert_allclose(tgt, out['target'], rtol=1e-4, atol=2e-5)
         planes = np.concatenate([np.transpose(ref.states(ref.tau + t), (0, 3, 1, 2)) for t in range(n)])
-        losses, g_same = same_act_grads(eng.slot(0), planes, Pk, A, n, E, tgt, terms)
+        losses, g_same = same_act_grads(eng.slot(0), planes, Pk, A, n, E, tgt, terms, ref.h['beta'],
+                                        ref.h['literal_adv'])
         loss = eng.loss.cpu().numpy()
         for i, key in enumerate(('policy', 'value', 'entropy', 'total')):
             assert abs(loss[i] - losses[key]) <= 1e-4 * max(1.0, abs(losses[key])), (it, key, loss[i], losses[key])
@@ -160,12 +169,15 @@ def test_engine_lstm_matches_oracle(A, E, n, lives):
             assert rel_l2(G[name], g_same[name]) < 1e-4, (it, name, rel_l2(G[name], g_same[name]))
             assert rel_l2(G[name], out['grads'][name]) < 2e-2, (it, name)
         eng.apply()
-        ref.apply({k: Rc.clip_by_norm(v, 40.0) for k, v in g_same.items()})
+        lr = ref.apply({k: Rc.clip_by_norm(v, ref.h['clip_norm']) for k, v in g_same.items()})
         torch.cuda.synchronize()
         P = unflat(eng, ns, eng.params)
         for name, _ in ns:
             d = np.abs(P[name] - ref.params[name]).max()
             assert d <= 1e-5 * max(1.0, np.abs(ref.params[name]).max()), (it, name, d)
+        if on_update is not None:
+            on_update(it, eng, ref, lr)
+    return eng, ref
 
 
 def test_engine_lstm_overlap_zero_lr_equals_sync():
@@ -281,7 +293,8 @@ def test_engine_lstm_overlap_matches_oracle(E, frames):
         for name, _ in ns:
             assert rel_l2(G[name], g_same[name]) < 1e-4, (k, name, rel_l2(G[name], g_same[name]))
         assert_independent_grads(G, out_p['grads'], names, k, worst)
-        ref.apply({kk: Rc.clip_by_norm(v, 40.0) for kk, v in g_same.items()}, advance_tau=False, tau=out_p['tau'])
+        ref.apply({kk: Rc.clip_by_norm(v, ref.h['clip_norm']) for kk, v in g_same.items()}, advance_tau=False,
+                  tau=out_p['tau'])
         P = unflat(eng, ns, eng.params)
         for name, _ in ns:
             d = np.abs(P[name] - ref.params[name]).max()
