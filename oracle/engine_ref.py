@@ -156,6 +156,7 @@ class EngineRef:
         rewards = np.zeros((n, E), np.float32)
         rewards_raw = np.zeros((n, E), np.float32)
         terms = np.zeros((n, E), np.uint8)
+        overs = np.zeros((n, E), np.uint8)     # game overs: the terminals whose new game was a reset
         us = np.zeros((n, E), np.float32)
         epss = np.zeros((n, E), np.float32)
         zs, pis, frames = [], [], []
@@ -182,11 +183,13 @@ class EngineRef:
             for e in range(E):
                 self.ring[e, (self.tau + t + 1) % self.R] = self.screen_of(frame[e])
             if term.any():
+                episode = self.env.episode.copy()
                 self.env.new_random_game(term.astype(bool))
+                overs[t] = self.env.episode != episode          # environment.py:29-30
         states = np.concatenate([self.states(self.tau + t) for t in range(n)])      # b = t*E + e
         B = n * E
         out = dict(actions=acts, sampled=sampled, rewards=rewards, rewards_raw=rewards_raw, terminals=terms,
-                   z=np.stack(zs), u=us, eps=epss, h0c0=h0c0,
+                   game_overs=overs, z=np.stack(zs), u=us, eps=epss, h0c0=h0c0,
                    pi=pis, frames=np.stack(frames), tau=self.tau)
         if self.algo == 'a3c':
             zb, _ = self._step_z(self.states(self.tau + n), self.hc)

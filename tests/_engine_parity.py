@@ -44,6 +44,12 @@ Every check_* asserts all three plus the independent loss.  Q-learning on the ov
 forms its TD targets late (with the target network as it stands after rollout k), so its
 independent leg is q_independent on those late targets, not the rollout-time oracle batch.
 The largest independent rel-L2 a check saw is printed at its end and kept in INDEPENDENT_MAX.
+Episode boundaries: every check also counts the terminals and game overs of its rollouts per
+(rollout, t) cell (EpisodeCount; printed, kept in EPISODE_COUNTS and left on the returned oracle as
+ref.episode_counts), and compares the env state after every synchronised iteration.  The env ends
+an episode only after 200-2000 steps, so a check that must see game overs passes
+start=scheduled(K), which shortens ep_len in engine and oracle alike (schedule, end_episodes);
+tests/test_gpu_episode_ends.py does, and asserts the counts.
 Reference: agent.py:141-207 (act / observe / batch_update), agent.py:306-321 (loss, clip, apply),
 network.py:60-94 + assets/a3c.png (A3C losses, n-step returns), main.py:63-65 (RMSProp)."""
 import numpy as np
@@ -136,9 +142,11 @@ def assert_saved_acts(slot, out, n, E, tag, rtol=1e-4):
                                    err_msg=str((tag, f'act_l{i + 1}')))
     if 'lstm' in out:
         seq = out['lstm']
-        np.testing.assert_allclose(g('lstm_h').cpu().numpy(), seq['H'], rtol=1e-4, atol=2e-5,
-                                   err_msg=str((tag, 'lstm_h')))
-        for key, rk in (('lstm_c', 'C'), ('lstm_gates', 'G')):
+        # (lstm_hp / lstm_cp: every step's carried-in state, zeroed where the step before it -- the
+        # previous rollout's last step for t = 0 -- was terminal)
+        for key, rk in (('lstm_h', 'H'), ('lstm_hp', 'HP')):
+            np.testing.assert_allclose(g(key).cpu().numpy(), seq[rk], rtol=1e-4, atol=2e-5, err_msg=str((tag, key)))
+        for key, rk in (('lstm_c', 'C'), ('lstm_cp', 'CP'), ('lstm_gates', 'G')):
             r = np.asarray(seq[rk])
             np.testing.assert_allclose(g(key).cpu().numpy(), r, rtol=rtol,
                                        atol=rtol * max(1.0, float(np.abs(r).max())), err_msg=str((tag, key)))
@@ -164,6 +172,76 @@ def report_independent(label, worst):
     print(f'independent rel-L2 max {label}: {top:.3e} ' +
           ' '.join(f'{k}={v:.1e}' for k, v in sorted(worst.items())))
     return top
+
+
+EPISODE_COUNTS = {}      # label of a check -> the terminals and game overs it saw (EpisodeCount.report)
+
+
+def schedule(E, n, K, action_repeat=1):
+    """Steps-from-now d [E] that put one game over on every (rollout, t) cell of K rollouts of n
+    steps when E >= n * K: env e ends at env step e % (n * K).  In raw emulator steps; with
+    action_repeat = r the episode of env e ends e % r raw steps before its act would finish, in
+    the middle of the repeat (environment.py:78-96, the break on terminal)."""
+    e = np.arange(E, dtype=np.int64)
+    r = int(action_repeat)
+    return r * (1 + e % (n * K)) - e % r
+
+
+def end_episodes(eng, ref, d, host_envs=None):
+    """End env e's episode d[e] >= 1 raw steps from now, in the engine and the oracle alike:
+    ep_len = ep_step + d (the oracle's ep_step: the two are in lock-step).  The engine's env state
+    is double-buffered by step parity; both rows are written, and the one that is not current is
+    overwritten by the next step.  Only on an idle engine.  After its reset an env draws a new
+    ep_len >= 200, so every env ends once per call.  host_envs: the per-env SyntheticAtari objects
+    of a host-stepped engine (whose envs are not on the device), shortened instead."""
+    d = np.asarray(d, np.int64)
+    assert d.shape == (ref.E,) and (d >= 1).all()
+    new = ref.env.ep_step.astype(np.int64) + d
+    ref.env.ep_len[:] = new.astype(np.uint32)
+    if host_envs is not None:
+        for e, env in enumerate(host_envs):
+            assert env.E == 1 and int(env.ep_step[0]) == int(ref.env.ep_step[e])
+            env.ep_len[0] = new[e]
+        return
+    torch.cuda.synchronize()
+    row = torch.as_tensor(new.astype(np.int32)).cuda()
+    for parity in range(2):
+        eng._env['ep_len'][parity].copy_(row)
+    torch.cuda.synchronize()
+
+
+def scheduled(K, host_envs=None):
+    """A check's start(eng, ref) hook: schedule() over K back-propagated rollouts."""
+    def start(eng, ref):
+        end_episodes(eng, ref, schedule(ref.E, ref.n, K, ref.env.action_repeat),
+                     None if host_envs is None else host_envs())
+    return start
+
+
+class EpisodeCount:
+    """Terminals and game overs of a check's rollouts by (rollout, t) cell, from the oracle's
+    replay (out['terminals'], out['game_overs']: the env_reset calls, where `episode` advanced)."""
+
+    def __init__(self):
+        self.terms, self.overs = [], []
+
+    def add(self, out):
+        self.terms.append(out['terminals'].astype(np.int64).sum(axis=1))
+        self.overs.append(out['game_overs'].astype(np.int64).sum(axis=1))
+
+    def report(self, label, backprop=None):
+        """Log the counts (pytest -s) and keep them in EPISODE_COUNTS[label].  backprop: how many of
+        the rollouts were back-propagated (default: all); 'cells' / 'terminal_cells' [backprop, n]
+        hold those rollouts only, which is what a coverage assertion is about."""
+        terms, overs = np.array(self.terms), np.array(self.overs)
+        K = len(terms) if backprop is None else backprop
+        c = dict(rollouts=len(terms), backprop=K, terminals=int(terms.sum()), first=int(terms[:, 0].sum()),
+                 last=int(terms[:, -1].sum()), game_overs=int(overs.sum()), cells=overs[:K], terminal_cells=terms[:K])
+        EPISODE_COUNTS[label] = c
+        print(f"episode ends {label}: terminals {c['terminals']} (first / last step {c['first']} / {c['last']}) "
+              f"game overs {c['game_overs']}, per (rollout, t) of the {K} back-propagated rollouts "
+              f"{overs[:K].tolist()}")
+        return c
 
 
 def q_independent(P, planes, actions, want):
@@ -250,10 +328,12 @@ def assert_params(eng, ns, ref, tag):
         assert d <= 1e-5 * max(1.0, np.abs(ref.params[name]).max()), (tag, name, d)
 
 
-def assert_env_state(eng, ref, tag):
+def assert_env_state(eng, ref, tag, tau=None):
+    """tau: the step whose parity row is current (default: the engine's own tau counter)."""
     for f, ref_v in (('frame', ref.env.frame), ('lives', ref.env.lives), ('episode', ref.env.episode),
                      ('ep_step', ref.env.ep_step), ('ep_len', ref.env.ep_len)):
-        assert np.array_equal(eng.env_field(f).cpu().numpy(), ref_v.astype(np.int32)), (tag, f)
+        got = eng.env_field(f) if tau is None else eng._env[f][int(tau) & 1]
+        assert np.array_equal(got.cpu().numpy(), ref_v.astype(np.int32)), (tag, f)
 
 
 def check_sync_vs_oracle(algo, A, E, n, lives, iters=3, seed=None, frames=48, scale=4.0, independent=True,
@@ -280,6 +360,7 @@ def check_sync_vs_oracle(algo, A, E, n, lives, iters=3, seed=None, frames=48, sc
         assert np.array_equal(eng.env_frame.cpu().numpy(), ref.env.frame.astype(np.int32))
     R = eng.ring_slots
     worst = {}
+    counts = EpisodeCount()
     ring = eng.frame_ring.cpu().numpy()
     for c in range(4):
         assert np.array_equal(ring[:, c % R], ref.ring[:, c % R])
@@ -291,6 +372,7 @@ def check_sync_vs_oracle(algo, A, E, n, lives, iters=3, seed=None, frames=48, sc
         torch.cuda.synchronize()
         acts = eng.actions.cpu().numpy()
         out = ref.iterate(forced_actions=acts)
+        counts.add(out)
         planes = rollout_planes(ref, n)           # after: the rollout's own frames are in the ring
         zw = A + 1 if algo == 'a3c' else A
         z_eng = eng.z.cpu().numpy()[:n].reshape(n, E, -1)
@@ -334,12 +416,14 @@ def check_sync_vs_oracle(algo, A, E, n, lives, iters=3, seed=None, frames=48, sc
                 np.testing.assert_allclose(T[name], ref.tparams[name], rtol=1e-5, atol=1e-6)
     if pool is not None:
         pool.close()
-    report_independent(f'sync {algo} A={A} E={E} n={n} {eng.dqn_type}', worst)
+    label = f'sync {algo} A={A} E={E} n={n} {eng.dqn_type}'
+    report_independent(label, worst)
+    ref.episode_counts = counts.report(label)
     return eng, ref
 
 
 def check_overlap_vs_oracle(A, E, n, lives, rollouts=5, seed=77, frames=48, scale=4.0, algo='a3c', hogwild=False,
-                            on_update=None, **kw):
+                            on_update=None, start=None, **kw):
     """Overlap (stale-1) pipeline: rollout k uses the parameters after update k-2.  The oracle is
     replayed in that order with the engine's own actions and activations.  algo='q': the TD targets
     of rollout k-1 are formed by its backward, after rollout k, with the target network as it
@@ -350,7 +434,9 @@ def check_overlap_vs_oracle(A, E, n, lives, rollouts=5, seed=77, frames=48, scal
     After iterate() k, slot k-1 -- the buffer the backward just consumed -- is held against the
     independent forward of rollout k-1 (assert_saved_acts), and the engine's loss, head rows and
     gradient against the independent leg (q: q_independent on the late targets; hogwild: the
-    clipped independent gradient, the engine's buffer being clipped in place)."""
+    clipped independent gradient, the engine's buffer being clipped in place).
+    start(eng, ref): called once before the first rollout, on the idle engine.  After every
+    iterate() the env state (episode, ep_step, ep_len, lives, frame) equals the oracle's."""
     if algo == 'q':
         kw.setdefault('target_q_update_step', 40)
     eng, ref, ns = build(algo, A, E, n, lives, seed=seed, frames=frames, scale=scale, overlap=True, **kw)
@@ -360,7 +446,11 @@ def check_overlap_vs_oracle(A, E, n, lives, rollouts=5, seed=77, frames=48, scal
         ps = HogwildPS(eng.params, decay=ref.h['decay'], momentum=ref.h['momentum'], epsilon=ref.h['epsilon'])
     hist = []                  # per rollout: (oracle params used, planes, oracle out)
     worst = {}
+    counts = EpisodeCount()
     names = [name for name, _ in ns]
+    if start is not None:
+        start(eng, ref)
+        torch.cuda.synchronize()
     for k in range(rollouts):
         if ps is not None:
             eng.iterate_hogwild(ps)
@@ -375,8 +465,10 @@ def check_overlap_vs_oracle(A, E, n, lives, rollouts=5, seed=77, frames=48, scal
         if algo == 'q':                                 # s_{t+1} of every step, for the late TD target
             out['next_states'] = np.concatenate([ref.states(ref.tau + t + 1) for t in range(n)])
         ref.tau += n                                    # the rollout owns tau in overlap mode
+        counts.add(out)
         assert np.array_equal(sl['rewards'].cpu().numpy(), out['rewards']), k
         assert np.array_equal(sl['terminals'].cpu().numpy(), out['terminals']), k
+        assert_env_state(eng, ref, k, tau=ref.tau)      # (the row by the oracle's tau: the engine is idle)
         ring = eng.frame_ring.cpu().numpy()            # the rollout's new screens, bit-exact
         for t in range(n):
             tt = ref.tau - n + t + 1
@@ -439,27 +531,36 @@ def check_overlap_vs_oracle(A, E, n, lives, rollouts=5, seed=77, frames=48, scal
                 np.testing.assert_allclose(T[name], ref.tparams[name], rtol=1e-5, atol=1e-6)
     if ps is not None:
         ps.close()
-    report_independent(f"overlap{'-hogwild' if hogwild else ''} {algo} A={A} E={E} n={n} {eng.dqn_type}", worst)
+    label = f"overlap{'-hogwild' if hogwild else ''} {algo} A={A} E={E} n={n} {eng.dqn_type}"
+    report_independent(label, worst)
+    ref.episode_counts = counts.report(label, backprop=rollouts - 1)    # (the last rollout has no backward)
     return eng, ref
 
 
-def check_hogwild1_vs_oracle(A, E, n, lives, iters=3, seed=91, frames=48, scale=4.0, on_update=None, **kw):
+def check_hogwild1_vs_oracle(A, E, n, lives, iters=3, seed=91, frames=48, scale=4.0, on_update=None, start=None,
+                             **kw):
     """Hogwild with one worker (src/hogwild.py at world 1): rollout + gradient, per-worker clip,
     unlocked RMSProp push into the sharded PS, pull.  With one worker the push order is fixed, so
-    it must equal the oracle's clip + RMSProp step for step."""
+    it must equal the oracle's clip + RMSProp step for step.
+    start(eng, ref): called once before the first rollout."""
     from src.hogwild import HogwildPS
     algo = 'a3c'
     eng, ref, ns = build(algo, A, E, n, lives, seed=seed, frames=frames, scale=scale, **kw)
     ps = HogwildPS(eng.params, decay=ref.h['decay'], momentum=ref.h['momentum'], epsilon=ref.h['epsilon'])
     worst = {}
+    counts = EpisodeCount()
     names = [name for name, _ in ns]
     try:
+        if start is not None:
+            start(eng, ref)
+            torch.cuda.synchronize()
         for it in range(iters):
             Pk = unflat(eng, ns, eng.params)
             eng.iterate_hogwild(ps)
             torch.cuda.synchronize()
             acts = eng.actions.cpu().numpy()
             out = ref.iterate(forced_actions=acts)
+            counts.add(out)
             planes = rollout_planes(ref, n)
             z_eng = eng.z.cpu().numpy()[:n].reshape(n, E, -1)
             assert_draws_explained(acts, out, algo, A, it, z_eng=z_eng)
@@ -485,7 +586,10 @@ def check_hogwild1_vs_oracle(A, E, n, lives, iters=3, seed=91, frames=48, scale=
             assert torch.equal(ps.gather(), eng.params)
             cnt = eng.counters.cpu().numpy()
             assert cnt[0] == ref.tau and cnt[1] == ref.global_step
+            assert_env_state(eng, ref, it)
     finally:
         ps.close()
-    report_independent(f'hogwild-sync a3c A={A} E={E} n={n}', worst)
+    label = f'hogwild-sync a3c A={A} E={E} n={n}'
+    report_independent(label, worst)
+    ref.episode_counts = counts.report(label)
     return eng, ref

@@ -13,8 +13,8 @@ torch = pytest.importorskip('torch')
 
 from oracle import ref_cpu as Rc  # noqa: E402
 from oracle.engine_ref import EngineRef  # noqa: E402
-from _engine_parity import (REF_KEYS, assert_draws_explained, assert_independent_grads,  # noqa: E402
-                            assert_saved_acts, report_independent)
+from _engine_parity import (REF_KEYS, EpisodeCount, assert_draws_explained, assert_env_state,  # noqa: E402
+                            assert_independent_grads, assert_saved_acts, report_independent)
 
 NOT_LSTM = ('dqn_type', 'double_q', 'target_q_update_step')     # options of the other heads / of Q-learning
 
@@ -132,10 +132,15 @@ def test_engine_lstm_matches_oracle(A, E, n, lives):
     check_lstm_sync_vs_oracle(A, E, n, lives, learning_rate=2e-3)
 
 
-def check_lstm_sync_vs_oracle(A, E, n, lives, iters=4, on_update=None, **kw):
+def check_lstm_sync_vs_oracle(A, E, n, lives, iters=4, on_update=None, start=None, seed=None, **kw):
     """The synchronous LSTM engine against the oracle, every iteration; the hyperparameters in kw
-    reach both.  on_update(it, eng, ref, lr): called after every checked update."""
-    eng, ref, ns = build(A, E, n, lives, seed=300 + E, **kw)
+    reach both.  on_update(it, eng, ref, lr): called after every checked update.
+    start(eng, ref): called once before the first rollout."""
+    eng, ref, ns = build(A, E, n, lives, seed=300 + E if seed is None else seed, **kw)
+    counts = EpisodeCount()
+    if start is not None:
+        start(eng, ref)
+        torch.cuda.synchronize()
     for it in range(iters):
         Pk = unflat(eng, ns, eng.params)
         eng.rollout_grad()
@@ -145,6 +150,7 @@ def check_lstm_sync_vs_oracle(A, E, n, lives, iters=4, on_update=None, **kw):
         # the rollout's carry-in state = the oracle's carry (computed on its own fp64 forward)
         np.testing.assert_allclose(eng.lstm_hp.cpu().numpy()[0], h0, rtol=1e-4, atol=2e-5)
         out = ref.iterate(forced_actions=acts)
+        counts.add(out)
         assert_draws_explained(acts, out, 'a3c', A, it, z_eng=eng.z.cpu().numpy()[:n])
         assert np.array_equal(eng.rewards.cpu().numpy(), out['rewards'])
         terms = eng.terminals.cpu().numpy()
@@ -175,8 +181,10 @@ def check_lstm_sync_vs_oracle(A, E, n, lives, iters=4, on_update=None, **kw):
         for name, _ in ns:
             d = np.abs(P[name] - ref.params[name]).max()
             assert d <= 1e-5 * max(1.0, np.abs(ref.params[name]).max()), (it, name, d)
+        assert_env_state(eng, ref, it)
         if on_update is not None:
             on_update(it, eng, ref, lr)
+    ref.episode_counts = counts.report(f'lstm sync A={A} E={E} n={n}')
     return eng, ref
 
 
@@ -252,13 +260,22 @@ def test_engine_lstm_overlap_matches_oracle(E, frames):
     After iterate() k, slot k-1 (the buffers the backward just consumed) is held against the oracle's
     independent fp64 forward of rollout k-1: trunk activations, lstm_h / lstm_c / lstm_gates, losses
     and gradients (2e-2, the bound of the synchronous test)."""
+    check_lstm_overlap_vs_oracle(6, E, 5, 3, rollouts=4, seed=60 + E, frames=frames, scale=2.0, learning_rate=2e-3)
+
+
+def check_lstm_overlap_vs_oracle(A, E, n, lives, rollouts=4, seed=76, start=None, **kw):
+    """The pipelined LSTM engine against the oracle (see test_engine_lstm_overlap_matches_oracle).
+    start(eng, ref): called once before the first rollout, on the idle engine."""
     from _engine_parity import rollout_planes
-    A, n = 6, 5
-    eng, ref, ns = build(A, E, n, 3, seed=60 + E, frames=frames, scale=2.0, learning_rate=2e-3, overlap=True)
+    eng, ref, ns = build(A, E, n, lives, seed=seed, overlap=True, **kw)
     hist = []
     worst = {}
+    counts = EpisodeCount()
     names = [name for name, _ in ns]
-    for k in range(4):
+    if start is not None:
+        start(eng, ref)
+        torch.cuda.synchronize()
+    for k in range(rollouts):
         eng.iterate()
         torch.cuda.synchronize()
         sl = eng.slot(k & 1)
@@ -266,8 +283,10 @@ def test_engine_lstm_overlap_matches_oracle(E, frames):
         out = ref.iterate(forced_actions=sl['actions'].cpu().numpy())
         planes = rollout_planes(ref, n)
         ref.tau += n
+        counts.add(out)
         assert np.array_equal(sl['rewards'].cpu().numpy(), out['rewards']), k
         assert np.array_equal(sl['terminals'].cpu().numpy(), out['terminals']), k
+        assert_env_state(eng, ref, k, tau=ref.tau)
         assert_draws_explained(sl['actions'].cpu().numpy(), out, 'a3c', A, k,
                                z_eng=sl['z'].cpu().numpy()[:n].reshape(n, E, -1))
         z = sl['z'].cpu().numpy()[:n].reshape(n, E, -1)[:, :, :A + 1]
@@ -300,3 +319,5 @@ def test_engine_lstm_overlap_matches_oracle(E, frames):
             d = np.abs(P[name] - ref.params[name]).max()
             assert d <= 1e-5 * max(1.0, np.abs(ref.params[name]).max()), (k, name, d)
     report_independent(f'lstm overlap E={E}', worst)
+    ref.episode_counts = counts.report(f'lstm overlap A={A} E={E} n={n}', backprop=rollouts - 1)
+    return eng, ref
