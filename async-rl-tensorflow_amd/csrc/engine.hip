@@ -104,6 +104,7 @@ struct a3c_engine {
   int overlap, nslot;
   int fused_screen;        // 1: screen kernel fused into the head (k_head_screen)
   int frame84;             // cfg.frame84: pre-sized 84x84 pool frames (measurement mode M2)
+  int game;                // A3C_GAME_*: the device envs' game (a3c_engine_create_ex)
   int fuse_conv;           // 1: step t+1's conv1 + conv2 fused into step t's head + screen
   unsigned long long* spans;  // [2][SPAN_RECS][2]: live launch spans of k_conv_bwd, k_head_screen_conv12
   Slot slot[2];
@@ -244,6 +245,10 @@ static int frame_bytes(const a3c_engine* e) { return e->frame84 ? PLANE : SCREEN
 static bool boot_bwd(const a3c_engine* e);
 static int l2bits_choice(const a3c_engine* e);
 extern "C" int a3c_engine_create(const a3c_engine_config* cfg, a3c_engine** out) {
+  return a3c_engine_create_ex(cfg, A3C_GAME_SYNTH, out);
+}
+
+extern "C" int a3c_engine_create_ex(const a3c_engine_config* cfg, int game, a3c_engine** out) {
   if (!cfg || !out) return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_create", "null");
   *out = nullptr;
   a3c_engine* e = new (std::nothrow) a3c_engine();
@@ -274,6 +279,19 @@ extern "C" int a3c_engine_create(const a3c_engine_config* cfg, a3c_engine** out)
     return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_create",
                          "gae_lambda != 1 with literal_adv: the lambda-return is a constant of the gradient");
   }
+  if (game != A3C_GAME_SYNTH && game != A3C_GAME_CATCH) {
+    delete e;
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_create", "unknown game");
+  }
+  // Catch: its frame index is its state, f < 640 -- the pool must hold those frames, as
+  // raw RGB, on the device
+  if (game == A3C_GAME_CATCH && (cfg->num_frames < 640 || cfg->net.action_size != 3 || cfg->start_lives != 0 ||
+                                      cfg->frame84 || cfg->external_env)) {
+    delete e;
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_create",
+                         "Catch needs num_frames >= 640, action_size 3, start_lives 0, no frame84, no external_env");
+  }
+  e->game = game;
   a3c_init_once();
   const NetLayout& L = e->L;
   e->E = cfg->num_envs;
@@ -462,6 +480,7 @@ extern "C" int a3c_engine_create(const a3c_engine_config* cfg, a3c_engine** out)
   e->envp.random_start = cfg->random_start;
   e->envp.action_repeat = cfg->action_repeat;
   e->envp.env_id_base = cfg->env_id_base;
+  e->envp.game = e->game;
   // per-env final epsilon (main.py:68 samples ep_end per worker from {0.1, 0.01, 0.5})
   std::vector<int32_t> idx(E);
   for (int64_t i = 0; i < E; ++i) idx[i] = (int32_t)i;
@@ -1154,7 +1173,9 @@ extern "C" int a3c_engine_reset(a3c_engine* e, const float* host_params, void* s
   A3C_CHECK(hipMemsetAsync(e->loss, 0, 64, s));
   A3C_CHECK(hipMemsetAsync(e->ring, 0, (size_t)e->E * e->R * PLANE, s));
   if (!e->ext) {
-    rc = a3c_pool_fill_launch(e->pool, e->cfg.num_frames, e->k0, e->k1, s, frame_bytes(e));
+    rc = e->envp.game == A3C_GAME_CATCH     // (rendered from the frame index, not hashed: DESIGN §4g)
+             ? a3c_pool_render_catch_launch(e->pool, e->cfg.num_frames, s)
+             : a3c_pool_fill_launch(e->pool, e->cfg.num_frames, e->k0, e->k1, s, frame_bytes(e));
     if (rc) return rc;
     rc = a3c_env_init_launch(e->envp, e->env, e->E, e->pool, e->ring, e->R, e->counters, s, e->frame84);
     if (rc) return rc;

@@ -25,12 +25,14 @@ __global__ void k_pool_fill(uint8_t* __restrict__ pool, int64_t chunks_per_frame
 // reset every env (state zeroed, lives = 0 so new_game resets), new_random_game, and fill the
 // history with HIST copies of the first screen (agent.py:35-38).  tau := HIST-1; the env
 // state lives at parity (tau & 1) of the double-buffered state arrays.
+// (GAME: A3C_GAME_*; the Catch instantiations of this file's kernels are launched at its end)
+template <int GAME = A3C_GAME_SYNTH>
 __global__ void k_env_init_state(EnvParams p, EnvBufs b, int E, int64_t* __restrict__ counters) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e == 0) { counters[0] = HIST - 1; counters[1] = 0; counters[2] = 0; }   // tau, global, worker step
   if (e >= E) return;
   EnvState s = {0u, 0u, 0u, 0, 0, 0.f, 0u};
-  env_new_random_game(s, p, (uint32_t)(p.env_id_base + e));
+  game_new_random_game<GAME>(s, p, (uint32_t)(p.env_id_base + e));
   env_store(b, (int64_t)((HIST - 1) & 1) * E + e, s);
 }
 
@@ -77,6 +79,9 @@ __global__ void __launch_bounds__(256) k_env_init_copy84(EnvBufs b, int E, const
 
 // frame f, 16-byte chunk j = philox(j, f, P_POOL, 0): frame_bytes = 210*160*3 (RGB frames) or
 // 84*84 (mode M2 -- the first 441 chunks of the same hash)
+static int catch_init_state_launch(const EnvParams& p, const EnvBufs& b, int E, int64_t* counters, hipStream_t s);
+static int catch_play_begin_state_launch(const EnvParams& p, const EnvBufs& b, int E, int n_active, int64_t tau,
+                                         const PlayBook& bk, int64_t* counters, hipStream_t s);
 int a3c_pool_fill_launch(uint8_t* pool, int P, uint32_t k0, uint32_t k1, hipStream_t s, int frame_bytes) {
   const int64_t cpf = frame_bytes / 16;
   const int64_t total = cpf * P;
@@ -88,7 +93,11 @@ int a3c_pool_fill_launch(uint8_t* pool, int P, uint32_t k0, uint32_t k1, hipStre
 int a3c_env_init_launch(const EnvParams& p, const EnvBufs& b, int E, const uint8_t* pool, uint8_t* ring,
                         int R, int64_t* counters, hipStream_t s, int frame84) {
   PreGeom g = a3c_make_geom(SCREEN_H, SCREEN_W, IMG_OUT, IMG_OUT);
-  hipLaunchKernelGGL(k_env_init_state, dim3((E + 63) / 64), dim3(64), 0, s, p, b, E, counters);
+  if (p.game == A3C_GAME_CATCH) {
+    if (int rc = catch_init_state_launch(p, b, E, counters, s)) return rc;
+  } else {
+    hipLaunchKernelGGL(k_env_init_state<>, dim3((E + 63) / 64), dim3(64), 0, s, p, b, E, counters);
+  }
   A3C_CHECK(hipGetLastError());
   if (frame84) {
     hipLaunchKernelGGL(k_env_init_copy84, dim3(E), dim3(256), 0, s, b, E, pool, ring, R);
@@ -113,6 +122,7 @@ int a3c_env_init_screens_launch(const EnvBufs& b, int E, const uint8_t* pool, ui
 // The play context keeps both parity copies of an env's state equal, so the state is read from
 // copy 0 and written to both.  Zeroes the wave's return / length / terminated words, freezes the
 // envs without an episode (both parity copies of the flag) and sets the play tau.
+template <int GAME = A3C_GAME_SYNTH>
 __global__ void k_play_begin(EnvParams p, EnvBufs b, int E, int n_active, int64_t tau, PlayBook bk,
                              int64_t* __restrict__ counters) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
@@ -125,7 +135,7 @@ __global__ void k_play_begin(EnvParams p, EnvBufs b, int E, int n_active, int64_
   bk.term[e] = 0;
   if (!active) return;
   EnvState s = env_load(b, e);
-  env_new_random_game(s, p, (uint32_t)(p.env_id_base + e));
+  game_new_random_game<GAME>(s, p, (uint32_t)(p.env_id_base + e));
   env_store(b, e, s);
   env_store(b, (int64_t)E + e, s);
 }
@@ -166,7 +176,11 @@ int a3c_play_begin_launch(const EnvParams& p, const EnvBufs& b, int E, int n_act
                           const uint8_t* pool, uint8_t* ring, int R, int64_t* counters, int frame84, hipStream_t s) {
   if (E < 1 || n_active < 1 || n_active > E || tau < HIST - 1 || R < HIST + 1)
     return a3c_set_error(A3C_ERR_INVALID, "a3c_play_begin", "bad argument");
-  hipLaunchKernelGGL(k_play_begin, dim3((E + 63) / 64), dim3(64), 0, s, p, b, E, n_active, tau, bk, counters);
+  if (p.game == A3C_GAME_CATCH) {
+    if (int rc = catch_play_begin_state_launch(p, b, E, n_active, tau, bk, counters, s)) return rc;
+  } else {
+    hipLaunchKernelGGL(k_play_begin<>, dim3((E + 63) / 64), dim3(64), 0, s, p, b, E, n_active, tau, bk, counters);
+  }
   A3C_CHECK(hipGetLastError());
   if (frame84) {
     hipLaunchKernelGGL(k_play_begin_copy84, dim3(E), dim3(256), 0, s, b, bk.frozen, pool, ring, R, tau);
@@ -180,6 +194,11 @@ int a3c_play_begin_launch(const EnvParams& p, const EnvBufs& b, int E, int n_act
 }
 
 // ---- play with refill: an env whose episode ends takes the next unassigned episode at once ------
+static int catch_refill_set_smem();
+static int catch_refill_launch(const EnvParams& p, const EnvBufs& b, const PlayBook& bk, const PlayRefill& rf, int E, int t,
+                               int64_t tau, const float* rraw, const uint8_t* terms, int64_t* counters,
+                               const uint8_t* pool, uint8_t* ring, int R, const float* h_src, const float* c_src,
+                               float* h_dst, float* c_dst, hipStream_t s);
 // start of the run, behind k_play_begin: episode e on env e < n_active, starting at tau
 __global__ void k_play_refill_begin(PlayRefill rf, int E, int n_active, int64_t tau) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
@@ -217,6 +236,7 @@ __global__ void k_play_refill_begin(PlayRefill rf, int E, int n_active, int64_t 
 // sched (next index, episodes not finished, steps with a live env) and tau.  tau is an argument
 // (HIST-1 + t: a refill run's tau has no gaps), since workgroup 0 writes the counter.
 #define RF_THREADS 512
+template <int GAME = A3C_GAME_SYNTH>
 __global__ void __launch_bounds__(RF_THREADS) k_play_observe_refill(EnvParams p, EnvBufs b, PlayBook bk, PlayRefill rf,
                                                              int E, int t, int64_t tau,
                                                              const float* __restrict__ rraw,
@@ -280,7 +300,7 @@ __global__ void __launch_bounds__(RF_THREADS) k_play_observe_refill(EnvParams p,
     }
     if (refill) {
       EnvState s = env_load(b, e);
-      env_new_random_game(s, p, (uint32_t)(p.env_id_base + e));
+      game_new_random_game<GAME>(s, p, (uint32_t)(p.env_id_base + e));
       env_store(b, e, s);
       env_store(b, (int64_t)E + e, s);
       s_frame = s.frame;
@@ -315,8 +335,9 @@ __global__ void __launch_bounds__(RF_THREADS) k_play_observe_refill(EnvParams p,
 int a3c_play_refill_begin_launch(const PlayRefill& rf, int E, int n_active, int64_t tau, hipStream_t s) {
   if (E < 1 || n_active < 1 || n_active > E || n_active > rf.n_episode || rf.n_step < 1)
     return a3c_set_error(A3C_ERR_INVALID, "a3c_play_refill_begin", "bad argument");
-  A3C_CHECK(hipFuncSetAttribute((const void*)k_play_observe_refill, hipFuncAttributeMaxDynamicSharedMemorySize,
+  A3C_CHECK(hipFuncSetAttribute((const void*)k_play_observe_refill<>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 SCREEN_FRAME_SMEM));
+  if (int rc = catch_refill_set_smem()) return rc;
   hipLaunchKernelGGL(k_play_refill_begin, dim3((E + 63) / 64), dim3(64), 0, s, rf, E, n_active, tau);
   A3C_CHECK(hipGetLastError());
   return 0;
@@ -328,7 +349,9 @@ int a3c_play_refill_launch(const EnvParams& p, const EnvBufs& b, const PlayBook&
                            float* c_dst, hipStream_t s) {
   if (E < 1 || R < HIST + 1 || t < 0 || tau < HIST - 1)
     return a3c_set_error(A3C_ERR_INVALID, "a3c_play_refill", "bad argument");
-  hipLaunchKernelGGL(k_play_observe_refill, dim3(E), dim3(RF_THREADS), frame84 ? 0 : SCREEN_FRAME_SMEM, s, p, b, bk, rf, E,
+  if (p.game == A3C_GAME_CATCH)     // (never with frame84: a3c_engine_create rejects the pair)
+    return catch_refill_launch(p, b, bk, rf, E, t, tau, rraw, terms, counters, pool, ring, R, h_src, c_src, h_dst, c_dst, s);
+  hipLaunchKernelGGL(k_play_observe_refill<>, dim3(E), dim3(RF_THREADS), frame84 ? 0 : SCREEN_FRAME_SMEM, s, p, b, bk, rf, E,
                      t, tau, rraw, terms, counters, pool, ring, R, frame84, h_src, c_src, h_dst, c_dst);
   A3C_CHECK(hipGetLastError());
   return 0;
@@ -353,6 +376,74 @@ int a3c_env_screen_launch(int E, const int32_t* frames, const uint8_t* pool, uin
     case 12: launch_env_screen<12>(E, frames, pool, ring, R, counters, t, s); break;
     default: launch_env_screen<14>(E, frames, pool, ring, R, counters, t, s); break;
   }
+  A3C_CHECK(hipGetLastError());
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Catch (A3C_GAME_CATCH): the pool render kernel and the GAME = A3C_GAME_CATCH
+// instantiations of this file's kernels, emitted behind the default-game ones.
+// ---------------------------------------------------------------------------------------------
+// Frames 0 .. CATCH_FRAMES-1 of the RGB pool, frame f = (c * CATCH_ROWS + r) * CATCH_COLS + p: black,
+// the ball's cell (rows [21 r, 21 r + 21) x cols [20 c, 20 c + 20)) in (236,236,236), then the
+// paddle (rows [200, 210) x cols [20 p, 20 p + 20)) in (92,186,92) over it.  One 16-byte chunk per
+// thread and pass; frames >= CATCH_FRAMES of a larger pool are never read and stay as they are.
+#define CATCH_CELL_W (SCREEN_W / CATCH_COLS)      // 20
+#define CATCH_CELL_H (SCREEN_H / CATCH_ROWS)      // 21
+#define CATCH_PADDLE_Y (SCREEN_H - 10)            // 200
+static_assert(CATCH_CELL_W * CATCH_COLS == SCREEN_W && CATCH_CELL_H * CATCH_ROWS == SCREEN_H, "Catch cells tile the screen");
+__global__ void __launch_bounds__(256) k_pool_render_catch(uint8_t* __restrict__ pool) {
+  constexpr int64_t CPF = SCREEN_H * SCREEN_W * 3 / 16;   // 6300 chunks per frame
+  constexpr int64_t TOTAL = CPF * CATCH_FRAMES;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < TOTAL; i += (int64_t)gridDim.x * blockDim.x) {
+    const int f = (int)(i / CPF), j = (int)(i - (int64_t)f * CPF);
+    const int p = f % CATCH_COLS, r = (f / CATCH_COLS) % CATCH_ROWS, c = f / (CATCH_COLS * CATCH_ROWS);
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+      const int byte = 16 * j + k, pix = byte / 3, ch = byte - 3 * pix;
+      const int y = pix / SCREEN_W, x = pix - y * SCREEN_W;
+      uint32_t v = 0u;
+      if (y / CATCH_CELL_H == r && x / CATCH_CELL_W == c) v = 236u;
+      if (y >= CATCH_PADDLE_Y && x / CATCH_CELL_W == p) v = ch == 1 ? 186u : 92u;
+      w[k >> 2] |= v << (8 * (k & 3));
+    }
+    ((uint4*)pool)[i] = make_uint4(w[0], w[1], w[2], w[3]);
+  }
+}
+
+// P: the pool's frame count (>= CATCH_FRAMES, or nothing is written)
+int a3c_pool_render_catch_launch(uint8_t* pool, int P, hipStream_t s) {
+  if (!pool || P < CATCH_FRAMES) return a3c_set_error(A3C_ERR_INVALID, "a3c_pool_render_catch", "the pool holds fewer than 640 frames");
+  hipLaunchKernelGGL(k_pool_render_catch, dim3(4096), dim3(256), 0, s, pool);
+  A3C_CHECK(hipGetLastError());
+  return 0;
+}
+
+static int catch_init_state_launch(const EnvParams& p, const EnvBufs& b, int E, int64_t* counters, hipStream_t s) {
+  hipLaunchKernelGGL(k_env_init_state<A3C_GAME_CATCH>, dim3((E + 63) / 64), dim3(64), 0, s, p, b, E, counters);
+  return 0;
+}
+
+static int catch_play_begin_state_launch(const EnvParams& p, const EnvBufs& b, int E, int n_active, int64_t tau,
+                                         const PlayBook& bk, int64_t* counters, hipStream_t s) {
+  hipLaunchKernelGGL(k_play_begin<A3C_GAME_CATCH>, dim3((E + 63) / 64), dim3(64), 0, s, p, b, E, n_active, tau, bk,
+                     counters);
+  return 0;
+}
+
+static int catch_refill_set_smem() {
+  A3C_CHECK(hipFuncSetAttribute((const void*)k_play_observe_refill<A3C_GAME_CATCH>,
+                                hipFuncAttributeMaxDynamicSharedMemorySize, SCREEN_FRAME_SMEM));
+  return 0;
+}
+
+static int catch_refill_launch(const EnvParams& p, const EnvBufs& b, const PlayBook& bk, const PlayRefill& rf, int E, int t,
+                               int64_t tau, const float* rraw, const uint8_t* terms, int64_t* counters,
+                               const uint8_t* pool, uint8_t* ring, int R, const float* h_src, const float* c_src,
+                               float* h_dst, float* c_dst, hipStream_t s) {
+  hipLaunchKernelGGL(k_play_observe_refill<A3C_GAME_CATCH>, dim3(E), dim3(RF_THREADS), SCREEN_FRAME_SMEM, s, p, b, bk, rf,
+                     E, t, tau, rraw, terms, counters, pool, ring, R, 0, h_src, c_src, h_dst, c_dst);
   A3C_CHECK(hipGetLastError());
   return 0;
 }

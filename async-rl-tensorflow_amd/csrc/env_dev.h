@@ -98,3 +98,99 @@ __host__ __device__ inline void env_act(EnvState& s, const EnvParams& p, uint32_
   s.frame = env_frame_of(env_act_pre(s, p, id, training), action, p);
 }
 
+
+// ---- Catch (A3C_GAME_CATCH): a game with real dynamics whose whole state is the pool
+// frame index f = (c * CATCH_ROWS + r) * CATCH_COLS + p -- ball column c, ball row r, paddle column
+// p.  ep_step mirrors r, ep_len = CATCH_ROWS - 1, lives stays 0.  The ball falls one row per step;
+// actions 0 stay, 1 left, 2 right (anything else: stay); at the landing (r = CATCH_ROWS - 1) the
+// reward is +1 with the paddle under the ball, else -1, and the episode ends.  No Philox draw in a
+// step, one in a reset.  The act is split for the fused head kernels: catch_act_pre is everything
+// that does not depend on the action (rows, landing, terminal), catch_act_post the paddle move,
+// the reward and the frame index.
+#define CATCH_COLS 8
+#define CATCH_ROWS 10
+#define CATCH_FRAMES (CATCH_COLS * CATCH_ROWS * CATCH_COLS)   // 640
+
+// reset (and new_game / new_random_game: lives == 0 always holds, no no-op steps follow)
+__host__ __device__ inline void catch_reset(EnvState& s, const EnvParams& p, uint32_t id) {
+  s.episode += 1u;
+  u32x4 x = philox4x32(s.episode, id, P_RESET, 0u, p.k0, p.k1);
+  s.ep_step = 0;
+  s.ep_len = CATCH_ROWS - 1;
+  s.lives = 0;
+  s.frame = (int32_t)((x.x % CATCH_COLS) * CATCH_ROWS * CATCH_COLS + x.y % CATCH_COLS);
+  s.reward = 0.f;
+  s.terminal = 0u;
+}
+
+// `repeat` steps of one action up to the action: ball row, landing, terminal (the loop of
+// env_act_pre: stop at a terminal).  s.frame stays the pre-act frame, s.reward is 0 (the reward
+// needs the action).  Returns the word catch_act_post finishes the act from: the pre-act frame
+// reduced into [0, CATCH_FRAMES) | new row << 10 | paddle moves << 14 | landed in this act << 18.
+// A step on a landed state changes nothing: reward 0, terminal 1, no move.
+__host__ __device__ inline uint32_t catch_act_pre(EnvState& s, int repeat) {
+  const uint32_t f = (uint32_t)s.frame % (uint32_t)CATCH_FRAMES;
+  uint32_t r = (f / CATCH_COLS) % CATCH_ROWS, moves = 0, landed = 0;
+  for (int k = 0; k < repeat; ++k) {
+    if (r < CATCH_ROWS - 1) {
+      r += 1u;
+      moves += 1u;
+      landed = r == CATCH_ROWS - 1 ? 1u : 0u;
+    } else {
+      landed = 0u;
+    }
+    if (r == CATCH_ROWS - 1) break;
+  }
+  s.ep_step = r;
+  s.ep_len = CATCH_ROWS - 1;
+  s.lives = 0;
+  s.reward = 0.f;
+  s.terminal = r == CATCH_ROWS - 1 ? 1u : 0u;
+  return f | r << 10 | moves << 14 | landed << 18;
+}
+
+// the action's part: `moves` clamped paddle steps, the landing's reward, the post-act frame index
+// (< CATCH_FRAMES for every word catch_act_pre returns: c, r', p' are each within their range)
+__host__ __device__ inline int32_t catch_act_post(uint32_t w, uint32_t action, float& reward) {
+  const int f = (int)(w & 1023u), r = (int)(w >> 10 & 15u), moves = (int)(w >> 14 & 15u);
+  const int c = f / (CATCH_ROWS * CATCH_COLS);
+  int p = f % CATCH_COLS + moves * ((action == 2u ? 1 : 0) - (action == 1u ? 1 : 0));
+  p = p < 0 ? 0 : (p > CATCH_COLS - 1 ? CATCH_COLS - 1 : p);
+  reward = (w >> 18 & 1u) ? (p == c ? 1.0f : -1.0f) : 0.f;
+  return (c * CATCH_ROWS + r) * CATCH_COLS + p;
+}
+
+// GymEnvironment.act for Catch (is_training makes no difference: no life is ever lost); repeat = 1
+// is the raw step of SimpleGymEnvironment.act
+__host__ __device__ inline void catch_act(EnvState& s, int repeat, uint32_t action) {
+  const uint32_t w = catch_act_pre(s, repeat);
+  s.frame = catch_act_post(w, action, s.reward);
+}
+
+// ---- the game picked at compile time (GAME: A3C_GAME_*), for the kernels that step an env -------
+template <int GAME>
+__host__ __device__ inline void game_new_game(EnvState& s, const EnvParams& p, uint32_t id) {
+  if constexpr (GAME == A3C_GAME_CATCH) {
+    catch_reset(s, p, id);
+  } else {
+    if (s.lives == 0) env_reset(s, p, id);
+    env_step_raw(s, p, id, 0u);
+  }
+}
+
+template <int GAME>
+__host__ __device__ inline void game_new_random_game(EnvState& s, const EnvParams& p, uint32_t id) {
+  if constexpr (GAME == A3C_GAME_CATCH) catch_reset(s, p, id);     // (random_start: the reset is the random start)
+  else env_new_random_game(s, p, id);
+}
+
+template <int GAME>
+__host__ __device__ inline void game_act(EnvState& s, const EnvParams& p, uint32_t id, uint32_t action, bool training,
+                                         bool simple = false) {
+  if constexpr (GAME == A3C_GAME_CATCH) {
+    catch_act(s, simple ? 1 : p.action_repeat, action);
+  } else {
+    if (simple) env_step_raw(s, p, id, action);
+    else env_act(s, p, id, action, training);
+  }
+}

@@ -1359,6 +1359,8 @@ __global__ void __launch_bounds__(256) k_nat_dx32(const float* __restrict__ dl3,
 
 // the policy / value head of B states (one wave each) on the 512-wide fc output, + the action
 // draw and fused env act when sel.mode >= 0 (agent.py:59-62, network.py:72)
+// (GAME: the device env's game of the fused act, A3C_GAME_*)
+template <int GAME = A3C_GAME_SYNTH>
 __global__ void __launch_bounds__(256) k_nat_head(const float* __restrict__ l4, int64_t B, const float* __restrict__ Wp,
                                                   const float* __restrict__ bp, const float* __restrict__ Wv,
                                                   const float* __restrict__ bv, int A, int zs, float* __restrict__ z,
@@ -1368,11 +1370,13 @@ __global__ void __launch_bounds__(256) k_nat_head(const float* __restrict__ l4, 
   if (b >= B) return;
   const float myz = head_row<NoMid, NT_FC>(l4, b, Wp, bp, Wv, bv, A, lane);
   if (lane < zs) z[b * zs + lane] = myz;
-  if (sel.mode >= 0) (void)head_act(myz, lane, A, sel, b);
+  if (sel.mode >= 0) (void)head_act<GAME>(myz, lane, A, sel, b);
   // the overlap rollout's bootstrap head (its last kernel) advances tau (no tau read here)
   if (sel.adv_ptr && blockIdx.x == 0 && threadIdx.x == 0) *sel.adv_ptr += sel.adv_n;
 }
 
+static int nat_head_catch_launch(const NetLayout& L, const float* P, const float* l4, int64_t B, float* z,
+                                 const HeadSelect& sel, hipStream_t s);
 // ---------------------------------------------------------------------------------------
 // passes (one launch each, timed individually by a3c_engine_time_kernel)
 // ---------------------------------------------------------------------------------------
@@ -1708,7 +1712,9 @@ int a3c_nat_forward_launch(const NetLayout& L, const float* P, const StateAddr& 
   if (step_tail)   // head + act + Environment.screen
     return a3c_head_screen_wide_launch(l4, P + L.off[N_HW], P + L.off[N_HB], P + L.off[N_VW], P + L.off[N_VB], L.A,
                                        L.zs, B, z, sel, s);
-  hipLaunchKernelGGL(k_nat_head, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, s, l4, B, P + L.off[N_HW],
+  if (sel.mode >= 0 && sel.env_on && sel.envp.game == A3C_GAME_CATCH)   // (the Catch form: end of this file)
+    return nat_head_catch_launch(L, P, l4, B, z, sel, s);
+  hipLaunchKernelGGL(k_nat_head<>, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, s, l4, B, P + L.off[N_HW],
                      P + L.off[N_HB], P + L.off[N_VW], P + L.off[N_VB], L.A, L.zs, z, sel);
   A3C_CHECK(hipGetLastError());
   return 0;
@@ -1904,4 +1910,14 @@ extern "C" int a3c_nature_loss_backward(const a3c_net_desc* net, const float* pa
   return a3c_nat_backward_launch(L, params, nat_states(states, B), B, l1, l2, l3, l4, z, actions, target, beta,
                                  literal_adv, grads, loss_out, nat_align(workspace), (hipStream_t)stream, nullptr,
                                  nullptr, nullptr);
+}
+
+// Catch: k_nat_head's A3C_GAME_CATCH instantiation, emitted behind every other kernel
+// of this file
+static int nat_head_catch_launch(const NetLayout& L, const float* P, const float* l4, int64_t B, float* z,
+                                 const HeadSelect& sel, hipStream_t s) {
+  hipLaunchKernelGGL(k_nat_head<A3C_GAME_CATCH>, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, s, l4, B, P + L.off[N_HW],
+                     P + L.off[N_HB], P + L.off[N_VW], P + L.off[N_VB], L.A, L.zs, z, sel);
+  A3C_CHECK(hipGetLastError());
+  return 0;
 }

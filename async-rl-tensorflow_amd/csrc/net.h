@@ -95,6 +95,7 @@ inline int a3c_make_layout(const a3c_net_desc* d, NetLayout* L) {
 struct EnvParams {
   uint32_t k0, k1;
   int P, A, L0, random_start, action_repeat, env_id_base;
+  int game;                 // A3C_GAME_*: picks the kernels' instantiation on the host (never read on device)
 };
 
 struct EnvBufs {

@@ -462,6 +462,8 @@ __global__ void __launch_bounds__(512) k_conv12_fwd(StateAddr sa, int64_t B,
 }
 
 // head: one wave per state.  z[b][j] = h3[b] . W[:,j] + bias[j]
+// (GAME: the device env's game of the fused act, A3C_GAME_*)
+template <int GAME = A3C_GAME_SYNTH>
 __global__ void __launch_bounds__(256) k_head_fwd(const float* __restrict__ h3, int64_t B,
                                                   const float* __restrict__ Wp, const float* __restrict__ bp,
                                                   const float* __restrict__ Wv, const float* __restrict__ bv,
@@ -491,7 +493,7 @@ __global__ void __launch_bounds__(256) k_head_fwd(const float* __restrict__ h3, 
     myz = head_row(h3, b, Wp, bp, Wv, bv, A, lane);
   }
   if (lane < zs) z[b * zs + lane] = myz;   // padding columns are 0
-  if (sel.mode >= 0) (void)head_act(myz, lane, A, sel, b);
+  if (sel.mode >= 0) (void)head_act<GAME>(myz, lane, A, sel, b);
   if (sel.adv_ptr && blockIdx.x == 0 && threadIdx.x == 0) *sel.adv_ptr += sel.adv_n;   // (reads no tau)
 }
 
@@ -505,7 +507,11 @@ __global__ void __launch_bounds__(256) k_head_fwd(const float* __restrict__ h3, 
 // to both parity copies, so an env that is frozen afterwards needs no copy across the (tau & 1)
 // double buffer.  frozen[e] != 0: env e is done or has no episode in this wave -- nothing of it is
 // touched and -1 is returned (the whole workgroup, before any barrier).
-template <int W = FC, bool PLAY = false>
+// GAME = A3C_GAME_CATCH: wave 1 runs the part of the act that does not depend on the
+// action (catch_act_pre: ball row, landing, terminal, and the new game on a terminal); the paddle
+// move, the reward and the frame index (catch_act_post) follow the barrier that publishes s_act,
+// so the reward stores move behind it.  frame_salt and A3C_ABL_FRAME do not apply.
+template <int W = FC, bool PLAY = false, int GAME = A3C_GAME_SYNTH>
 __device__ inline int32_t head_act_env(const float* __restrict__ h3, const float* __restrict__ Wp,
                                        const float* __restrict__ bp, const float* __restrict__ Wv,
                                        const float* __restrict__ bv, int A, int zs, float* __restrict__ z,
@@ -548,9 +554,14 @@ __device__ inline int32_t head_act_env(const float* __restrict__ h3, const float
     const int64_t cur = (tau & 1) * (int64_t)sel.par_E + e;
     const uint32_t id = (uint32_t)(sel.env_id_base + e);
     EnvState s = env_load(sel.envb, cur);
-    const uint32_t draw = env_act_pre(s, sel.envp, id, !PLAY);
-    if constexpr (!PLAY) sel.rewards[e] = fmaxf(-1.0f, fminf(1.0f, s.reward));   // observe clip, agent.py:154
-    if (sel.rewards_raw) sel.rewards_raw[e] = s.reward;
+    uint32_t draw;
+    if constexpr (GAME == A3C_GAME_CATCH) {
+      draw = catch_act_pre(s, sel.envp.action_repeat);         // (the rewards: behind the barrier)
+    } else {
+      draw = env_act_pre(s, sel.envp, id, !PLAY);
+      if constexpr (!PLAY) sel.rewards[e] = fmaxf(-1.0f, fminf(1.0f, s.reward));   // observe clip, agent.py:154
+      if (sel.rewards_raw) sel.rewards_raw[e] = s.reward;
+    }
     sel.terms[e] = (uint8_t)s.terminal;
     s_draw = draw;
     if constexpr (PLAY) {
@@ -560,7 +571,7 @@ __device__ inline int32_t head_act_env(const float* __restrict__ h3, const float
     } else {
       s_term = s.terminal;
       if (s.terminal) {
-        env_new_random_game(s, sel.envp, id);                  // agent.py:66-67
+        game_new_random_game<GAME>(s, sel.envp, id);           // agent.py:66-67
         env_store(sel.envb, nxt, s);
       } else {
         env_store(sel.envb, nxt, s, false);                    // frame: after the action draw
@@ -571,11 +582,21 @@ __device__ inline int32_t head_act_env(const float* __restrict__ h3, const float
   __syncthreads();
   int32_t frame;
   if (sel.env_on) {
-    frame = env_frame_of(s_draw + sel.frame_salt, (uint32_t)s_act, sel.envp);
+    float reward = 0.f;
+    if constexpr (GAME == A3C_GAME_CATCH) {
+      frame = catch_act_post(s_draw, (uint32_t)s_act, reward);   // < CATCH_FRAMES <= the pool's frames
+    } else {
+      frame = env_frame_of(s_draw + sel.frame_salt, (uint32_t)s_act, sel.envp);
 #ifdef A3C_ABL_FRAME
-    frame = e & 63;   // measurement only: every step reads from 64 L2-resident frames
+      frame = e & 63;   // measurement only: every step reads from 64 L2-resident frames
 #endif
+    }
     if (threadIdx.x == 0) {
+      if constexpr (GAME == A3C_GAME_CATCH) {
+        if constexpr (!PLAY) sel.rewards[e] = reward;            // in {-1, 0, 1}: the observe clip changes nothing
+        if (sel.rewards_raw) sel.rewards_raw[e] = reward;
+        if constexpr (PLAY) sel.envb.reward[nxt] = sel.envb.reward[(tau & 1) * (int64_t)sel.par_E + e] = reward;
+      }
       sel.frames_out[e] = frame;
       if (!s_term) sel.envb.frame[nxt] = frame;
       if constexpr (PLAY) sel.envb.frame[(tau & 1) * (int64_t)sel.par_E + e] = frame;
@@ -590,7 +611,7 @@ __device__ inline int32_t head_act_env(const float* __restrict__ h3, const float
 // head + action draw + env act (head_act_env), then the whole workgroup computes
 // Environment.screen (environment.py:49-53, bit-exact) of the post-act frame straight from the
 // HBM pool into the env's frame-ring slot
-template <int HS_THREADS, int W = FC>
+template <int HS_THREADS, int W = FC, int GAME = A3C_GAME_SYNTH>
 __global__ void __launch_bounds__(HS_THREADS) k_head_screen(const float* __restrict__ h3,
                                                             const float* __restrict__ Wp,
                                                             const float* __restrict__ bp,
@@ -606,7 +627,7 @@ __global__ void __launch_bounds__(HS_THREADS) k_head_screen(const float* __restr
   dbg = blockIdx.x == HS_TIMES ? (uint64_t*)z : nullptr;
   if (dbg && threadIdx.x == 0) dbg[0] = __builtin_readcyclecounter();
 #endif
-  const int32_t frame = head_act_env<W>(h3, Wp, bp, Wv, bv, A, zs, z, sel, b, tau, dbg);
+  const int32_t frame = head_act_env<W, false, GAME>(h3, Wp, bp, Wv, bv, A, zs, z, sel, b, tau, dbg);
   uint8_t* slot = sel.ring + b * sel.R * PLANE + ((tau + 1) % sel.R) * PLANE;
   if (sel.frame84)
     atari::copy_frame84<HS_THREADS>(sel.pool + (int64_t)frame * PLANE, slot);
@@ -618,7 +639,7 @@ __global__ void __launch_bounds__(HS_THREADS) k_head_screen(const float* __restr
 // The play form of k_head_screen (a3c_engine_play): one step of Agent.play's loop for env b
 // (agent.py:371-377: predict with the fixed test epsilon, act with is_training = false, history
 // add) -- or nothing at all when the env is frozen.
-template <int HS_THREADS, int W>
+template <int HS_THREADS, int W, int GAME = A3C_GAME_SYNTH>
 __global__ void __launch_bounds__(HS_THREADS) k_head_screen_play(const float* __restrict__ h3,
                                                                  const float* __restrict__ Wp,
                                                                  const float* __restrict__ bp,
@@ -629,7 +650,7 @@ __global__ void __launch_bounds__(HS_THREADS) k_head_screen_play(const float* __
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const int64_t b = blockIdx.x;
   const int64_t tau = *sel.tau_ptr + sel.tau_add;
-  const int32_t frame = head_act_env<W, true>(h3, Wp, bp, Wv, bv, A, zs, z, sel, b, tau, nullptr, nullptr, frozen);
+  const int32_t frame = head_act_env<W, true, GAME>(h3, Wp, bp, Wv, bv, A, zs, z, sel, b, tau, nullptr, nullptr, frozen);
   if (frame < 0) return;
   uint8_t* slot = sel.ring + b * sel.R * PLANE + ((tau + 1) % sel.R) * PLANE;
   if (sel.frame84)
@@ -658,7 +679,7 @@ static_assert(HSC_KV_OFF % 16 == 0 && HSC_KV_OFF + SCREEN_KV_BYTES <= HSC_X8_BYT
 static_assert(HSC_SMEM + 16 + 4096 <= 160 * 1024 - 82944, "rollout workgroup beside a compact conv backward one");
 // waves_per_eu(4) caps it at 128 VGPRs: with the concurrent k_conv_bwd<false,4> (254 VGPRs,
 // one wave per SIMD) two of its waves per SIMD must fit in the remaining 258
-template <bool SAVE_L1, bool L2M>
+template <bool SAVE_L1, bool L2M, int GAME = A3C_GAME_SYNTH>
 __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) k_head_screen_conv12(const float* __restrict__ h3,
                                                             const float* __restrict__ Wp,
                                                             const float* __restrict__ bp,
@@ -743,7 +764,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) k
     }
     hrow = (const float*)fl;
   }
-  const int32_t frame = head_act_env(h3, Wp, bp, Wv, bv, A, zs, z, sel, b, tau, dbg, hrow);
+  const int32_t frame = head_act_env<FC, false, GAME>(h3, Wp, bp, Wv, bv, A, zs, z, sel, b, tau, dbg, hrow);
   uint16_t* xold = (uint16_t*)smem;                      // planes 0..2, bf16
   uint4* wlds = (uint4*)x8;
   if (pt >= 0) {
@@ -820,7 +841,7 @@ int a3c_fc_fwd_launch(const float* A, const float* W, const float* bias, float* 
 // env b's row of the nsplit K-slice partials (slice order, + bias, ReLU: k_reduce_slabs' order, so
 // the row is bit-identical to the separate fold), keeps it in LDS for the head and writes it out for
 // the backward -- one launch per step fewer
-template <int HS_THREADS, int W>
+template <int HS_THREADS, int W, int GAME = A3C_GAME_SYNTH>
 __global__ void __launch_bounds__(HS_THREADS) k_head_screen_fold(const float* __restrict__ part, int nsplit,
                                                                  int64_t pstride, const float* __restrict__ fbias,
                                                                  float* __restrict__ hout,
@@ -839,7 +860,7 @@ __global__ void __launch_bounds__(HS_THREADS) k_head_screen_fold(const float* __
     hout[b * W + i] = v;
   }
   __syncthreads();
-  const int32_t frame = head_act_env<W>(nullptr, Wp, bp, Wv, bv, A, zs, z, sel, b, tau, nullptr, hrow);
+  const int32_t frame = head_act_env<W, false, GAME>(nullptr, Wp, bp, Wv, bv, A, zs, z, sel, b, tau, nullptr, hrow);
   uint8_t* slot = sel.ring + b * sel.R * PLANE + ((tau + 1) % sel.R) * PLANE;
   if (sel.frame84)
     atari::copy_frame84<HS_THREADS>(sel.pool + (int64_t)frame * PLANE, slot);
@@ -847,12 +868,31 @@ __global__ void __launch_bounds__(HS_THREADS) k_head_screen_fold(const float* __
     atari::screen_frame<HS_THREADS>(sel.pool + (int64_t)frame * (atari::IH * atari::IW * 3), slot, smem, nullptr);
 }
 
+// The Catch instantiations (GAME = A3C_GAME_CATCH) of the kernels that step a device env, and their
+// launches, are at the end of this file, behind every default-game kernel.
+static bool catch_on(const HeadSelect& sel) { return sel.env_on && sel.envp.game == A3C_GAME_CATCH; }
+static int catch_fold_launch(const float* part, int nsplit, const float* fbias, float* l4, const float* Wp,
+                             const float* bp, const float* Wv, const float* bv, int A, int zs, int64_t B, float* z,
+                             const HeadSelect& sel, int nt, hipStream_t s);
+static int catch_head_screen_launch(int W, const float* h, const float* Wp, const float* bp, const float* Wv,
+                                    const float* bv, int A, int zs, int64_t B, float* z, const HeadSelect& sel, int nt,
+                                    hipStream_t s);
+static int catch_play_launch(int W, const float* h, const float* Wp, const float* bp, const float* Wv, const float* bv,
+                             int A, int zs, int64_t B, float* z, const HeadSelect& sel, const uint8_t* frozen, int nt,
+                             hipStream_t s);
+static int catch_conv12_launch(const float* h, const float* Wp, const float* bp, const float* Wv, const float* bv, int A,
+                               int zs, int64_t B, float* z, const HeadSelect& sel, const Conv12Next& nx, hipStream_t s);
+static int catch_head_fwd_launch(const float* h, const float* Wp, const float* bp, const float* Wv, const float* bv, int A,
+                                 int zs, int64_t B, float* z, const HeadSelect& sel, hipStream_t s);
+static void catch_set_smem();
+
 int a3c_head_screen_fold_launch(const float* part, int nsplit, const float* fbias, float* l4, const float* Wp,
                                 const float* bp, const float* Wv, const float* bv, int A, int zs, int64_t B, float* z,
                                 const HeadSelect& sel, hipStream_t s) {
   static const int env_t = (int)A3C_AB_KNOB("A3C_HS_THREADS", 0);
   const int nt = env_t ? env_t : (a3c_shared_gpu() ? 512 : 1024);
   const int64_t ps = B * 512;
+  if (catch_on(sel)) return catch_fold_launch(part, nsplit, fbias, l4, Wp, bp, Wv, bv, A, zs, B, z, sel, nt, s);
   if (nt == 1024)
     hipLaunchKernelGGL((k_head_screen_fold<1024, 512>), dim3((unsigned)B), dim3(1024), SCREEN_FRAME_SMEM, s, part,
                        nsplit, ps, fbias, l4, Wp, bp, Wv, bv, A, zs, z, sel);
@@ -868,6 +908,7 @@ int a3c_head_screen_wide_launch(const float* l4, const float* Wp, const float* b
                                 int A, int zs, int64_t B, float* z, const HeadSelect& sel, hipStream_t s) {
   static const int env_t = (int)A3C_AB_KNOB("A3C_HS_THREADS", 0);
   const int nt = env_t ? env_t : (a3c_shared_gpu() ? 512 : 1024);
+  if (catch_on(sel)) return catch_head_screen_launch(512, l4, Wp, bp, Wv, bv, A, zs, B, z, sel, nt, s);
   if (nt == 1024)
     hipLaunchKernelGGL((k_head_screen<1024, 512>), dim3((unsigned)B), dim3(1024), SCREEN_FRAME_SMEM, s, l4, Wp, bp,
                        Wv, bv, A, zs, z, sel);
@@ -886,6 +927,7 @@ int a3c_head_screen_play_launch(int W, const float* h, const float* Wp, const fl
       !sel.frames_out || !sel.actions || sel.mode < 0 || sel.par_E < B || (W != FC && W != 512))
     return a3c_set_error(A3C_ERR_INVALID, "a3c_head_screen_play", "bad argument");
   const int nt = a3c_shared_gpu() ? 512 : 1024;
+  if (catch_on(sel)) return catch_play_launch(W, h, Wp, bp, Wv, bv, A, zs, B, z, sel, frozen, nt, s);
 #define HSP_GO(T, WW) hipLaunchKernelGGL((k_head_screen_play<T, WW>), dim3((unsigned)B), dim3(T), SCREEN_FRAME_SMEM, s, h, \
                                          Wp, bp, Wv, bv, A, zs, z, sel, frozen)
   if (W == FC) {
@@ -965,7 +1007,9 @@ int a3c_forward_launch(const NetLayout& L, const float* params, const uint8_t* p
       hs.fc_bias = P + L.off[T_FCB];
       hs.l3_out = act_l3;
     }
-    hipLaunchKernelGGL(k_head_fwd, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, s, head_in, B,
+    if (hs.mode >= 0 && catch_on(hs))
+      return catch_head_fwd_launch(head_in, P + L.off[T_HW], P + L.off[T_HB], Wv, bv, L.A, L.zs, B, z, hs, s);
+    hipLaunchKernelGGL(k_head_fwd<>, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, s, head_in, B,
                        P + L.off[T_HW], P + L.off[T_HB], Wv, bv, L.A, L.zs, z, hs);
   }
   A3C_CHECK(hipGetLastError());
@@ -980,6 +1024,8 @@ int a3c_head_screen_launch(const NetLayout& L, const float* P, const float* act_
   // 1024 threads when the step owns the GPU; 512 leave room for the concurrent backward
   static const int env_t = (int)A3C_AB_KNOB("A3C_HS_THREADS", 0);
   const int nt = env_t ? env_t : (a3c_shared_gpu() ? 512 : 1024);
+  if (catch_on(sel))
+    return catch_head_screen_launch(FC, act_l3, P + L.off[T_HW], P + L.off[T_HB], Wv, bv, L.A, L.zs, B, z, sel, nt, s);
   if (nt == 1024)
     hipLaunchKernelGGL(k_head_screen<1024>, dim3((unsigned)B), dim3(1024), SCREEN_FRAME_SMEM, s, act_l3,
                        P + L.off[T_HW], P + L.off[T_HB], Wv, bv, L.A, L.zs, z, sel);
@@ -996,6 +1042,8 @@ int a3c_head_screen_conv12_launch(const NetLayout& L, const float* P, const floa
   const float* bv = L.algo == A3C_ALGO_A3C ? P + L.off[T_VB] : nullptr;
   if (!nx.sa.tau_ptr || !sel.tau_ptr)
     return a3c_set_error(A3C_ERR_INVALID, "a3c_head_screen_conv12", "device tau counters required");
+  if (catch_on(sel))
+    return catch_conv12_launch(act_l3, P + L.off[T_HW], P + L.off[T_HB], Wv, bv, L.A, L.zs, B, z, sel, nx, s);
 #define HSC_GO(S, M) hipLaunchKernelGGL((k_head_screen_conv12<S, M>), dim3((unsigned)B), dim3(512), HSC_SMEM, s, act_l3, \
                                         P + L.off[T_HW], P + L.off[T_HB], Wv, bv, L.A, L.zs, z, sel, nx)
   if (nx.act_l1 && nx.l2m) HSC_GO(true, true);
@@ -1077,6 +1125,7 @@ void a3c_conv12_set_smem() {
                             SCREEN_FRAME_SMEM);
   (void)hipFuncSetAttribute((const void*)k_head_screen_play<1024, 512>, hipFuncAttributeMaxDynamicSharedMemorySize,
                             SCREEN_FRAME_SMEM);
+  catch_set_smem();
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1453,7 +1502,7 @@ int a3c_head_fold_launch(const NetLayout& L, const float* P, const float* fc_par
   hs.fc_bias = P + L.off[T_FCB];
   const float* Wv = L.algo == A3C_ALGO_A3C ? P + L.off[T_VW] : nullptr;
   const float* bv = L.algo == A3C_ALGO_A3C ? P + L.off[T_VB] : nullptr;
-  hipLaunchKernelGGL(k_head_fwd, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, s, nullptr, B, P + L.off[T_HW],
+  hipLaunchKernelGGL(k_head_fwd<>, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, s, nullptr, B, P + L.off[T_HW],
                      P + L.off[T_HB], Wv, bv, L.A, L.zs, z, hs);
   A3C_CHECK(hipGetLastError());
   return 0;
@@ -1552,3 +1601,98 @@ int a3c_fc_fwd_launch(const float* A, const float* W, const float* bias, float* 
 #ifdef A3C_WGLOG
 WGLOG_BIND(a3c_wglog_bind_fwd)
 #endif
+
+// ---------------------------------------------------------------------------------------
+// Catch (A3C_GAME_CATCH): the GAME = A3C_GAME_CATCH instantiations of the kernels that
+// step a device env, emitted here -- behind every default-game kernel of this file, which keep
+// their instructions and their place in the code object -- and their launches (the grids, block
+// sizes and LDS of the default-game launches above; nt: the 512 / 1024 threads they chose).
+// ---------------------------------------------------------------------------------------
+#define CG A3C_GAME_CATCH
+static int catch_fold_launch(const float* part, int nsplit, const float* fbias, float* l4, const float* Wp,
+                             const float* bp, const float* Wv, const float* bv, int A, int zs, int64_t B, float* z,
+                             const HeadSelect& sel, int nt, hipStream_t s) {
+  const int64_t ps = B * 512;
+  if (nt == 1024)
+    hipLaunchKernelGGL((k_head_screen_fold<1024, 512, CG>), dim3((unsigned)B), dim3(1024), SCREEN_FRAME_SMEM, s, part,
+                       nsplit, ps, fbias, l4, Wp, bp, Wv, bv, A, zs, z, sel);
+  else
+    hipLaunchKernelGGL((k_head_screen_fold<512, 512, CG>), dim3((unsigned)B), dim3(512), SCREEN_FRAME_SMEM, s, part,
+                       nsplit, ps, fbias, l4, Wp, bp, Wv, bv, A, zs, z, sel);
+  A3C_CHECK(hipGetLastError());
+  return 0;
+}
+
+static int catch_head_screen_launch(int W, const float* h, const float* Wp, const float* bp, const float* Wv,
+                                    const float* bv, int A, int zs, int64_t B, float* z, const HeadSelect& sel, int nt,
+                                    hipStream_t s) {
+#define CHS_GO(T, WW) hipLaunchKernelGGL((k_head_screen<T, WW, CG>), dim3((unsigned)B), dim3(T), SCREEN_FRAME_SMEM, s, h, \
+                                         Wp, bp, Wv, bv, A, zs, z, sel)
+  if (W == FC) {
+    if (nt == 1024) CHS_GO(1024, FC);
+    else CHS_GO(512, FC);
+  } else {
+    if (nt == 1024) CHS_GO(1024, 512);
+    else CHS_GO(512, 512);
+  }
+#undef CHS_GO
+  A3C_CHECK(hipGetLastError());
+  return 0;
+}
+
+static int catch_play_launch(int W, const float* h, const float* Wp, const float* bp, const float* Wv, const float* bv,
+                             int A, int zs, int64_t B, float* z, const HeadSelect& sel, const uint8_t* frozen, int nt,
+                             hipStream_t s) {
+#define CHP_GO(T, WW) hipLaunchKernelGGL((k_head_screen_play<T, WW, CG>), dim3((unsigned)B), dim3(T), SCREEN_FRAME_SMEM, \
+                                         s, h, Wp, bp, Wv, bv, A, zs, z, sel, frozen)
+  if (W == FC) {
+    if (nt == 1024) CHP_GO(1024, FC);
+    else CHP_GO(512, FC);
+  } else {
+    if (nt == 1024) CHP_GO(1024, 512);
+    else CHP_GO(512, 512);
+  }
+#undef CHP_GO
+  A3C_CHECK(hipGetLastError());
+  return 0;
+}
+
+static int catch_conv12_launch(const float* h, const float* Wp, const float* bp, const float* Wv, const float* bv, int A,
+                               int zs, int64_t B, float* z, const HeadSelect& sel, const Conv12Next& nx, hipStream_t s) {
+#define CHC_GO(S, M) hipLaunchKernelGGL((k_head_screen_conv12<S, M, CG>), dim3((unsigned)B), dim3(512), HSC_SMEM, s, h, \
+                                        Wp, bp, Wv, bv, A, zs, z, sel, nx)
+  if (nx.act_l1 && nx.l2m) CHC_GO(true, true);
+  else if (nx.act_l1) CHC_GO(true, false);
+  else if (nx.l2m) CHC_GO(false, true);
+  else CHC_GO(false, false);
+#undef CHC_GO
+  A3C_CHECK(hipGetLastError());
+  return 0;
+}
+
+static int catch_head_fwd_launch(const float* h, const float* Wp, const float* bp, const float* Wv, const float* bv, int A,
+                                 int zs, int64_t B, float* z, const HeadSelect& sel, hipStream_t s) {
+  hipLaunchKernelGGL(k_head_fwd<CG>, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, s, h, B, Wp, bp, Wv, bv, A, zs, z, sel);
+  A3C_CHECK(hipGetLastError());
+  return 0;
+}
+
+static void catch_set_smem() {
+#define CSM(K, BYTES) (void)hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, BYTES)
+  CSM((k_head_screen_conv12<true, true, CG>), HSC_SMEM);
+  CSM((k_head_screen_conv12<true, false, CG>), HSC_SMEM);
+  CSM((k_head_screen_conv12<false, true, CG>), HSC_SMEM);
+  CSM((k_head_screen_conv12<false, false, CG>), HSC_SMEM);
+  CSM((k_head_screen<512, FC, CG>), SCREEN_FRAME_SMEM);
+  CSM((k_head_screen<1024, FC, CG>), SCREEN_FRAME_SMEM);
+  CSM((k_head_screen<512, 512, CG>), SCREEN_FRAME_SMEM);
+  CSM((k_head_screen<1024, 512, CG>), SCREEN_FRAME_SMEM);
+  CSM((k_head_screen_fold<512, 512, CG>), SCREEN_FRAME_SMEM);
+  CSM((k_head_screen_fold<1024, 512, CG>), SCREEN_FRAME_SMEM);
+  CSM((k_head_screen_play<512, FC, CG>), SCREEN_FRAME_SMEM);
+  CSM((k_head_screen_play<1024, FC, CG>), SCREEN_FRAME_SMEM);
+  CSM((k_head_screen_play<512, 512, CG>), SCREEN_FRAME_SMEM);
+  CSM((k_head_screen_play<1024, 512, CG>), SCREEN_FRAME_SMEM);
+#undef CSM
+}
+#undef CG

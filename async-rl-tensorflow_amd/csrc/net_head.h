@@ -192,6 +192,8 @@ __device__ inline float head_row(const float* __restrict__ h3, int64_t b, const 
 
 // action draw for row b (all lanes) and, in lane 0, the fused env act (agent.py:59-62).
 // Returns the post-act frame index in lane 0 when the env is stepped, else -1.
+// GAME: the device env's game (A3C_GAME_*), picked at compile time.
+template <int GAME = A3C_GAME_SYNTH>
 __device__ inline int32_t head_act(float myz, int lane, int A, const HeadSelect& sel, int64_t b) {
   int32_t frame = -1;
   const int32_t a = select_from_lanes(myz, lane, A, sel, b);
@@ -203,13 +205,13 @@ __device__ inline int32_t head_act(float myz, int lane, int A, const HeadSelect&
       const int64_t cur = (tau & 1) * (int64_t)sel.par_E + e, nxt = ((tau + 1) & 1) * (int64_t)sel.par_E + e;
       const uint32_t id = (uint32_t)(sel.env_id_base + e);
       EnvState s = env_load(sel.envb, cur);
-      env_act(s, sel.envp, id, (uint32_t)a, true);
+      game_act<GAME>(s, sel.envp, id, (uint32_t)a, true);
       sel.rewards[e] = fmaxf(-1.0f, fminf(1.0f, s.reward));   // observe clip, agent.py:154
       if (sel.rewards_raw) sel.rewards_raw[e] = s.reward;
       sel.terms[e] = (uint8_t)s.terminal;
       sel.frames_out[e] = s.frame;
       frame = s.frame;
-      if (s.terminal) env_new_random_game(s, sel.envp, id);    // agent.py:66-67
+      if (s.terminal) game_new_random_game<GAME>(s, sel.envp, id);    // agent.py:66-67
       env_store(sel.envb, nxt, s);
     }
   }

@@ -1,11 +1,13 @@
-// Standalone batched synthetic env (C-ABI a3c_env_*): the reference's Environment /
+// Standalone batched device env (C-ABI a3c_env_*): the reference's Environment /
 // GymEnvironment interface (environment.py:14-106) for E envs on device, used by the Python
 // mirror src/environment.py.  Dynamics are env_dev.h (bit-identical to oracle/synthetic_env.py);
-// screens go through the Atari Environment.screen kernel.
+// screens go through the Atari Environment.screen kernel.  a3c_env_create_ex picks the game: the
+// synthetic stand-in or Catch (env_dev.h), whose pool is rendered, not hashed.
 #include <new>
 #include "env_dev.h"
 
 int a3c_pool_fill_launch(uint8_t* pool, int P, uint32_t k0, uint32_t k1, hipStream_t s, int frame_bytes);
+int a3c_pool_render_catch_launch(uint8_t* pool, int P, hipStream_t s);
 int a3c_launch_screen_atari(const uint8_t* rgb, const int32_t* idx, int64_t n, uint8_t* out, int64_t stride,
                             hipStream_t s);
 
@@ -25,21 +27,20 @@ __global__ void k_venv_zero(EnvBufs b, int E) {
 }
 
 // op 0: new_game (environment.py:28-33), 1: new_random_game (:35-40)
+// (GAME: A3C_GAME_*, picked at compile time)
+template <int GAME>
 __global__ void k_venv_new(EnvParams p, EnvBufs b, int E, const uint8_t* __restrict__ mask, int random) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= E || (mask && !mask[e])) return;
   const uint32_t id = (uint32_t)(p.env_id_base + e);
   EnvState s = env_load(b, e);
-  if (random) {
-    env_new_random_game(s, p, id);
-  } else {
-    if (s.lives == 0) env_reset(s, p, id);
-    env_step_raw(s, p, id, 0u);
-  }
+  if (random) game_new_random_game<GAME>(s, p, id);
+  else game_new_game<GAME>(s, p, id);
   env_store(b, e, s);
 }
 
 // GymEnvironment.act (environment.py:78-96) / SimpleGymEnvironment.act (:102-106 with simple=1)
+template <int GAME>
 __global__ void k_venv_act(EnvParams p, EnvBufs b, int E, const int32_t* __restrict__ actions, int training,
                            int simple, float* __restrict__ rewards, uint8_t* __restrict__ terms,
                            int32_t* __restrict__ frames) {
@@ -47,8 +48,12 @@ __global__ void k_venv_act(EnvParams p, EnvBufs b, int E, const int32_t* __restr
   if (e >= E) return;
   const uint32_t id = (uint32_t)(p.env_id_base + e);
   EnvState s = env_load(b, e);
-  if (simple) env_step_raw(s, p, id, (uint32_t)actions[e]);
-  else env_act(s, p, id, (uint32_t)actions[e], training != 0);
+  if constexpr (GAME == A3C_GAME_CATCH) {
+    catch_act(s, simple ? 1 : p.action_repeat, (uint32_t)actions[e]);
+  } else {
+    if (simple) env_step_raw(s, p, id, (uint32_t)actions[e]);
+    else env_act(s, p, id, (uint32_t)actions[e], training != 0);
+  }
   env_store(b, e, s);
   if (rewards) rewards[e] = s.reward;
   if (terms) terms[e] = (uint8_t)s.terminal;
@@ -57,9 +62,17 @@ __global__ void k_venv_act(EnvParams p, EnvBufs b, int E, const int32_t* __restr
 
 extern "C" int a3c_env_create(int num_envs, int action_size, int start_lives, int random_start, int action_repeat,
                               int num_frames, uint64_t seed, int env_id_base, a3c_env** out) {
+  return a3c_env_create_ex(num_envs, action_size, start_lives, random_start, action_repeat, num_frames, seed,
+                           env_id_base, A3C_GAME_SYNTH, out);
+}
+
+extern "C" int a3c_env_create_ex(int num_envs, int action_size, int start_lives, int random_start, int action_repeat,
+                                 int num_frames, uint64_t seed, int env_id_base, int game, a3c_env** out) {
   if (!out || num_envs < 1 || action_size < 1 || random_start < 1 || action_repeat < 1 || num_frames < 1 ||
-      start_lives < 0)
+      start_lives < 0 || (game != A3C_GAME_SYNTH && game != A3C_GAME_CATCH))
     return a3c_set_error(A3C_ERR_INVALID, "a3c_env_create", "bad argument");
+  if (game == A3C_GAME_CATCH && (num_frames < CATCH_FRAMES || action_size != 3 || start_lives != 0))
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_env_create", "Catch needs num_frames >= 640, action_size 3, start_lives 0");
   a3c_env* v = new (std::nothrow) a3c_env();
   if (!v) return a3c_set_error(A3C_ERR_INVALID, "a3c_env_create", "oom");
   const int64_t E = num_envs;
@@ -87,7 +100,10 @@ extern "C" int a3c_env_create(int num_envs, int action_size, int start_lives, in
   v->p.random_start = random_start;
   v->p.action_repeat = action_repeat;
   v->p.env_id_base = env_id_base;
-  int rc = a3c_pool_fill_launch(v->pool, num_frames, v->p.k0, v->p.k1, nullptr, SCREEN_H * SCREEN_W * 3);
+  v->p.game = game;
+  int rc = game == A3C_GAME_CATCH
+               ? a3c_pool_render_catch_launch(v->pool, num_frames, nullptr)
+               : a3c_pool_fill_launch(v->pool, num_frames, v->p.k0, v->p.k1, nullptr, SCREEN_H * SCREEN_W * 3);
   if (!rc) {
     hipLaunchKernelGGL(k_venv_zero, dim3((num_envs + 63) / 64), dim3(64), 0, nullptr, v->b, num_envs);
     if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess)
@@ -111,8 +127,12 @@ extern "C" int a3c_env_destroy(a3c_env* v) {
 
 extern "C" int a3c_env_new_game(a3c_env* v, const uint8_t* mask, int random, void* stream) {
   if (!v) return a3c_set_error(A3C_ERR_INVALID, "a3c_env_new_game", "null");
-  hipLaunchKernelGGL(k_venv_new, dim3((v->E + 63) / 64), dim3(64), 0, (hipStream_t)stream, v->p, v->b, v->E, mask,
-                     random);
+  if (v->p.game != A3C_GAME_CATCH)
+    hipLaunchKernelGGL(k_venv_new<A3C_GAME_SYNTH>, dim3((v->E + 63) / 64), dim3(64), 0, (hipStream_t)stream, v->p, v->b,
+                       v->E, mask, random);
+  else
+    hipLaunchKernelGGL(k_venv_new<A3C_GAME_CATCH>, dim3((v->E + 63) / 64), dim3(64), 0, (hipStream_t)stream, v->p, v->b,
+                       v->E, mask, random);
   A3C_CHECK(hipGetLastError());
   return 0;
 }
@@ -120,8 +140,12 @@ extern "C" int a3c_env_new_game(a3c_env* v, const uint8_t* mask, int random, voi
 extern "C" int a3c_env_act(a3c_env* v, const int32_t* actions, int is_training, int simple, float* rewards,
                            uint8_t* terminals, int32_t* frames, void* stream) {
   if (!v || !actions) return a3c_set_error(A3C_ERR_INVALID, "a3c_env_act", "null");
-  hipLaunchKernelGGL(k_venv_act, dim3((v->E + 63) / 64), dim3(64), 0, (hipStream_t)stream, v->p, v->b, v->E, actions,
-                     is_training, simple, rewards, terminals, frames);
+  if (v->p.game != A3C_GAME_CATCH)
+    hipLaunchKernelGGL(k_venv_act<A3C_GAME_SYNTH>, dim3((v->E + 63) / 64), dim3(64), 0, (hipStream_t)stream, v->p, v->b,
+                       v->E, actions, is_training, simple, rewards, terminals, frames);
+  else
+    hipLaunchKernelGGL(k_venv_act<A3C_GAME_CATCH>, dim3((v->E + 63) / 64), dim3(64), 0, (hipStream_t)stream, v->p, v->b,
+                       v->E, actions, is_training, simple, rewards, terminals, frames);
   A3C_CHECK(hipGetLastError());
   return 0;
 }

@@ -21,6 +21,8 @@ A3C_ALGO_Q = 1
 A3C_TRUNK_NIPS = 0
 A3C_TRUNK_NATURE = 1
 A3C_LSTM_UNITS = 256
+A3C_GAME_SYNTH = 0   # the synthetic Atari stand-in
+A3C_GAME_CATCH = 1   # Catch (include/a3c_hip.h)
 MAX_TENSORS = 16
 
 c_int, c_i64, c_u64, c_float, c_double, c_void_p = (ctypes.c_int, ctypes.c_int64, ctypes.c_uint64,
@@ -120,6 +122,8 @@ SIGNATURES = {
     'a3c_lstm_workspace_bytes': (c_int, [c_int, c_i64, ctypes.POINTER(c_i64)]),
     'a3c_lstm_bptt': (c_int, [c_void_p, c_int, c_i64] + [c_void_p] * 12),
     'a3c_env_create': (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_u64, c_int, ctypes.POINTER(c_void_p)]),
+    'a3c_env_create_ex': (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_u64, c_int, c_int,
+                                  ctypes.POINTER(c_void_p)]),
     'a3c_env_destroy': (c_int, [c_void_p]),
     'a3c_env_new_game': (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     'a3c_env_act': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -127,6 +131,7 @@ SIGNATURES = {
     'a3c_env_buffers': (c_int, [c_void_p] + [ctypes.POINTER(c_void_p)] * 7),
     'a3c_engine_config_default': (None, [ctypes.POINTER(EngineConfig)]),
     'a3c_engine_create': (c_int, [ctypes.POINTER(EngineConfig), ctypes.POINTER(c_void_p)]),
+    'a3c_engine_create_ex': (c_int, [ctypes.POINTER(EngineConfig), c_int, ctypes.POINTER(c_void_p)]),
     'a3c_engine_destroy': (c_int, [c_void_p]),
     'a3c_engine_reset': (c_int, [c_void_p, c_void_p, c_void_p]),
     'a3c_engine_rollout_grad': (c_int, [c_void_p, c_void_p]),
@@ -187,7 +192,7 @@ OPTIONAL_IN_OLD_BUILDS = MEASUREMENT_ONLY + ('a3c_engine_exchange_split', 'a3c_e
                                              'a3c_engine_state_bytes', 'a3c_engine_state_save',
                                              'a3c_engine_state_load', 'a3c_play_config_default', 'a3c_engine_play',
                                              'a3c_engine_play_buffers', 'a3c_gae_returns', 'a3c_engine_play_ex',
-                                             'a3c_engine_play_schedule')
+                                             'a3c_engine_play_schedule', 'a3c_env_create_ex', 'a3c_engine_create_ex')
 
 KER_CONV12_FWD, KER_FC_FWD, KER_ENV_STEP, KER_CONV_BWD, KER_HEAD_SCREEN, KER_HEAD_SCREEN_CONV12, KER_FC_PART = 0, 1, 2, 3, 4, 5, 6
 # nature trunk passes (include/a3c_hip.h A3C_KER_NAT_*)

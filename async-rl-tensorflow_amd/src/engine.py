@@ -30,7 +30,10 @@ GAMES = {  # ALE minimal action sets / starting lives
     'Pong-v0': (6, 0),
     'Breakout-v0': (4, 5),
     'SpaceInvaders-v0': (6, 3),
+    'Catch-v0': (3, 0),
 }
+GAME_IDS = {'synth': _lib.A3C_GAME_SYNTH, 'catch': _lib.A3C_GAME_CATCH}
+CATCH_FRAMES = 640
 
 
 class _DevArray:
@@ -48,10 +51,18 @@ def _view(ptr, shape, dtype):
 
 
 class Engine:
-    def __init__(self, num_envs=256, n_step=5, action_size=6, algo='a3c', start_lives=0, num_frames=1024,
+    def __init__(self, num_envs=256, n_step=5, action_size=6, algo='a3c', start_lives=0, num_frames=None,
                  seed=123, env_id_base=0, world_size=1, use_graph=False, overlap=False, lstm=False,
-                 external_env=False, dqn_type='nips', **overrides):
+                 external_env=False, dqn_type='nips', game='synth', **overrides):
+        """game: 'synth' (the synthetic Atari stand-in) or 'catch' (Catch-v0, DESIGN §4g: action_size 3,
+        start_lives 0, device envs, raw RGB pool; random_start is ignored).  num_frames=None: 1024
+        frames (Catch needs its 640: a smaller explicit value is rejected by the library)."""
         _lib.require_device()
+        if game not in GAME_IDS:
+            raise ValueError('unknown game %r (the engine knows %s)' % (game, sorted(GAME_IDS)))
+        self.game = game
+        if num_frames is None:
+            num_frames = max(1024, CATCH_FRAMES)
         if lstm and algo != 'a3c':
             raise ValueError('the LSTM head is an a3c head')
         self.dqn_type = str(dqn_type).lower()
@@ -82,7 +93,10 @@ class Engine:
         self.A = int(action_size)
         self.E, self.n = int(num_envs), int(n_step)
         h = ctypes.c_void_p()
-        check(lib().a3c_engine_create(ctypes.byref(cfg), ctypes.byref(h)), 'a3c_engine_create')
+        if game == 'synth':
+            check(lib().a3c_engine_create(ctypes.byref(cfg), ctypes.byref(h)), 'a3c_engine_create')
+        else:
+            check(lib().a3c_engine_create_ex(ctypes.byref(cfg), GAME_IDS[game], ctypes.byref(h)), 'a3c_engine_create_ex')
         self._h = h
         b = _lib.EngineBuffers()
         check(lib().a3c_engine_get_buffers(h, ctypes.byref(b)), 'a3c_engine_get_buffers')

@@ -10,6 +10,10 @@ training and stops at a terminal (:78-96), ``screen`` is the fp64-luminance + Pi
 BILINEAR 84x84 image (:49-53, bit-exact).  Screens are u8 [84,84] device tensors.
 
 ``BatchedEnvironment`` is the same for E envs at once (the MI355X-native form).
+
+``env_name = 'Catch-v0'`` selects Catch instead (a3c_env_create_ex): a game with real
+dynamics -- 3 actions, no lives, 9-step episodes, reward +-1 at the landing -- behind the same
+interface; ``new_game`` / ``new_random_game`` are its reset, and ``random_start`` is ignored.
 """
 import ctypes
 
@@ -23,7 +27,11 @@ GAMES = {  # ALE minimal action sets and starting lives
     'Pong-v0': (6, 0),
     'Breakout-v0': (4, 5),
     'SpaceInvaders-v0': (6, 3),
+    'Catch-v0': (3, 0),       # the learnable device game: stay / left / right, no lives
 }
+GAME_KINDS = {'Catch-v0': 'catch'}     # every other name plays the synthetic stand-in ('synth')
+GAME_IDS = {'synth': _lib.A3C_GAME_SYNTH, 'catch': _lib.A3C_GAME_CATCH}
+CATCH_FRAMES = 640                     # Catch's state is its frame index: the pool must hold them all
 
 
 def game_spec(env_name):
@@ -32,8 +40,15 @@ def game_spec(env_name):
   return GAMES[env_name]
 
 
+def game_kind(env_name):
+  """'catch' or 'synth': the device game behind env_name (Engine(game=...), a3c_env_create_ex)."""
+  game_spec(env_name)
+  return GAME_KINDS.get(env_name, 'synth')
+
+
 class BatchedEnvironment(object):
-  """E synthetic Atari envs on device."""
+  """E device envs: the synthetic Atari stand-in, or Catch for env_name 'Catch-v0' (random_start is
+  ignored there: the reset is the random start)."""
 
   def __init__(self, config, num_envs=1, env_id_base=0, seed=None, num_frames=None):
     _lib.require_device()
@@ -47,9 +62,12 @@ class BatchedEnvironment(object):
     self.display = getattr(config, 'display', False)
     seed = int(getattr(config, 'random_seed', 123) if seed is None else seed)
     nf = int(num_frames if num_frames is not None else min(getattr(config, 'num_frames', 1024), 4096))
+    self.game = game_kind(config.env_name)
+    if self.game == 'catch' and num_frames is None:
+      nf = max(nf, CATCH_FRAMES)
     h = ctypes.c_void_p()
-    check(lib().a3c_env_create(self.E, self.action_size_, self.start_lives, self.random_start, self.action_repeat,
-                               nf, seed, int(env_id_base), ctypes.byref(h)), 'a3c_env_create')
+    check(lib().a3c_env_create_ex(self.E, self.action_size_, self.start_lives, self.random_start, self.action_repeat,
+                                  nf, seed, int(env_id_base), GAME_IDS[self.game], ctypes.byref(h)), 'a3c_env_create_ex')
     self._h = h
     ptrs = [ctypes.c_void_p() for _ in range(7)]
     check(lib().a3c_env_buffers(h, *[ctypes.byref(p) for p in ptrs]), 'a3c_env_buffers')

@@ -277,6 +277,28 @@ int a3c_rmsprop_range(float* w, float* ms, float* mom, const float* grads, int64
 typedef struct a3c_env a3c_env;
 int a3c_env_create(int num_envs, int action_size, int start_lives, int random_start, int action_repeat,
                    int num_frames, uint64_t seed, int env_id_base, a3c_env** out);
+/* The game the device envs play (a3c_engine_create_ex, a3c_env_create_ex).
+ *  A3C_GAME_SYNTH: the synthetic Atari stand-in above -- rewards, lives and episode ends are
+ *    Philox draws that do not depend on the action, which only picks a hashed noise frame.
+ *  A3C_GAME_CATCH ("Catch-v0"): a game that can be learned.  A ball falls down an 8-column,
+ *    10-row board, one row per step, onto a paddle in the bottom row: actions 0 stay, 1 left,
+ *    2 right (any other value: stay), the paddle clamped to the board.  At the landing (row 9)
+ *    the reward is +1 with the paddle in the ball's column, else -1, and the episode ends:
+ *    every episode lasts 9 steps, the optimal return is +1.  The state is the pool frame index
+ *    f = (c*10 + r)*8 + p < 640 (ball column c, ball row r, paddle column p); ep_step = r,
+ *    ep_len = 9, lives = 0.  reset: episode += 1, (x0, x1, ..) = philox(episode, id, P_RESET, 0),
+ *    c = x0 % 8, p = x1 % 8, r = 0; new_game and new_random_game are the reset (random_start is
+ *    ignored: the reset is the random start); a step draws nothing; a step on a landed state
+ *    changes nothing and returns reward 0, terminal 1.  Frame f of the pool is rendered, not
+ *    hashed: black, the ball's 21 x 20 px cell (rows 21r.., cols 20c..) in (236,236,236), then
+ *    the paddle, rows 200..209 x cols 20p..20p+19, in (92,186,92).
+ *    Needs num_frames >= 640, action_size 3, start_lives 0; not with frame84 or external_env
+ *    (A3C_ERR_INVALID).  a3c_hostenv_* stays the synthetic game. */
+#define A3C_GAME_SYNTH 0
+#define A3C_GAME_CATCH 1
+/* a3c_env_create with the game as an argument; a3c_env_create is game = A3C_GAME_SYNTH. */
+int a3c_env_create_ex(int num_envs, int action_size, int start_lives, int random_start, int action_repeat,
+                      int num_frames, uint64_t seed, int env_id_base, int game, a3c_env** out);
 int a3c_env_destroy(a3c_env* env);
 int a3c_env_new_game(a3c_env* env, const uint8_t* mask, int random, void* stream);
 int a3c_env_act(a3c_env* env, const int32_t* actions, int is_training, int simple, float* rewards,
@@ -349,6 +371,13 @@ typedef struct a3c_engine_config {
 
 void a3c_engine_config_default(a3c_engine_config* cfg);
 int a3c_engine_create(const a3c_engine_config* cfg, a3c_engine** out);
+/* a3c_engine_create with the game of the device envs, `game` = A3C_GAME_SYNTH or A3C_GAME_CATCH: the
+ * same fused rollout / play kernels step it (their Catch instantiations).  a3c_engine_create is
+ * game = A3C_GAME_SYNTH.  (An argument and not a field of a3c_engine_config, so that callers built
+ * against the struct as it stands stay valid -- as a3c_engine_play_ex's refill.)  A3C_ERR_INVALID
+ * for an unknown game, and for Catch with num_frames < 640, action_size != 3, start_lives != 0,
+ * frame84 or external_env; nothing is allocated or launched then. */
+int a3c_engine_create_ex(const a3c_engine_config* cfg, int game, a3c_engine** out);
 int a3c_engine_destroy(a3c_engine* eng);
 /* fill the frame pool, reset the envs (new_random_game, environment.py:35-40), fill each
  * history with 4 copies of the first screen (agent.py:37-38) and initialise params
