@@ -142,6 +142,15 @@ extern "C" int a3c_td_target(const float* rewards, const uint8_t* terminals, con
   return a3c_td_target_launch(rewards, terminals, q_next, B, A, zs, discount, target, (hipStream_t)stream);
 }
 
+extern "C" int a3c_nstep_q_target(const float* rewards, const uint8_t* terminals, const float* q_boot,
+                                  const float* q_sel, int n, int64_t E, int A, int zs, double discount, float* target,
+                                  void* stream) {
+  if (!rewards || !terminals || !q_boot || !target || n < 1 || E < 1 || A < 1 || zs < A)
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_nstep_q_target", "bad argument");
+  return a3c_nstep_q_target_launch(rewards, terminals, q_boot, q_sel, n, E, A, zs, discount, target,
+                                   (hipStream_t)stream);
+}
+
 extern "C" int a3c_loss_backward(const a3c_net_desc* net, const float* params, const uint8_t* states, int64_t B,
                                  const float* act_l1, const float* act_l2, const float* act_l3, const float* z,
                                  const int32_t* actions, const float* target, float beta, int literal_adv,

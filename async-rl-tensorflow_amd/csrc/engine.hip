@@ -279,6 +279,15 @@ extern "C" int a3c_engine_create_ex(const a3c_engine_config* cfg, int game, a3c_
     return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_create",
                          "gae_lambda != 1 with literal_adv: the lambda-return is a constant of the gradient");
   }
+  if (cfg->q_nstep != 0 && cfg->q_nstep != 1) {
+    delete e;
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_create", "q_nstep must be 0 or 1");
+  }
+  if (cfg->q_nstep && cfg->net.algo != A3C_ALGO_Q) {
+    delete e;
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_create",
+                         "q_nstep is a Q-learning option (algo a3c has its n-step returns already)");
+  }
   if (game != A3C_GAME_SYNTH && game != A3C_GAME_CATCH) {
     delete e;
     return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_create", "unknown game");
@@ -1019,7 +1028,28 @@ static int enqueue_grad_impl(a3c_engine* e, const Slot& sl, hipStream_t s) {
   const int E = e->E, n = e->n, zs = L.zs;
   const bool q = L.algo == A3C_ALGO_Q;
   int rc;
-  if (q) {
+  if (q && c.q_nstep) {
+    // n-step Q-learning (Algorithm S2): the target network on the one bootstrap state s_n of
+    // every env (E rows, not n*E), double Q: the slot's own parameters on the same state for the
+    // argmax; then the rollout's n-step returns from it
+    HeadSelect none = {};
+    none.mode = -1;
+    none.E = E;
+    const float* qsel = nullptr;
+    if (c.double_q) {
+      rc = a3c_forward_launch(L, sl.P, sl.prep, ring_addr(e, n, sl.tau), E, nullptr, sl.scr_l2, sl.scr_l3,
+                              sl.z + e->nE * zs, none, s);
+      if (rc) return rc;
+      qsel = sl.z + e->nE * zs;
+    }
+    rc = a3c_prep_fwd_launch(L, e->tparams, e->prep_t, s);
+    if (rc) return rc;
+    rc = a3c_forward_launch(L, e->tparams, e->prep_t, ring_addr(e, n, sl.tau), E, nullptr, sl.scr_l2, sl.scr_l3,
+                            e->zt, none, s);
+    if (rc) return rc;
+    rc = a3c_nstep_q_target_launch(sl.rewards, sl.terms, e->zt, qsel, n, E, L.A, zs, c.discount, sl.R_buf, s);
+    if (rc) return rc;
+  } else if (q) {
     // target network on s_{t+1} for every transition (agent.py:186)
     HeadSelect none = {};
     none.mode = -1;

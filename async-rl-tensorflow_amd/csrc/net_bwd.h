@@ -108,6 +108,10 @@ int a3c_gae_launch(const float* rewards, const uint8_t* terms, const float* valu
 // qsel != nullptr: double Q-learning -- the value of qn's row at qsel's row argmax (agent.py:176-184)
 int a3c_td_target_launch(const float* rewards, const uint8_t* terms, const float* qn, int64_t B, int A,
                          int zs, double discount, float* target, hipStream_t s, const float* qsel = nullptr);
+// n-step Q-learning: target [n][E] from the Q rows qb [E][zs] of the bootstrap state s_n (max over
+// A, or with qsel the value at qsel's row argmax) and k_returns' recursion with `discount`
+int a3c_nstep_q_target_launch(const float* rewards, const uint8_t* terms, const float* qb, const float* qsel, int n,
+                              int64_t E, int A, int zs, double discount, float* target, hipStream_t s);
 int a3c_select_launch(const float* z, int64_t B, int zs, int A, const HeadSelect& sel, hipStream_t s);
 void a3c_conv12_set_smem();
 void a3c_conv_bwd_set_smem();

@@ -6,6 +6,7 @@
 //  k_td_target   agent.py:186-190 in float64.
 //  k_gae         GAE(lambda) advantage and lambda-return per env in float64 (at the
 //                end of the file with k_head_bwd's GAE instantiations).
+//  k_nstep_q_target  n-step Q-learning targets per env in float64 (at the end of the file).
 //  k_head_bwd    one wave per sample: softmax/log-softmax/entropy, network.py:81-94 losses
 //                (A11 fixes) or agent.py:310-314 MSE, dz, dl3 = (W_h dz) * (l3 > 0).
 //  fc layer      gemm.hip: dW = l2^T dl3 (+colsum -> db), dl2 = (dl3 W^T) * (l2 > 0),
@@ -1477,6 +1478,57 @@ int a3c_gae_launch(const float* rewards, const uint8_t* terms, const float* valu
   else
     hipLaunchKernelGGL(k_gae<false>, grid, dim3(256), 0, s, rewards, terms, values, vstride, boot, boot_stride, n, E,
                        gamma, lambda, R, adv);
+  A3C_CHECK(hipGetLastError());
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------
+// Asynchronous n-step Q-learning (Algorithm S2 of the A3C paper)
+// ---------------------------------------------------------------------------------------
+// One thread per env: the bootstrap B_e = max_a qb[e][a] (qsel: qb[e] at qsel[e]'s first argmax,
+// k_td_target's double-Q form) of the state behind the rollout, then k_returns' recursion with the
+// Q engine's discount: R = B_e; for i = n-1 .. 0: terminal -> R = 0; R = r_i + discount R.
+// n = 1 is k_td_target to the last bit (the same fp64 operations).  A template (DOUBLE: qsel given), as
+// k_gae is: its instantiations are emitted behind every kernel the file had, which keep their place.
+template <bool DOUBLE>
+__global__ void __launch_bounds__(256) k_nstep_q_target(const float* __restrict__ rewards,
+                                                        const uint8_t* __restrict__ terms,
+                                                        const float* __restrict__ qb,
+                                                        const float* __restrict__ qsel, int n, int64_t E, int A,
+                                                        int zs, double discount, float* __restrict__ target) {
+#pragma clang fp contract(off)
+  int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= E) return;
+  float m = qb[e * zs];
+  if constexpr (DOUBLE) {
+    float best = qsel[e * zs];
+    int arg = 0;
+    for (int j = 1; j < A; ++j) {
+      const float v = qsel[e * zs + j];
+      if (v > best) { best = v; arg = j; }
+    }
+    m = qb[e * zs + arg];
+  } else {
+    for (int j = 1; j < A; ++j) m = fmaxf(m, qb[e * zs + j]);
+  }
+  double r = (double)m;
+  for (int i = n - 1; i >= 0; --i) {
+    if (terms[i * E + e]) r = 0.0;
+    r = (double)rewards[i * E + e] + discount * r;
+    target[i * E + e] = (float)r;
+  }
+}
+
+int a3c_nstep_q_target_launch(const float* rewards, const uint8_t* terms, const float* qb, const float* qsel, int n,
+                              int64_t E, int A, int zs, double discount, float* target, hipStream_t s) {
+  if (E <= 0) return 0;
+  const dim3 grid((unsigned)((E + 255) / 256));
+  if (qsel)
+    hipLaunchKernelGGL(k_nstep_q_target<true>, grid, dim3(256), 0, s, rewards, terms, qb, qsel, n, E, A, zs, discount,
+                       target);
+  else
+    hipLaunchKernelGGL(k_nstep_q_target<false>, grid, dim3(256), 0, s, rewards, terms, qb, qsel, n, E, A, zs, discount,
+                       target);
   A3C_CHECK(hipGetLastError());
   return 0;
 }

@@ -35,13 +35,15 @@ class NetDesc(ctypes.Structure):
 
 
 class EngineConfig(ctypes.Structure):
+    # q_nstep fills the 4 bytes that aligned ep_end_t: every other offset and the size are what they
+    # were without it (include/a3c_hip.h)
     _fields_ = [('net', NetDesc), ('num_envs', c_int), ('n_step', c_int), ('env_id_base', c_int),
                 ('world_size', c_int), ('start_lives', c_int), ('random_start', c_int),
                 ('action_repeat', c_int), ('num_frames', c_int), ('use_graph', c_int),
                 ('seed', c_u64), ('gamma', c_double), ('beta', c_float), ('learning_rate', c_float),
                 ('max_step', c_i64), ('decay', c_float), ('momentum', c_float), ('epsilon', c_float),
                 ('clip_norm', c_float), ('literal_adv', c_int), ('ep_start', c_float),
-                ('ep_end', c_float), ('ep_end_t', c_i64), ('learn_start', c_i64),
+                ('ep_end', c_float), ('q_nstep', c_int), ('ep_end_t', c_i64), ('learn_start', c_i64),
                 ('target_q_update_step', c_i64), ('discount', c_double), ('overlap', c_int),
                 ('external_env', c_int), ('frame84', c_int), ('split_exchange', c_int),
                 ('double_q', c_int), ('gae_lambda', c_float)]
@@ -97,6 +99,8 @@ SIGNATURES = {
                                 c_void_p, c_void_p, c_void_p]),
     'a3c_td_target': (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int, c_double, c_void_p,
                               c_void_p]),
+    'a3c_nstep_q_target': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_i64, c_int, c_int, c_double,
+                                   c_void_p, c_void_p]),
     'a3c_loss_backward': (c_int, [ctypes.POINTER(NetDesc), c_void_p, c_void_p, c_i64, c_void_p, c_void_p,
                                   c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_void_p,
                                   c_void_p, c_void_p, c_void_p]),
@@ -192,7 +196,8 @@ OPTIONAL_IN_OLD_BUILDS = MEASUREMENT_ONLY + ('a3c_engine_exchange_split', 'a3c_e
                                              'a3c_engine_state_bytes', 'a3c_engine_state_save',
                                              'a3c_engine_state_load', 'a3c_play_config_default', 'a3c_engine_play',
                                              'a3c_engine_play_buffers', 'a3c_gae_returns', 'a3c_engine_play_ex',
-                                             'a3c_engine_play_schedule', 'a3c_env_create_ex', 'a3c_engine_create_ex')
+                                             'a3c_engine_play_schedule', 'a3c_env_create_ex', 'a3c_engine_create_ex',
+                                             'a3c_nstep_q_target')
 
 KER_CONV12_FWD, KER_FC_FWD, KER_ENV_STEP, KER_CONV_BWD, KER_HEAD_SCREEN, KER_HEAD_SCREEN_CONV12, KER_FC_PART = 0, 1, 2, 3, 4, 5, 6
 # nature trunk passes (include/a3c_hip.h A3C_KER_NAT_*)

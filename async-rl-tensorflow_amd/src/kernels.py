@@ -354,5 +354,26 @@ def td_target(rewards, terminals, q_next, A, discount=0.99):
     return out
 
 
+def nstep_q_target(rewards, terminals, q_boot, A, discount=0.99, q_sel=None):
+    """n-step Q-learning targets [n,E] (a3c_nstep_q_target): rewards / terminals [n,E] of the rollout,
+    q_boot [E,zs] the Q rows of the bootstrap state s_n (A live columns), q_sel [E,zs] (optional, double Q) the
+    rows whose argmax picks q_boot's column."""
+    _dev(rewards, torch.float32, 'rewards')
+    _dev(terminals, torch.uint8, 'terminals')
+    _dev(q_boot, torch.float32, 'q_boot')
+    n, E = int(rewards.shape[0]), int(rewards.shape[1])
+    if tuple(terminals.shape) != (n, E) or q_boot.dim() != 2 or int(q_boot.shape[0]) != E:
+        raise ValueError('expected rewards / terminals [n, E] and q_boot [E, zs]')
+    if q_sel is not None:
+        _dev(q_sel, torch.float32, 'q_sel')
+        if tuple(q_sel.shape) != tuple(q_boot.shape):
+            raise ValueError('q_sel: expected the shape of q_boot')
+    out = torch.empty((n, E), dtype=torch.float32, device=rewards.device)
+    check(lib().a3c_nstep_q_target(ptr(rewards), ptr(terminals), ptr(q_boot), ptr(q_sel), n, E, int(A),
+                                   int(q_boot.shape[1]), float(discount), ptr(out), stream_handle()),
+          'a3c_nstep_q_target')
+    return out
+
+
 def copy_params(dst, src):
     check(lib().a3c_copy_params(ptr(dst), ptr(src), int(src.numel()), stream_handle()), 'a3c_copy_params')

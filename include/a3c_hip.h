@@ -170,6 +170,23 @@ int a3c_gae_returns(const float* rewards, const uint8_t* terminals, const float*
                     double lambda, float* R, float* adv, void* stream);
 
 /* ----------------------------------------------------------------------------
+ * K7c  n-step Q-learning targets (asynchronous n-step Q-learning, Algorithm S2 of the A3C paper)
+ *     over [n][E] in float64, contraction off, from the rollout's clipped rewards and terminals and
+ *     the Q rows of the bootstrap state s_n (row e of q_boot / q_sel at + e*zs, A live columns):
+ *       B_e = max_a q_boot[e][a]
+ *             q_sel != NULL (double Q): q_boot[e][argmax_a q_sel[e][a]]   (the first maximum)
+ *       R   = (double)B_e
+ *       for i = n-1 .. 0:  if terminals[i][e]: R = 0;  R = rewards[i][e] + discount*R;
+ *                          target[i][e] = (float)R
+ *     n = 1 is a3c_td_target to the last bit.  The engine (cfg.q_nstep) takes q_boot from the
+ *     target network and q_sel from the slot's own parameters.
+ *     A3C_ERR_INVALID: a null pointer other than q_sel, n < 1, E < 1, A < 1, zs < A.
+ * -------------------------------------------------------------------------- */
+int a3c_nstep_q_target(const float* rewards, const uint8_t* terminals, const float* q_boot,
+                       const float* q_sel, int n, int64_t E, int A, int zs, double discount,
+                       float* target, void* stream);
+
+/* ----------------------------------------------------------------------------
  * K8+K9  loss + backward (network.py:81-94 with the SURVEY §8 A11 fixes / agent.py:306-317).
  *  target: a3c -> R (n-step return); q -> TD target.
  *  a3c loss per sample  -log pi(a)*stopgrad(R-V) - beta*H + (R-V)^2/2, summed over B
@@ -337,7 +354,16 @@ typedef struct a3c_engine_config {
   float clip_norm;       /* agent.py:319: 40                                          */
   int literal_adv;       /* 1: network.py literal un-stopped advantage gradient       */
   /* q-learning only */
-  float ep_start, ep_end; int64_t ep_end_t, learn_start;  /* config.py:18-25         */
+  float ep_start, ep_end;   /* config.py:18-19                                          */
+  int q_nstep;        /* q only: 1 = asynchronous n-step Q-learning (Algorithm S2; a3c_nstep_q_target): the
+                        target of step i of the rollout is its n-step return, bootstrapped from the target
+                        net on s_n alone (double_q: at the slot's own argmax), instead of the one-step TD
+                        target of every transition.  0 (default): one-step.  Other values, and 1 with
+                        algo a3c, are rejected.  A hyperparameter (not in the checkpoint's state; play does
+                        not read it).  python async-rl-tensorflow_amd/main.py --mode engine --algo q
+                        --q_nstep true --n_step 5 --env_name Catch-v0.  It takes the 4 bytes that aligned ep_end_t: the size
+                        and every other offset of this struct are what they were without it.     */
+  int64_t ep_end_t, learn_start;  /* config.py:20-25                                    */
   int64_t target_q_update_step;   /* config.py:10 (4e4)                               */
   double discount;                /* config.py:9                                      */
   int overlap;        /* 1 (a3c, q; not with host envs): rollout k runs on an engine stream while the backward +
