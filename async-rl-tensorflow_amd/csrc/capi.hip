@@ -151,6 +151,28 @@ extern "C" int a3c_nstep_q_target(const float* rewards, const uint8_t* terminals
                                    (hipStream_t)stream);
 }
 
+extern "C" int a3c_boot_action(const float* q, const float* eps, int64_t E, int A, int zs, int64_t tau, int env_id_base,
+                               uint64_t seed, int32_t* boot_actions, void* stream) {
+  if (!q || !eps || !boot_actions || E < 1 || E > INT32_MAX || A < 1 || zs < A)
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_boot_action", "bad argument");
+  HeadSelect sel = {};
+  sel.mode = 1;
+  sel.k0 = (uint32_t)seed; sel.k1 = (uint32_t)(seed >> 32);
+  sel.env_id_base = env_id_base; sel.E = (int)E;
+  sel.eps = eps;
+  return a3c_boot_action_launch(sel, nullptr, tau, q, zs, A, boot_actions, (hipStream_t)stream);
+}
+
+extern "C" int a3c_sarsa_target(const float* rewards, const uint8_t* terminals, const int32_t* actions,
+                                const int32_t* boot_actions, const float* q_target, int nstep, int n, int64_t E, int A,
+                                int zs, double discount, float* target, void* stream) {
+  if (!rewards || !terminals || !actions || !boot_actions || !q_target || !target || (nstep != 0 && nstep != 1) ||
+      n < 1 || E < 1 || A < 1 || zs < A)
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_sarsa_target", "bad argument");
+  return a3c_sarsa_target_launch(rewards, terminals, actions, boot_actions, q_target, nstep, n, E, A, zs, discount,
+                                 target, (hipStream_t)stream);
+}
+
 extern "C" int a3c_loss_backward(const a3c_net_desc* net, const float* params, const uint8_t* states, int64_t B,
                                  const float* act_l1, const float* act_l2, const float* act_l3, const float* z,
                                  const int32_t* actions, const float* target, float beta, int literal_adv,

@@ -41,6 +41,7 @@ struct Slot {
   uint8_t* terms;          // [n][E]
   float* z;                // [(n+1)][E][zs]
   float* R_buf;            // [n][E] returns / TD targets
+  int32_t* boot_action;    // sarsa: [E] the action drawn for the bootstrap state s_n (k_boot_action)
   float *act_l1, *act_l2, *act_l3;
   float* act_l4;           // nature trunk: the fc output [n*E][512] (act_l1..3: its conv outputs)
   float* nscr;             // nature trunk: the bootstrap state's activations [E][l1 | l2 | l3 | l4]
@@ -105,6 +106,7 @@ struct a3c_engine {
   int fused_screen;        // 1: screen kernel fused into the head (k_head_screen)
   int frame84;             // cfg.frame84: pre-sized 84x84 pool frames (measurement mode M2)
   int game;                // A3C_GAME_*: the device envs' game (a3c_engine_create_ex)
+  int sarsa;               // a3c_engine_opts.sarsa: Sarsa targets
   int fuse_conv;           // 1: step t+1's conv1 + conv2 fused into step t's head + screen
   unsigned long long* spans;  // [2][SPAN_RECS][2]: live launch spans of k_conv_bwd, k_head_screen_conv12
   Slot slot[2];
@@ -244,13 +246,30 @@ static int frame_bytes(const a3c_engine* e) { return e->frame84 ? PLANE : SCREEN
 
 static bool boot_bwd(const a3c_engine* e);
 static int l2bits_choice(const a3c_engine* e);
+extern "C" void a3c_engine_opts_default(a3c_engine_opts* o) {
+  memset(o, 0, sizeof(*o));
+  o->size = (int)sizeof(*o);
+  o->game = A3C_GAME_SYNTH;
+  o->sarsa = 0;
+}
+
 extern "C" int a3c_engine_create(const a3c_engine_config* cfg, a3c_engine** out) {
   return a3c_engine_create_ex(cfg, A3C_GAME_SYNTH, out);
 }
 
 extern "C" int a3c_engine_create_ex(const a3c_engine_config* cfg, int game, a3c_engine** out) {
+  a3c_engine_opts o;
+  a3c_engine_opts_default(&o);
+  o.game = game;
+  return a3c_engine_create_opts(cfg, &o, out);
+}
+
+extern "C" int a3c_engine_create_opts(const a3c_engine_config* cfg, const a3c_engine_opts* opts, a3c_engine** out) {
   if (!cfg || !out) return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_create", "null");
   *out = nullptr;
+  if (!opts || opts->size < (int)sizeof(a3c_engine_opts))
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_create", "opts: null, or size smaller than the fields read");
+  const int game = opts->game, sarsa = opts->sarsa;
   a3c_engine* e = new (std::nothrow) a3c_engine();
   if (!e) return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_create", "oom");
   e->cfg = *cfg;
@@ -292,6 +311,19 @@ extern "C" int a3c_engine_create_ex(const a3c_engine_config* cfg, int game, a3c_
     delete e;
     return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_create", "unknown game");
   }
+  if (sarsa != 0 && sarsa != 1) {
+    delete e;
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_create", "sarsa must be 0 or 1");
+  }
+  if (sarsa && cfg->net.algo != A3C_ALGO_Q) {
+    delete e;
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_create", "sarsa is a Q-learning option (its target is a Q value)");
+  }
+  if (sarsa && cfg->double_q) {
+    delete e;
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_create",
+                         "sarsa with double_q: double Q picks the argmax, Sarsa the taken action");
+  }
   // Catch: its frame index is its state, f < 640 -- the pool must hold those frames, as
   // raw RGB, on the device
   if (game == A3C_GAME_CATCH && (cfg->num_frames < 640 || cfg->net.action_size != 3 || cfg->start_lives != 0 ||
@@ -301,6 +333,7 @@ extern "C" int a3c_engine_create_ex(const a3c_engine_config* cfg, int game, a3c_
                          "Catch needs num_frames >= 640, action_size 3, start_lives 0, no frame84, no external_env");
   }
   e->game = game;
+  e->sarsa = sarsa;
   a3c_init_once();
   const NetLayout& L = e->L;
   e->E = cfg->num_envs;
@@ -430,6 +463,8 @@ extern "C" int a3c_engine_create_ex(const a3c_engine_config* cfg, int game, a3c_
   // last: the other buffers keep the placement they had before the ReLU bits existed
   for (int k = 0; k < e->nslot; ++k) ALLOC(e->slot[k].l2m, nE * C2_Q * 4);
   ALLOC(e->fctick, fctick_bytes(E));
+  if (e->sarsa)   // (behind everything an engine without it allocates)
+    for (int k = 0; k < e->nslot; ++k) ALLOC(e->slot[k].boot_action, E * 4);
   if (hipError_t st = hipMemset(e->fctick, 0, fctick_bytes(E))) {
     a3c_engine_destroy(e);
     return a3c_set_error((int)st, "a3c_engine_create", "hipMemset failed");
@@ -1028,7 +1063,34 @@ static int enqueue_grad_impl(a3c_engine* e, const Slot& sl, hipStream_t s) {
   const int E = e->E, n = e->n, zs = L.zs;
   const bool q = L.algo == A3C_ALGO_Q;
   int rc;
-  if (q && c.q_nstep) {
+  if (q && e->sarsa) {
+    // Sarsa: the slot's own parameters on s_n (double Q's launch); the target network on
+    // s_1..s_n (q_nstep: on s_n alone); then one kernel draws, from the slot's rows, the action the
+    // rollout's head would draw in s_n, at the slot's tau + n (sl.tau holds tau alone: the schedule's base
+    // step comes from the counters, where only a3c_engine_set_step writes it), and forms the targets at
+    // the taken actions -- as many launches as double Q
+    HeadSelect none = {};
+    none.mode = -1;
+    none.E = E;
+    rc = a3c_forward_launch(L, sl.P, sl.prep, ring_addr(e, n, sl.tau), E, nullptr, sl.scr_l2, sl.scr_l3,
+                            sl.z + e->nE * zs, none, s);
+    if (rc) return rc;
+    HeadSelect sel = {};
+    sel.mode = 1;
+    sel.k0 = e->k0; sel.k1 = e->k1;
+    sel.tau_ptr = e->counters;
+    sel.env_ids = nullptr; sel.env_id_base = c.env_id_base; sel.E = E;
+    set_eps_schedule(e, sel);
+    const BootDraw bd = {sel, sl.tau, sl.z + e->nE * zs, sl.boot_action};
+    rc = a3c_prep_fwd_launch(L, e->tparams, e->prep_t, s);
+    if (rc) return rc;
+    rc = a3c_forward_launch(L, e->tparams, e->prep_t, ring_addr(e, c.q_nstep ? n : 1, sl.tau), c.q_nstep ? E : e->nE,
+                            nullptr, sl.scr_l2, sl.scr_l3, e->zt, none, s);
+    if (rc) return rc;
+    rc = a3c_sarsa_target_launch(sl.rewards, sl.terms, sl.actions, nullptr, e->zt, c.q_nstep, n, E, L.A, zs,
+                                 c.discount, sl.R_buf, s, &bd);
+    if (rc) return rc;
+  } else if (q && c.q_nstep) {
     // n-step Q-learning (Algorithm S2): the target network on the one bootstrap state s_n of
     // every env (E rows, not n*E), double Q: the slot's own parameters on the same state for the
     // argmax; then the rollout's n-step returns from it
@@ -1684,6 +1746,12 @@ extern "C" int a3c_engine_state_load(a3c_engine* e, const void* host, int64_t by
     o += x.bytes;
   }
   A3C_CHECK(hipMemset(e->xflags, 0, 64));       // fresh cross-stream sequence numbers
+  // q, overlap: the pending backward of the rollout in flight may run a forward with the slot's own
+  // parameters (Sarsa's and double Q's forward of s_n), which reads the slot's prepared weights: derived
+  // from sl.P, not saved, so made again here
+  if (e->overlap && e->L.algo == A3C_ALGO_Q)
+    for (int k = 0; k < e->nslot; ++k)
+      if (int rc = a3c_prep_fwd_launch(e->L, e->slot[k].P, e->slot[k].prep, s)) return rc;
   A3C_CHECK(hipDeviceSynchronize());
   e->s_seq = e->r_seq = 0;
   e->roll_seq[0] = e->roll_seq[1] = 0;
@@ -1730,6 +1798,13 @@ extern "C" int a3c_engine_advance(a3c_engine* e, void* stream) {
   hipLaunchKernelGGL(k_advance, dim3(1), dim3(1), 0, (hipStream_t)stream, e->counters, (int64_t)e->n,
                      e->nE * e->cfg.world_size);
   A3C_CHECK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int a3c_engine_slot_boot_actions(a3c_engine* e, int slot, int32_t** out) {
+  if (!e || !out || slot < 0 || slot >= e->nslot || !e->sarsa)
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_slot_boot_actions", "bad argument, or an engine without sarsa");
+  *out = e->slot[slot].boot_action;
   return 0;
 }
 

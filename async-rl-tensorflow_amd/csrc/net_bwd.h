@@ -112,6 +112,24 @@ int a3c_td_target_launch(const float* rewards, const uint8_t* terms, const float
 // A, or with qsel the value at qsel's row argmax) and k_returns' recursion with `discount`
 int a3c_nstep_q_target_launch(const float* rewards, const uint8_t* terms, const float* qb, const float* qsel, int n,
                               int64_t E, int A, int zs, double discount, float* target, hipStream_t s);
+// Sarsa: boot_action [sel.E] <- the draw the rollout's head would make at step *tau0 + n (tau0 null:
+// at step n) from the Q rows q [E][zs] (sel: mode 1, key, env ids, eps / the schedule with tau_ptr the counters:
+// only tau_ptr[2] is read)
+int a3c_boot_action_launch(const HeadSelect& sel, const int64_t* tau0, int64_t n, const float* q, int zs, int A,
+                           int32_t* boot_action, hipStream_t s);
+// the draw of a_n fused into the target kernel (the engine): a3c_boot_action_launch's arguments
+struct BootDraw {
+  HeadSelect sel;
+  const int64_t* tau0;      // the slot's rollout-start tau (device); the draw's step is *tau0 + n
+  const float* q;           // [E][zs] the slot's own parameters' Q rows of s_n
+  int32_t* boot_action;     // [E] out
+};
+// target [n][E] at the taken actions: qt [n*E][zs] of s_1..s_n (nstep 0, k_td_target's form) or [E][zs] of s_n
+// (nstep 1, k_nstep_q_target's recursion); a' = actions[i+1][e], boot[e] behind the rollout.  draw != nullptr:
+// boot is not read -- the kernel draws a_n itself, as a3c_boot_action_launch would, and writes draw->boot_action
+int a3c_sarsa_target_launch(const float* rewards, const uint8_t* terms, const int32_t* actions, const int32_t* boot,
+                            const float* qt, int nstep, int n, int64_t E, int A, int zs, double discount,
+                            float* target, hipStream_t s, const BootDraw* draw = nullptr);
 int a3c_select_launch(const float* z, int64_t B, int zs, int A, const HeadSelect& sel, hipStream_t s);
 void a3c_conv12_set_smem();
 void a3c_conv_bwd_set_smem();

@@ -7,6 +7,8 @@
 //  k_gae         GAE(lambda) advantage and lambda-return per env in float64 (at the
 //                end of the file with k_head_bwd's GAE instantiations).
 //  k_nstep_q_target  n-step Q-learning targets per env in float64 (at the end of the file).
+//  k_boot_action, k_sarsa_target  Sarsa: the bootstrap state's action draw and the targets at the taken
+//                actions in float64 (at the end of the file).
 //  k_head_bwd    one wave per sample: softmax/log-softmax/entropy, network.py:81-94 losses
 //                (A11 fixes) or agent.py:310-314 MSE, dz, dl3 = (W_h dz) * (l3 > 0).
 //  fc layer      gemm.hip: dW = l2^T dl3 (+colsum -> db), dl2 = (dl3 W^T) * (l2 > 0),
@@ -22,6 +24,7 @@
 #include "net.h"
 #include "gemm.h"
 #include "net_bwd.h"
+#include "net_head.h"
 #ifdef A3C_MARKERS
 void a3c_mark(int id, hipStream_t s);
 #endif
@@ -1529,6 +1532,137 @@ int a3c_nstep_q_target_launch(const float* rewards, const uint8_t* terms, const 
   else
     hipLaunchKernelGGL(k_nstep_q_target<false>, grid, dim3(256), 0, s, rewards, terms, qb, qsel, n, E, A, zs, discount,
                        target);
+  A3C_CHECK(hipGetLastError());
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------
+// Asynchronous one-step / n-step Sarsa (Algorithm S1 of the A3C paper with the Sarsa target
+// r + gamma Q(s', a'; theta^-) of its §4)
+// ---------------------------------------------------------------------------------------
+// The action the behaviour policy takes in the bootstrap state s_n: the draw the rollout's head would
+// make for env e at step tau (action_draw / sel_eps of net_head.h: the same Philox key, the same epsilon
+// schedule), from the Q rows q [E][zs] of s_n.  sel.tau_ptr (the live counters) only gives sel_eps its
+// base step tau_ptr[2], which no rollout writes.
+__device__ inline int32_t boot_draw(const HeadSelect& sel, int64_t tau, const float* __restrict__ q, int zs, int A,
+                                    int64_t e) {
+  const u32x4 x = action_draw(sel, e, tau);
+  const float eps = sel_eps(sel, (int)e, tau);
+  if (u01(x.x) < eps) return (int32_t)(x.y % (uint32_t)A);
+  float best = q[e * zs];
+  int32_t a = 0;
+  for (int j = 1; j < A; ++j) {
+    const float v = q[e * zs + j];
+    if (v > best) { best = v; a = j; }
+  }
+  return a;
+}
+
+// boot_action [sel.E] <- boot_draw at step *tau0 + n (DEV: tau0 is a slot's rollout-start tau, read here) or at
+// step n (a3c_boot_action).  One thread per env.  A template, as k_gae is: emitted behind every kernel the
+// file had.
+template <bool DEV>
+__global__ void __launch_bounds__(256) k_boot_action(HeadSelect sel, const int64_t* __restrict__ tau0, int64_t n,
+                                                     const float* __restrict__ q, int zs, int A,
+                                                     int32_t* __restrict__ boot_action) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= sel.E) return;
+  int64_t tau = n;
+  if constexpr (DEV) tau += *tau0;
+  boot_action[e] = boot_draw(sel, tau, q, zs, A, e);
+}
+
+int a3c_boot_action_launch(const HeadSelect& sel, const int64_t* tau0, int64_t n, const float* q, int zs, int A,
+                           int32_t* boot_action, hipStream_t s) {
+  if (sel.E <= 0) return 0;
+  const dim3 grid((unsigned)((sel.E + 255) / 256));
+  if (tau0)
+    hipLaunchKernelGGL(k_boot_action<true>, grid, dim3(256), 0, s, sel, tau0, n, q, zs, A, boot_action);
+  else
+    hipLaunchKernelGGL(k_boot_action<false>, grid, dim3(256), 0, s, sel, tau0, n, q, zs, A, boot_action);
+  A3C_CHECK(hipGetLastError());
+  return 0;
+}
+
+// Sarsa targets of one rollout, one thread per env.  qt: the target network's rows, [n*E][zs] of
+// s_1 .. s_n (NSTEP = false) or [E][zs] of s_n (NSTEP = true).  a' of step i is the rollout's next action
+// actions[i+1][e], of the last step a_n[e]; an action word is reduced into [0, A) as an unsigned
+// value before it is a column offset, so any word reads inside its row.
+//   one-step: target[i][e] = (1 - term) discount qt(s_{i+1})[e][a'] + r         (k_td_target's operand order)
+//   n-step:   R = qt(s_n)[e][a_n[e]]; i = n-1 .. 0: terminal -> R = 0; R = r + discount R   (k_nstep_q_target's)
+// DRAW (the engine): a_n[e] is drawn here -- k_boot_action's boot_draw at *bd.tau0 + n from bd.q, written to
+// bd.boot_action -- so the engine's gradient has no launch more than double Q's; else it is read from boot.
+// The one-step steps are independent: their loads are issued eight steps at a time, then the arithmetic.
+template <bool NSTEP, bool DRAW>
+__global__ void __launch_bounds__(256) k_sarsa_target(const float* __restrict__ rewards,
+                                                      const uint8_t* __restrict__ terms,
+                                                      const int32_t* __restrict__ actions,
+                                                      const int32_t* __restrict__ boot,
+                                                      const float* __restrict__ qt, int n, int64_t E, int A, int zs,
+                                                      double discount, float* __restrict__ target, BootDraw bd) {
+#pragma clang fp contract(off)
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= E) return;
+  uint32_t an;
+  if constexpr (DRAW) {
+    const int32_t a = boot_draw(bd.sel, *bd.tau0 + n, bd.q, zs, A, e);
+    bd.boot_action[e] = a;
+    an = (uint32_t)a % (uint32_t)A;
+  } else {
+    an = (uint32_t)boot[e] % (uint32_t)A;
+  }
+  if constexpr (NSTEP) {
+    double r = (double)qt[e * zs + an];
+    for (int i = n - 1; i >= 0; --i) {
+      if (terms[i * E + e]) r = 0.0;
+      r = (double)rewards[i * E + e] + discount * r;
+      target[i * E + e] = (float)r;
+    }
+  } else {
+    for (int i0 = 0; i0 < n; i0 += 8) {
+      uint32_t a[8];
+      float m[8], rw[8];
+      uint8_t tm[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const int i = i0 + k;
+        if (i < n) {
+          const int64_t b = i * E + e;
+          a[k] = i < n - 1 ? (uint32_t)actions[b + E] % (uint32_t)A : an;
+          rw[k] = rewards[b];
+          tm[k] = terms[b];
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < 8; ++k)
+        if (i0 + k < n) m[k] = qt[((i0 + k) * E + e) * zs + a[k]];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        if (i0 + k < n) {
+          const double t = tm[k] ? 1.0 : 0.0;
+          const double v = (1.0 - t) * discount * (double)m[k] + (double)rw[k];
+          target[(i0 + k) * E + e] = (float)v;
+        }
+      }
+    }
+  }
+}
+
+int a3c_sarsa_target_launch(const float* rewards, const uint8_t* terms, const int32_t* actions, const int32_t* boot,
+                            const float* qt, int nstep, int n, int64_t E, int A, int zs, double discount,
+                            float* target, hipStream_t s, const BootDraw* draw) {
+  if (E <= 0) return 0;
+  const dim3 grid((unsigned)((E + 255) / 256));
+  const BootDraw bd = draw ? *draw : BootDraw{};
+#define SARSA_LAUNCH(NS, DR)                                                                                      \
+  hipLaunchKernelGGL((k_sarsa_target<NS, DR>), grid, dim3(256), 0, s, rewards, terms, actions, boot, qt, n, E, A, \
+                     zs, discount, target, bd)
+  if (draw) {
+    if (nstep) SARSA_LAUNCH(true, true); else SARSA_LAUNCH(false, true);
+  } else {
+    if (nstep) SARSA_LAUNCH(true, false); else SARSA_LAUNCH(false, false);
+  }
+#undef SARSA_LAUNCH
   A3C_CHECK(hipGetLastError());
   return 0;
 }

@@ -10,6 +10,7 @@ accepted but the TF ps/worker cluster is replaced by one process per GPU under t
   python main.py --mode engine --env_name Pong-v0 --iterations 1000
   python main.py --mode engine --env_name Catch-v0 --iterations 1000   the learnable device game
   python main.py --mode engine --algo q --q_nstep true --n_step 5 --env_name Catch-v0   n-step Q-learning
+  python main.py --mode engine --algo q --sarsa true --n_step 5 --env_name Catch-v0     Sarsa (--q_nstep true: n-step)
   python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 main.py --mode engine
   python main.py --mode engine --is_train false --n_episode 100     evaluate the newest checkpoint
   python main.py --mode engine --is_train false --play_refill true  ... refilling finished envs (no waves)
@@ -64,6 +65,10 @@ def parse_flags(argv=None):
   p.add_argument('--q_nstep', type=str2bool, default=False,
                  help='engine mode, q: asynchronous n-step Q-learning (Algorithm S2) -- the target of every step of '
                       'the rollout is its n-step return, bootstrapped from the target network on s_n (DESIGN §4h)')
+  p.add_argument('--sarsa', type=str2bool, default=False,
+                 help='engine mode, q: asynchronous Sarsa -- the target takes the target network at the action the '
+                      'behaviour policy takes in the next state, not at the maximum; with --q_nstep true n-step Sarsa '
+                      '(DESIGN §4i)')
   p.add_argument('--num_envs', type=int, default=256)
   p.add_argument('--num_frames', type=int, default=16384)
   p.add_argument('--iterations', type=int, default=1000)
@@ -127,6 +132,10 @@ def engine_options(flags):
     raise ValueError('--gae_lambda is an A3C option (algo q has one-step TD targets): use it with --algo a3c')
   if flags.q_nstep and flags.algo != 'q':
     raise ValueError('--q_nstep is a Q-learning option (n-step targets, DESIGN §4h): use it with --algo q')
+  if flags.sarsa and flags.algo != 'q':
+    raise ValueError('--sarsa is a Q-learning option (its target is a Q value, DESIGN §4i): use it with --algo q')
+  if flags.sarsa and flags.double_q:
+    raise ValueError('--sarsa with --double_q: double Q picks the argmax, Sarsa the taken action (DESIGN §4i)')
   kw = dict(lstm=bool(flags.lstm))
   if flags.gae_lambda != 1.0:
     kw['gae_lambda'] = float(flags.gae_lambda)
@@ -134,6 +143,8 @@ def engine_options(flags):
     kw['double_q'] = True
   if flags.q_nstep:
     kw['q_nstep'] = 1
+  if flags.sarsa:
+    kw['sarsa'] = 1
   if flags.dqn_type == 'nature':
     kw['dqn_type'] = 'nature'
   return kw
@@ -405,6 +416,8 @@ def main(argv=None):
     raise ValueError('--gae_lambda is an engine option: --mode agent is the per-step Q-learning loop')
   if flags.mode == 'agent' and flags.q_nstep:
     raise ValueError('--q_nstep is an engine option: --mode agent is the per-step Q-learning loop (one-step targets)')
+  if flags.mode == 'agent' and flags.sarsa:
+    raise ValueError('--sarsa is an engine option: --mode agent is the per-step Q-learning loop (max targets)')
   random.seed(flags.random_seed)
   np.random.seed(flags.random_seed)
   from config import get_config

@@ -63,6 +63,11 @@ class EngineBuffers(ctypes.Structure):
                 ('lstm_gates', c_void_p), ('lstm_units', c_int), ('act_l4', c_void_p), ('trunk', c_int)]
 
 
+class EngineOpts(ctypes.Structure):
+    """a3c_engine_opts (a3c_engine_create_opts): size-prefixed, later options append."""
+    _fields_ = [('size', c_int), ('game', c_int), ('sarsa', c_int)]
+
+
 class PlayConfig(ctypes.Structure):
     """a3c_play_config (Agent.play's arguments, agent.py:351)."""
     _fields_ = [('n_episode', c_int), ('n_step', c_int), ('greedy', c_int), ('test_ep', c_float),
@@ -101,6 +106,9 @@ SIGNATURES = {
                               c_void_p]),
     'a3c_nstep_q_target': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_i64, c_int, c_int, c_double,
                                    c_void_p, c_void_p]),
+    'a3c_boot_action': (c_int, [c_void_p, c_void_p, c_i64, c_int, c_int, c_i64, c_int, c_u64, c_void_p, c_void_p]),
+    'a3c_sarsa_target': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_i64, c_int, c_int,
+                                 c_double, c_void_p, c_void_p]),
     'a3c_loss_backward': (c_int, [ctypes.POINTER(NetDesc), c_void_p, c_void_p, c_i64, c_void_p, c_void_p,
                                   c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_void_p,
                                   c_void_p, c_void_p, c_void_p]),
@@ -136,6 +144,9 @@ SIGNATURES = {
     'a3c_engine_config_default': (None, [ctypes.POINTER(EngineConfig)]),
     'a3c_engine_create': (c_int, [ctypes.POINTER(EngineConfig), ctypes.POINTER(c_void_p)]),
     'a3c_engine_create_ex': (c_int, [ctypes.POINTER(EngineConfig), c_int, ctypes.POINTER(c_void_p)]),
+    'a3c_engine_opts_default': (None, [ctypes.POINTER(EngineOpts)]),
+    'a3c_engine_create_opts': (c_int, [ctypes.POINTER(EngineConfig), ctypes.POINTER(EngineOpts),
+                                       ctypes.POINTER(c_void_p)]),
     'a3c_engine_destroy': (c_int, [c_void_p]),
     'a3c_engine_reset': (c_int, [c_void_p, c_void_p, c_void_p]),
     'a3c_engine_rollout_grad': (c_int, [c_void_p, c_void_p]),
@@ -146,6 +157,7 @@ SIGNATURES = {
     'a3c_engine_span_raw': (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
     'a3c_engine_get_buffers': (c_int, [c_void_p, ctypes.POINTER(EngineBuffers)]),
     'a3c_engine_slot_buffers': (c_int, [c_void_p, c_int, ctypes.POINTER(EngineBuffers)]),
+    'a3c_engine_slot_boot_actions': (c_int, [c_void_p, c_int, ctypes.POINTER(c_void_p)]),
     'a3c_engine_grad_ready': (c_int, [c_void_p]),
     'a3c_engine_advance': (c_int, [c_void_p, c_void_p]),
     'a3c_engine_set_step': (c_int, [c_void_p, c_i64, c_i64, c_void_p]),
@@ -197,7 +209,9 @@ OPTIONAL_IN_OLD_BUILDS = MEASUREMENT_ONLY + ('a3c_engine_exchange_split', 'a3c_e
                                              'a3c_engine_state_load', 'a3c_play_config_default', 'a3c_engine_play',
                                              'a3c_engine_play_buffers', 'a3c_gae_returns', 'a3c_engine_play_ex',
                                              'a3c_engine_play_schedule', 'a3c_env_create_ex', 'a3c_engine_create_ex',
-                                             'a3c_nstep_q_target')
+                                             'a3c_nstep_q_target', 'a3c_engine_opts_default',
+                                             'a3c_engine_create_opts', 'a3c_engine_slot_boot_actions',
+                                             'a3c_boot_action', 'a3c_sarsa_target')
 
 KER_CONV12_FWD, KER_FC_FWD, KER_ENV_STEP, KER_CONV_BWD, KER_HEAD_SCREEN, KER_HEAD_SCREEN_CONV12, KER_FC_PART = 0, 1, 2, 3, 4, 5, 6
 # nature trunk passes (include/a3c_hip.h A3C_KER_NAT_*)

@@ -56,7 +56,9 @@ class Engine:
                  external_env=False, dqn_type='nips', game='synth', **overrides):
         """game: 'synth' (the synthetic Atari stand-in) or 'catch' (Catch-v0, DESIGN §4g: action_size 3,
         start_lives 0, device envs, raw RGB pool; random_start is ignored).  num_frames=None: 1024
-        frames (Catch needs its 640: a smaller explicit value is rejected by the library)."""
+        frames (Catch needs its 640: a smaller explicit value is rejected by the library).
+        sarsa=0|1 (algo q): Sarsa targets, with q_nstep=1 n-step Sarsa; an option of
+        a3c_engine_opts, not a field of the config."""
         _lib.require_device()
         if game not in GAME_IDS:
             raise ValueError('unknown game %r (the engine knows %s)' % (game, sorted(GAME_IDS)))
@@ -84,6 +86,14 @@ class Engine:
         cfg.external_env = 1 if external_env else 0
         self.overlap = bool(overlap)
         self.external_env = bool(external_env)
+        # options of a3c_engine_opts (the config struct cannot grow): out before the config's fields
+        opts = None
+        if 'sarsa' in overrides:
+            opts = _lib.EngineOpts()
+            lib().a3c_engine_opts_default(ctypes.byref(opts))
+            opts.game = GAME_IDS[game]
+            opts.sarsa = int(overrides.pop('sarsa'))
+        self.sarsa = bool(opts.sarsa) if opts is not None else False
         for k, v in overrides.items():
             if not hasattr(cfg, k):
                 raise ValueError(f'unknown engine option {k}')
@@ -93,7 +103,10 @@ class Engine:
         self.A = int(action_size)
         self.E, self.n = int(num_envs), int(n_step)
         h = ctypes.c_void_p()
-        if game == 'synth':
+        if opts is not None:
+            check(lib().a3c_engine_create_opts(ctypes.byref(cfg), ctypes.byref(opts), ctypes.byref(h)),
+                  'a3c_engine_create_opts')
+        elif game == 'synth':
             check(lib().a3c_engine_create(ctypes.byref(cfg), ctypes.byref(h)), 'a3c_engine_create')
         else:
             check(lib().a3c_engine_create_ex(ctypes.byref(cfg), GAME_IDS[game], ctypes.byref(h)), 'a3c_engine_create_ex')
@@ -151,7 +164,12 @@ class Engine:
             acts = dict(act_l1=_view(b.act_l1, (n * E, 6400), torch.float32),
                         act_l2=_view(b.act_l2, (n * E, 2592), torch.float32),
                         act_l3=_view(b.act_l3, (n * E, 256), torch.float32))
-        return dict(**lstm, **acts, actions=_view(b.actions, (n, E), torch.int32),
+        sarsa = {}
+        if self.sarsa:      # the action drawn for the bootstrap state s_n by the slot's last gradient
+            p = ctypes.c_void_p()
+            check(lib().a3c_engine_slot_boot_actions(self._h, k, ctypes.byref(p)), 'a3c_engine_slot_boot_actions')
+            sarsa = dict(boot_actions=_view(p.value, (E,), torch.int32))
+        return dict(**lstm, **acts, **sarsa, actions=_view(b.actions, (n, E), torch.int32),
                     rewards=_view(b.rewards, (n, E), torch.float32),
                     terminals=_view(b.terminals, (n, E), torch.uint8),
                     z=_view(b.z, (n + 1, E, self.zs), torch.float32),

@@ -375,5 +375,40 @@ def nstep_q_target(rewards, terminals, q_boot, A, discount=0.99, q_sel=None):
     return out
 
 
+def boot_action(q, eps, A, tau, env_id_base=0, seed=123):
+    """The epsilon-greedy draw of env e at step tau from its Q row (a3c_boot_action): q [E,zs] (A live
+    columns), eps [E]; returns boot_actions [E] int32."""
+    _dev(q, torch.float32, 'q')
+    _dev(eps, torch.float32, 'eps')
+    if q.dim() != 2 or eps.dim() != 1 or int(eps.shape[0]) != int(q.shape[0]):
+        raise ValueError('expected q [E, zs] and eps [E]')
+    E = int(q.shape[0])
+    out = torch.empty((E,), dtype=torch.int32, device=q.device)
+    check(lib().a3c_boot_action(ptr(q), ptr(eps), E, int(A), int(q.shape[1]), int(tau), int(env_id_base), int(seed),
+                                ptr(out), stream_handle()), 'a3c_boot_action')
+    return out
+
+
+def sarsa_target(rewards, terminals, actions, boot_actions, q_target, A, discount=0.99, nstep=False):
+    """Sarsa targets [n,E] (a3c_sarsa_target): rewards / terminals / actions [n,E] of the rollout,
+    boot_actions [E] the action of the bootstrap state s_n, q_target the target rows [n*E,zs] of s_1..s_n, or
+    with nstep [E,zs] of s_n (A live columns)."""
+    _dev(rewards, torch.float32, 'rewards')
+    _dev(terminals, torch.uint8, 'terminals')
+    _dev(actions, torch.int32, 'actions')
+    _dev(boot_actions, torch.int32, 'boot_actions')
+    _dev(q_target, torch.float32, 'q_target')
+    n, E = int(rewards.shape[0]), int(rewards.shape[1])
+    rows = E if nstep else n * E
+    if (tuple(terminals.shape) != (n, E) or tuple(actions.shape) != (n, E) or tuple(boot_actions.shape) != (E,) or
+            q_target.dim() != 2 or int(q_target.shape[0]) != rows):
+        raise ValueError('expected rewards / terminals / actions [n, E], boot_actions [E] and q_target [%d, zs]' % rows)
+    out = torch.empty((n, E), dtype=torch.float32, device=rewards.device)
+    check(lib().a3c_sarsa_target(ptr(rewards), ptr(terminals), ptr(actions), ptr(boot_actions), ptr(q_target),
+                                 1 if nstep else 0, n, E, int(A), int(q_target.shape[1]), float(discount), ptr(out),
+                                 stream_handle()), 'a3c_sarsa_target')
+    return out
+
+
 def copy_params(dst, src):
     check(lib().a3c_copy_params(ptr(dst), ptr(src), int(src.numel()), stream_handle()), 'a3c_copy_params')

@@ -187,6 +187,44 @@ int a3c_nstep_q_target(const float* rewards, const uint8_t* terminals, const flo
                        float* target, void* stream);
 
 /* ----------------------------------------------------------------------------
+ * K7d  Sarsa: the bootstrap state's action (asynchronous one-step Sarsa, §4 and Algorithm S1 of the
+ *     A3C paper with the target r + gamma Q(s', a'; theta^-), a' the action the behaviour policy
+ *     takes in s').  The epsilon-greedy draw the rollout's head makes for env e at step tau
+ *     (agent.py:141-151), from the Q rows q [E][zs] (A live columns):
+ *       x = philox4x32(lo32(tau), hi32(tau), env_id_base + e, P_ACTION = 1; key = seed)
+ *       boot_actions[e] = u01(x.x) < eps[e] ? x.y % A : the first argmax_a q[e][a]
+ *     The engine (a3c_engine_opts.sarsa) draws it at tau = the slot's rollout-start tau + n with the
+ *     slot's own parameters' rows of s_n and the schedule's epsilon of that step: rollout k+1's own
+ *     first draw whenever the parameters did not change in between, and wherever u < eps.
+ *     A3C_ERR_INVALID: a null pointer, E < 1, A < 1, zs < A.
+ * -------------------------------------------------------------------------- */
+int a3c_boot_action(const float* q, const float* eps, int64_t E, int A, int zs, int64_t tau,
+                    int env_id_base, uint64_t seed, int32_t* boot_actions, void* stream);
+
+/* ----------------------------------------------------------------------------
+ * K7e  Sarsa targets (one-step Sarsa, §4 of the A3C paper; nstep: its n-step form, Algorithm S2's
+ *     returns bootstrapped at the taken action) over [n][E] in float64, contraction off, from the
+ *     rollout's clipped rewards, terminals and actions [n][E], the bootstrap state's action
+ *     boot_actions [E] (a3c_boot_action) and the target network's Q rows q_target (A live columns,
+ *     row stride zs).  An action word w is used as the column (uint32)w % A, so any word reads
+ *     inside its row.
+ *       nstep = 0, q_target [n*E][zs] the rows of s_1 .. s_n, b = i*E + e:
+ *         a' = i < n-1 ? actions[i+1][e] : boot_actions[e]
+ *         target[b] = (float)((1 - terminals[b]) * discount * (double)q_target[b][a'] + rewards[b])
+ *       nstep = 1, q_target [E][zs] the rows of s_n:
+ *         R = (double)q_target[e][boot_actions[e]]
+ *         for i = n-1 .. 0:  if terminals[i][e]: R = 0;  R = rewards[i][e] + discount*R;
+ *                            target[i][e] = (float)R
+ *     After a terminal, actions[i+1] belongs to the new game and (1 - terminal) removes it.  n = 1:
+ *     both forms are the same operations.  With a' the argmax of the same rows the targets are
+ *     a3c_td_target's / a3c_nstep_q_target's to the last bit.
+ *     A3C_ERR_INVALID: a null pointer, nstep not 0 or 1, n < 1, E < 1, A < 1, zs < A.
+ * -------------------------------------------------------------------------- */
+int a3c_sarsa_target(const float* rewards, const uint8_t* terminals, const int32_t* actions,
+                     const int32_t* boot_actions, const float* q_target, int nstep, int n, int64_t E,
+                     int A, int zs, double discount, float* target, void* stream);
+
+/* ----------------------------------------------------------------------------
  * K8+K9  loss + backward (network.py:81-94 with the SURVEY §8 A11 fixes / agent.py:306-317).
  *  target: a3c -> R (n-step return); q -> TD target.
  *  a3c loss per sample  -log pi(a)*stopgrad(R-V) - beta*H + (R-V)^2/2, summed over B
@@ -404,6 +442,25 @@ int a3c_engine_create(const a3c_engine_config* cfg, a3c_engine** out);
  * for an unknown game, and for Catch with num_frames < 640, action_size != 3, start_lives != 0,
  * frame84 or external_env; nothing is allocated or launched then. */
 int a3c_engine_create_ex(const a3c_engine_config* cfg, int game, a3c_engine** out);
+/* Options that a3c_engine_config, whose size and layout callers hold, has no room for: a struct that
+ * starts with its own size, so later options append and a caller built against a shorter one stays
+ * valid (fields past `size` take their defaults).
+ *  game:  A3C_GAME_*, as a3c_engine_create_ex's argument.
+ *  sarsa: q only.  1 = asynchronous Sarsa (§4 of the A3C paper, beside Algorithm S1): the target of a
+ *         transition is r + discount * Q(s', a'; theta^-) at the action a' the behaviour policy takes
+ *         in s' -- the rollout's next action, and for the last step the draw the rollout's head would
+ *         make in s_n (a3c_boot_action, with the slot's own parameters) -- instead of the maximum
+ *         (a3c_sarsa_target).  With cfg.q_nstep = 1: n-step Sarsa, the n-step returns bootstrapped
+ *         from Q(s_n, a_n; theta^-).  0 (default): Q-learning, the launches without it.  A
+ *         hyperparameter (not in the checkpoint's state; play does not read it).
+ *         python async-rl-tensorflow_amd/main.py --mode engine --algo q --sarsa true.
+ * a3c_engine_create and a3c_engine_create_ex are a3c_engine_create_opts with the defaults (and the
+ * game).  A3C_ERR_INVALID, beside a3c_engine_create_ex's cases: opts NULL or opts->size smaller than
+ * the fields read here, sarsa not 0 or 1, sarsa with algo a3c, sarsa with double_q (double Q picks
+ * the argmax, Sarsa the taken action); nothing is allocated or launched then. */
+typedef struct a3c_engine_opts { int size; int game; int sarsa; } a3c_engine_opts;
+void a3c_engine_opts_default(a3c_engine_opts* opts);   /* size = sizeof, game = A3C_GAME_SYNTH, sarsa = 0 */
+int a3c_engine_create_opts(const a3c_engine_config* cfg, const a3c_engine_opts* opts, a3c_engine** out);
 int a3c_engine_destroy(a3c_engine* eng);
 /* fill the frame pool, reset the envs (new_random_game, environment.py:35-40), fill each
  * history with 4 copies of the first screen (agent.py:37-38) and initialise params
@@ -564,6 +621,10 @@ int a3c_engine_get_buffers(a3c_engine* eng, a3c_engine_buffers* out);
 /* same, with the rollout buffers (actions .. act_l3) of slot 0 or 1 (overlap: rollout k
  * writes slot k & 1); get_buffers == slot 0 */
 int a3c_engine_slot_buffers(a3c_engine* eng, int slot, a3c_engine_buffers* out);
+/* Sarsa engines (a3c_engine_opts.sarsa): *out = the slot's boot_actions [E] i32, the action drawn for
+ * the bootstrap state s_n by the slot's last gradient (a3c_boot_action's rule; transient: written and
+ * read inside one gradient, not part of the saved state).  A3C_ERR_INVALID without sarsa. */
+int a3c_engine_slot_boot_actions(a3c_engine* eng, int slot, int32_t** out);
 
 /* ----------------------------------------------------------------------------
  * Evaluation: Agent.play (agent.py:351-391) on the engine, without learning.  The engine's E envs
