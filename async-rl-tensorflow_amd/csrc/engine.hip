@@ -125,7 +125,13 @@ struct a3c_engine {
   float* lws;              // LSTM BPTT workspace (a3c_lstm_ws_floats)
   float* ldh;              // LSTM: dL/dh_t from the heads [nE][U]
   double* opt_part;
-  float* sched;            // [0] lr, [1] target-sync flag (device)
+  float* sched;            // [0] lr, [1] target-sync flag, [2] Adam's alpha; the doubles at [4..7]: adam_pw (device)
+  // the optimizer (a3c_engine_set_optimizer): with Adam `mom` holds m, `ms` holds v
+  int opt_kind;            // A3C_OPT_*
+  double adam_b1, adam_b2;
+  float adam_eps;
+  double* adam_pw;         // [2] beta1^t, beta2^t of the t steps applied (inside sched's allocation)
+  int shard_nranks;        // nranks of the a3c_engine_apply_shard calls since the last commit
   double* stats;           // [A3C_STATS_N] train_with_summary aggregates since the last read
   double* ep_acc;          // [E] running episode reward per env (agent.py:91-98)
   TensorTab tt;
@@ -458,6 +464,7 @@ extern "C" int a3c_engine_create_opts(const a3c_engine_config* cfg, const a3c_en
   ALLOC(e->fcpart, (int64_t)FC_NS * E * FC * 4);
   ALLOC(e->opt_part, (int64_t)SS_MAX_BLOCKS * 8);
   ALLOC(e->sched, 64);
+  e->adam_pw = (double*)(e->sched + 4);
   ALLOC(e->stats, A3C_STATS_N * 8);
   ALLOC(e->ep_acc, E * 8);
   // last: the other buffers keep the placement they had before the ReLU bits existed
@@ -686,6 +693,13 @@ static OptParams opt_params(const a3c_engine* e, const Slot& sl) {
   op.rho = c.decay;
   op.momentum = c.momentum;
   op.eps = c.epsilon;
+  if (e->opt_kind == A3C_OPT_ADAM) {
+    op.adam = 1;
+    op.pw = e->adam_pw;
+    op.beta1 = e->adam_b1;
+    op.beta2 = e->adam_b2;
+    op.eps = e->adam_eps;
+  }
   return op;
 }
 
@@ -1194,7 +1208,8 @@ static int enqueue_rollout_grad(a3c_engine* e, hipStream_t s) {
   return rc ? rc : enqueue_grad(e, e->slot[0], s);
 }
 
-// RMSProp apply (lr from the schedule computed on device), target sync (q) and the counter
+// RMSProp (or Adam, opt_params: its alpha from the same schedule) apply (lr from the schedule computed
+// on device), target sync (q) and the counter
 // advance in one launch; world_size == 1: the per-tensor clip as well.  Overlap: then the
 // parameter snapshot of the rollout that will use slot `snap` (the slot just back-propagated).
 static int enqueue_apply(a3c_engine* e, int snap, hipStream_t s) {
@@ -1249,6 +1264,74 @@ static int run_graph(a3c_engine* e, int gi, int what, int slot, hipStream_t s) {
   return 0;
 }
 
+// the optimizer's slots as TF1 creates them: RMSProp rms = 1, mom = 0; Adam m = v = 0 and the
+// products beta1^0 = beta2^0 = 1
+static int init_slots(a3c_engine* e, hipStream_t s) {
+  const int64_t total = e->L.total;
+  if (e->opt_kind == A3C_OPT_ADAM) {
+    static const double one[2] = {1.0, 1.0};
+    A3C_CHECK(hipMemsetAsync(e->ms, 0, total * 4, s));
+    A3C_CHECK(hipMemcpyAsync(e->adam_pw, one, sizeof(one), hipMemcpyHostToDevice, s));
+  } else if (int rc = a3c_fill_launch(e->ms, total, 1.0f, s)) {   // TF1 RMSProp rms slot init = 1
+    return rc;
+  }
+  A3C_CHECK(hipMemsetAsync(e->mom, 0, total * 4, s));
+  return 0;
+}
+
+extern "C" int a3c_engine_set_optimizer(a3c_engine* e, int kind, double beta1, double beta2, double eps) {
+  if (kind != A3C_OPT_RMSPROP && kind != A3C_OPT_ADAM)
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_set_optimizer", "unknown optimizer kind");
+  if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0))
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_set_optimizer", "beta1 and beta2 must be in [0, 1)");
+  if (!(eps > 0.0)) return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_set_optimizer", "eps must be > 0");
+  if (!e) return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_set_optimizer", "null");
+  if (e->grad_ready && !e->grad_applied)
+    return a3c_set_error(A3C_ERR_STATE, "a3c_engine_set_optimizer", "a gradient is pending: apply it first");
+  A3C_CHECK(hipDeviceSynchronize());      // (the engine's streams: nothing in flight reads the slots)
+  e->opt_kind = kind;
+  e->adam_b1 = beta1;
+  e->adam_b2 = beta2;
+  e->adam_eps = (float)eps;
+  e->shard_nranks = 0;
+  // the captured graphs hold the other optimizer's launches
+  for (int i = 0; i < NGRAPH; ++i)
+    if (e->captured[i]) {
+      (void)hipGraphExecDestroy(e->gexec[i]);
+      (void)hipGraphDestroy(e->graph[i]);
+      e->captured[i] = false;
+    }
+  if (int rc = init_slots(e, nullptr)) return rc;
+  A3C_CHECK(hipStreamSynchronize(nullptr));
+  return 0;
+}
+
+extern "C" int a3c_engine_adam_powers(a3c_engine* e, double* beta1_power, double* beta2_power, void* stream) {
+  if (!e || !beta1_power || !beta2_power) return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_adam_powers", "null");
+  double pw[2] = {1.0, 1.0};
+  if (e->opt_kind == A3C_OPT_ADAM) {
+    A3C_CHECK(hipStreamSynchronize((hipStream_t)stream));
+    A3C_CHECK(hipMemcpy(pw, e->adam_pw, sizeof(pw), hipMemcpyDeviceToHost));
+  }
+  *beta1_power = pw[0];
+  *beta2_power = pw[1];
+  return 0;
+}
+
+extern "C" int a3c_engine_set_adam_powers(a3c_engine* e, double beta1_power, double beta2_power, void* stream) {
+  if (!e) return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_set_adam_powers", "null");
+  if (e->opt_kind != A3C_OPT_ADAM)
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_set_adam_powers", "the engine's optimizer is not Adam");
+  if (!(beta1_power >= 0.0 && beta1_power <= 1.0) || !(beta2_power >= 0.0 && beta2_power <= 1.0))
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_set_adam_powers", "a product of betas lies in [0, 1]");
+  if (e->grad_ready && !e->grad_applied)
+    return a3c_set_error(A3C_ERR_STATE, "a3c_engine_set_adam_powers", "a gradient is pending: apply it first");
+  const double pw[2] = {beta1_power, beta2_power};
+  A3C_CHECK(hipStreamSynchronize((hipStream_t)stream));
+  A3C_CHECK(hipMemcpy(e->adam_pw, pw, sizeof(pw), hipMemcpyHostToDevice));
+  return 0;
+}
+
 extern "C" int a3c_engine_reset(a3c_engine* e, const float* host_params, void* stream) {
   if (!e) return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_reset", "null");
   hipStream_t s = (hipStream_t)stream;
@@ -1258,9 +1341,8 @@ extern "C" int a3c_engine_reset(a3c_engine* e, const float* host_params, void* s
     A3C_CHECK(hipStreamSynchronize(s));
   }
   A3C_CHECK(hipMemcpyAsync(e->tparams, e->params, L.total * 4, hipMemcpyDeviceToDevice, s));
-  int rc = a3c_fill_launch(e->ms, L.total, 1.0f, s);   // TF1 RMSProp rms slot init = 1
+  int rc = init_slots(e, s);
   if (rc) return rc;
-  A3C_CHECK(hipMemsetAsync(e->mom, 0, L.total * 4, s));
   A3C_CHECK(hipMemsetAsync(e->grads, 0, L.total * 4, s));
   A3C_CHECK(hipMemsetAsync(e->loss, 0, 64, s));
   A3C_CHECK(hipMemsetAsync(e->ring, 0, (size_t)e->E * e->R * PLANE, s));
@@ -1440,6 +1522,10 @@ extern "C" int a3c_engine_apply_shard(a3c_engine* e, const float* grads_by_rank,
   if (e->cfg.world_size == 1)   // one rank: the per-worker clip has not run (a3c_engine_apply fuses it)
     return a3c_set_error(A3C_ERR_STATE, "a3c_engine_apply_shard", "world_size 1 engines use a3c_engine_apply");
   const a3c_engine_config& c = e->cfg;
+  e->shard_nranks = nranks;
+  if (e->opt_kind == A3C_OPT_ADAM)
+    return a3c_apply_seq_adam_launch(e->params + lo, e->ms + lo, e->mom + lo, grads_by_rank, nranks, n, e->sched,
+                                     e->adam_pw, e->adam_b1, e->adam_b2, e->adam_eps, w_out, (hipStream_t)stream);
   return a3c_apply_seq_launch(e->params + lo, e->ms + lo, e->mom + lo, grads_by_rank, nranks, n, e->sched, c.decay,
                               c.momentum, c.epsilon, w_out, (hipStream_t)stream);
 }
@@ -1449,10 +1535,17 @@ extern "C" int a3c_engine_apply_shard(a3c_engine* e, const float* grads_by_rank,
 extern "C" int a3c_engine_apply_commit(a3c_engine* e, const float* params_src, void* stream) {
   if (!e) return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_apply_commit", "null");
   if (!e->grad_ready || e->grad_applied) return 0;
+  if (e->opt_kind == A3C_OPT_ADAM && e->shard_nranks == 0)   // (a commit alone, Hogwild's path: no step count to advance)
+    return a3c_set_error(A3C_ERR_STATE, "a3c_engine_apply_commit", "Adam: a3c_engine_apply_shard of this gradient first");
   const OptParams op = opt_params(e, e->slot[0]);
   float* snap = e->overlap ? e->slot[(int)(e->iter & 1)].P : nullptr;
-  int rc = a3c_commit_launch(params_src ? params_src : e->params, e->L.total, e->params, snap, op.target, e->sched,
-                             e->counters, op.dtau, op.step_add, (hipStream_t)stream);
+  int rc = e->opt_kind == A3C_OPT_ADAM
+               ? a3c_commit_adam_launch(params_src ? params_src : e->params, e->L.total, e->params, snap, op.target,
+                                        e->sched, e->counters, op.dtau, op.step_add, e->adam_pw, e->adam_b1, e->adam_b2,
+                                        e->shard_nranks, (hipStream_t)stream)
+               : a3c_commit_launch(params_src ? params_src : e->params, e->L.total, e->params, snap, op.target, e->sched,
+                                   e->counters, op.dtau, op.step_add, (hipStream_t)stream);
+  e->shard_nranks = 0;
   e->grad_applied = rc == 0;
   return rc;
 }
@@ -1636,6 +1729,7 @@ static std::vector<StateRegion> state_regions(const a3c_engine* e) {
   const int64_t T = e->L.total, E = e->E, nE = e->nE, zs = e->L.zs;
   auto add = [&](const void* p, int64_t b) { r.push_back({const_cast<void*>(p), (size_t)b}); };
   add(e->params, T * 4); add(e->tparams, T * 4); add(e->ms, T * 4); add(e->mom, T * 4);
+  if (e->opt_kind == A3C_OPT_ADAM) add(e->adam_pw, 16);   // (another size than an RMSProp engine's: not interchangeable)
   add(e->counters, 64); add(e->loss, 64); add(e->stats, A3C_STATS_N * 8); add(e->ep_acc, E * 8);
   add(e->ring, E * e->R * PLANE);
   add(e->env.episode, 2 * E * 4); add(e->env.ep_step, 2 * E * 4); add(e->env.ep_len, 2 * E * 4);

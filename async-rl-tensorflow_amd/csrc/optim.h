@@ -47,24 +47,47 @@ struct OptParams {
   // apply / clip pass over float4 indices [q0, q1) only (q1 == 0: the whole flat vector) -- the
   // split exchange clips the fc / head tensors before the conv backward, the conv tensors after
   int64_t q0, q1;
+  // Adam (adam == 0: RMSProp and none of this is read).  mom holds m, ms holds v, eps is
+  // Adam's.  pw (engine; nullptr in the stand-alone op, whose caller passes alpha as lr): the fp64
+  // running products {beta1^t, beta2^t} of the t steps applied so far.  opt_schedule writes
+  // sched[2] = alpha of step t + 1; the apply reads it and its last thread advances the products.
+  int adam;
+  double* pw;
+  double beta1, beta2;
 };
 
 int a3c_make_tab(int n, const int64_t* off, const int64_t* size, int64_t total, TensorTab* tt);
 
-// the lr schedule and target-sync decision from the device step counter (one thread; k_sumsq's
-// block 0, or the backward's finalize when it produces the partials itself)
-__device__ inline void opt_schedule(const OptParams& op) {
-  if (!op.sched || !op.step_ptr) return;
+// TF1 ApplyAdam's step size from the schedule's float lr and the products beta1^t, beta2^t of the
+// step being applied, in fp64
+__device__ inline float adam_alpha(float lr, double p1, double p2) {
+  return (float)((double)lr * sqrt(1.0 - p2) / (1.0 - p1));
+}
+
+// the lr schedule and target-sync decision from the device step counter (one thread); returns the
+// float lr it wrote to sched[0] (0 without a schedule)
+__device__ inline float opt_schedule_lr(const OptParams& op) {
+  if (!op.sched || !op.step_ptr) return 0.f;
   const int64_t g0 = *op.step_ptr;
   const double step = op.wstep_ptr ? (double)(*op.wstep_ptr + (*op.tau_ptr - op.tau0) + op.n_step - 1)
                                    : (double)(g0 + op.step_add);
   // agent.py:393-395; the reference never trains past max_step (agent.py:46,55-57), so the
   // schedule is clamped at 0 there instead of turning negative (RMSProp would ascend)
   const double lr = (double)(op.max_step - step + 1.0) / (double)op.max_step * op.lr0;
-  op.sched[0] = (float)(lr > 0.0 ? lr : 0.0);
+  const float lrf = (float)(lr > 0.0 ? lr : 0.0);
+  op.sched[0] = lrf;
   int copy = 0;
   if (op.target_period > 0) copy = (g0 + op.step_add + 1) / op.target_period != (g0 + 1) / op.target_period;
   op.sched[1] = copy ? 1.0f : 0.0f;
+  return lrf;
+}
+
+// the engine's schedule (the backward's finalize, which produces the partials itself): the above,
+// and with Adam the step size of the step the coming apply takes.  k_sumsq keeps opt_schedule_lr:
+// the stand-alone ops have no schedule, and their callers pass alpha
+__device__ inline void opt_schedule(const OptParams& op) {
+  const float lr = opt_schedule_lr(op);      // (passed along: no word of sched is read here)
+  if (op.pw && op.sched && op.step_ptr) op.sched[2] = adam_alpha(lr, op.pw[0] * op.beta1, op.pw[1] * op.beta2);
 }
 
 // fp64 sum of squares of chunk c (SS_CHUNK elements) of tensor t, by one 256-thread block into
@@ -98,6 +121,15 @@ int a3c_fill_launch(float* p, int64_t n, float v, hipStream_t s);
 // partitioned PS: nranks sequential RMSProp steps of the owned range (lr = sched[0]) -> w_out
 int a3c_apply_seq_launch(const float* w, float* ms, float* mom, const float* g, int nranks, int64_t n,
                          const float* sched, float rho, float momentum, float eps, float* w_out, hipStream_t s);
+// Adam form: ms holds v, mom holds m; step q's alpha from the products pw advanced q + 1 times
+int a3c_apply_seq_adam_launch(const float* w, float* v, float* m, const float* g, int nranks, int64_t n,
+                              const float* sched, const double* pw, double beta1, double beta2, float eps,
+                              float* w_out, hipStream_t s);
 // params / snapshot / target (if sched[1]) <- src, counters += (dtau, dstep)
 int a3c_commit_launch(const float* src, int64_t total, float* params, float* snap, float* target, const float* sched,
                       int64_t* counters, int64_t dtau, int64_t dstep, hipStream_t s);
+// ... and the Adam products pw advance by nadv steps (the commit behind a3c_apply_seq_adam_launch)
+int a3c_commit_adam_launch(const float* src, int64_t total, float* params, float* snap, float* target,
+                           const float* sched, int64_t* counters, int64_t dtau, int64_t dstep, double* pw,
+                           double beta1, double beta2, int nadv, hipStream_t s);
+#define A3C_SEQ_MAX_RANKS 64   // sequential steps one k_apply_seq launch takes (its alpha table in LDS)

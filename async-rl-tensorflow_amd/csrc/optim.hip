@@ -9,6 +9,7 @@
 //          block 0 advances the engine counters at the end (nothing in this launch reads them).
 // Element math is written with contraction off so it matches the numpy oracle bit for bit on
 // equal gradients.
+// The Adam forms of k_apply / k_apply_seq / k_commit (TF1 ApplyAdam) are at the end of the file.
 #include <cstring>
 #include "optim.h"
 
@@ -37,7 +38,7 @@ __global__ void __launch_bounds__(256) k_sumsq(const float* __restrict__ g, Tens
   int t = 0;
   while (t + 1 < tt.n && (int)blockIdx.x >= tt.pb_first[t + 1]) ++t;
   sumsq_chunk(g, tt, t, blockIdx.x - tt.pb_first[t], part, blockIdx.x);
-  if (blockIdx.x == 0 && threadIdx.x == 0) opt_schedule(op);
+  if (blockIdx.x == 0 && threadIdx.x == 0) opt_schedule_lr(op);
 }
 
 __global__ void __launch_bounds__(256) k_apply(float* __restrict__ w, float* __restrict__ ms,
@@ -204,12 +205,18 @@ int a3c_sumsq_launch(const float* grads, const TensorTab& tt, const OptParams& o
   return 0;
 }
 
+// the Adam kernels are templates defined at the end of this file: their instantiations are emitted
+// behind every kernel the file had, which keep their places in the code object
+static int apply_adam_launch(float* w, float* v, float* m, float* grads, const TensorTab& tt, const OptParams& op,
+                             const double* part, float* sumsq_out, int blocks, hipStream_t s);
+
 int a3c_apply_launch(float* w, float* ms, float* mom, float* grads, const TensorTab& tt, const OptParams& op,
                      const double* part, float* sumsq_out, hipStream_t s) {
   const int64_t n4 = op.q1 > 0 ? op.q1 - op.q0 : tt.total >> 2;
   int blocks = (int)((n4 + 255) / 256);
   if (blocks > 1024) blocks = 1024;
   if (blocks < 1) blocks = 1;
+  if (op.adam && (op.mode & OPT_APPLY)) return apply_adam_launch(w, ms, mom, grads, tt, op, part, sumsq_out, blocks, s);
   hipLaunchKernelGGL(k_apply, dim3(blocks), dim3(256), 0, s, w, ms, mom, grads, tt, part, op, sumsq_out);
   A3C_CHECK(hipGetLastError());
   return 0;
@@ -347,6 +354,205 @@ extern "C" int a3c_ipc_open(const void* handle64, void** out) {
 extern "C" int a3c_ipc_close(void* p) {
   if (p) A3C_CHECK(hipIpcCloseMemHandle(p));
   return 0;
+}
+
+// ---- Adam (TF1 ApplyAdam) ---------------------------------------------------------
+// m = m + (g - m)(1 - beta1); v = v + (g^2 - v)(1 - beta2); w = w - m alpha / (sqrt(v) + eps), with
+// alpha = lr sqrt(1 - beta2^t) / (1 - beta1^t) formed in fp64 by opt_schedule (engine: sched[2]) or by
+// the caller (op.lr).  The kernels below are k_apply / k_apply_seq / k_commit with that element
+// math: the same fold of the partials, the same clip, one float4 pass over the same arrays (mom is
+// m, ms is v).  OPT is the optimizer (1: Adam, the only instantiation); they are templates so that
+// they are emitted behind the kernels above.
+template <int OPT>
+__global__ void __launch_bounds__(256) k_apply_opt(float* __restrict__ w, float* __restrict__ vs,
+                                                   float* __restrict__ mo, float* __restrict__ grads, TensorTab tt,
+                                                   const double* __restrict__ part, OptParams op,
+                                                   float* __restrict__ sumsq_out) {
+#pragma clang fp contract(off)
+  static_assert(OPT == 1, "Adam");
+  WGLOG(9);
+  __shared__ float cm[A3C_MAX_TENSORS];
+  __shared__ float s_alpha, s_copy;
+  __shared__ double red[A3C_MAX_TENSORS];
+  {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    for (int t = wv; t < tt.n; t += 4) {
+      double v = 0.0;
+      for (int b = lane; b < tt.pb_count[t]; b += 64) v += part[tt.pb_first[t] + b];
+      v = wave_sum_d(v);
+      if (lane == 0) red[t] = v;
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < tt.n) {
+    const float ssf = (float)red[threadIdx.x];
+    if (blockIdx.x == 0 && sumsq_out) sumsq_out[threadIdx.x] = ssf;
+    float m = 1.0f;
+    if (op.clip > 0.f && (op.mode & OPT_CLIP)) {
+      const float inv = ssf > 0.f ? 1.0f / sqrtf(ssf) : INFINITY;
+      m = fminf(inv, 1.0f / op.clip);      // tf.clip_by_norm: t * clip * min(rsqrt(ss), 1/clip)
+    }
+    cm[threadIdx.x] = m;
+  }
+  if (threadIdx.x == 0) {
+    s_alpha = op.sched ? op.sched[2] : op.lr;
+    s_copy = (op.sched && op.target) ? op.sched[1] : 0.f;
+  }
+  __syncthreads();
+  const float alpha = s_alpha;
+  const bool copy = s_copy != 0.f;
+  const bool clip = op.clip > 0.f && (op.mode & OPT_CLIP);
+  const float omb1 = 1.0f - (float)op.beta1, omb2 = 1.0f - (float)op.beta2;
+  const int64_t qe = op.q1 > 0 ? op.q1 : tt.total >> 2;
+  for (int64_t q = (op.q1 > 0 ? op.q0 : 0) + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < qe;
+       q += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t i = 4 * q;
+    int t = 0;
+    while (t + 1 < tt.n && i >= tt.off[t + 1]) ++t;     // padding after tensor t has zero grads
+    f32x4 g = *(const f32x4*)(grads + i);
+    if (clip) {
+      const float c = cm[t];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) g[k] = (g[k] * op.clip) * c;
+    }
+    f32x4 v = *(const f32x4*)(vs + i);
+    f32x4 m = *(const f32x4*)(mo + i);
+    f32x4 wv = *(const f32x4*)(w + i);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      m[k] = m[k] + (g[k] - m[k]) * omb1;
+      v[k] = v[k] + (g[k] * g[k] - v[k]) * omb2;
+      wv[k] = wv[k] - (m[k] * alpha) / (sqrtf(v[k]) + op.eps);
+    }
+    *(f32x4*)(vs + i) = v;
+    *(f32x4*)(mo + i) = m;
+    *(f32x4*)(w + i) = wv;
+    if (copy) *(f32x4*)(op.target + i) = wv;
+    if (op.snap) *(f32x4*)(op.snap + i) = wv;
+  }
+  // nothing in this launch reads the counters or the products: the next schedule does
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    if (op.counters) {
+      if (op.dtau) op.counters[0] += op.dtau;   // overlap mode: the rollout owns tau
+      op.counters[1] += op.step_add;
+    }
+    if (op.pw) {
+      op.pw[0] *= op.beta1;
+      op.pw[1] *= op.beta2;
+    }
+  }
+}
+
+// the partitioned PS's nranks sequential steps (k_apply_seq): step q's alpha from the products
+// advanced q + 1 times, one table per block in LDS; the products themselves advance in the commit
+template <int OPT>
+__global__ void __launch_bounds__(256) k_apply_seq_opt(const float* __restrict__ w, float* __restrict__ vs,
+                                                       float* __restrict__ mo, const float* __restrict__ g,
+                                                       int nranks, int64_t n, const float* __restrict__ sched,
+                                                       const double* __restrict__ pw, double beta1, double beta2,
+                                                       float eps, float* __restrict__ w_out) {
+#pragma clang fp contract(off)
+  static_assert(OPT == 1, "Adam");
+  __shared__ float s_alpha[A3C_SEQ_MAX_RANKS];
+  if (threadIdx.x == 0) {
+    const float lr = sched[0];
+    double p1 = pw[0], p2 = pw[1];
+    for (int q = 0; q < nranks; ++q) {
+      p1 *= beta1;
+      p2 *= beta2;
+      s_alpha[q] = adam_alpha(lr, p1, p2);
+    }
+  }
+  __syncthreads();
+  const float omb1 = 1.0f - (float)beta1, omb2 = 1.0f - (float)beta2;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    float wv = w[i], v = vs[i], m = mo[i];
+    for (int q = 0; q < nranks; ++q) {
+      const float gi = g[(int64_t)q * n + i];
+      m = m + (gi - m) * omb1;
+      v = v + (gi * gi - v) * omb2;
+      wv = wv - (m * s_alpha[q]) / (sqrtf(v) + eps);
+    }
+    vs[i] = v;
+    mo[i] = m;
+    w_out[i] = wv;
+  }
+}
+
+template <int OPT>
+__global__ void __launch_bounds__(256) k_commit_opt(const float* __restrict__ src, int64_t n4, float* __restrict__ params,
+                                                    float* __restrict__ snap, float* __restrict__ target,
+                                                    const float* __restrict__ sched, int64_t* counters, int64_t dtau,
+                                                    int64_t dstep, double* pw, double beta1, double beta2, int nadv) {
+  static_assert(OPT == 1, "Adam");
+  const bool tsync = target && sched[1] != 0.f;
+  for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < n4; q += (int64_t)gridDim.x * blockDim.x) {
+    const f32x4 v = ((const f32x4*)src)[q];
+    if (src != params) ((f32x4*)params)[q] = v;
+    if (snap) ((f32x4*)snap)[q] = v;
+    if (tsync) ((f32x4*)target)[q] = v;
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    if (counters) {
+      if (dtau) counters[0] += dtau;     // (k_commit: tau only when this pass owns it)
+      counters[1] += dstep;
+    }
+    double p1 = pw[0], p2 = pw[1];
+    for (int q = 0; q < nadv; ++q) {
+      p1 *= beta1;
+      p2 *= beta2;
+    }
+    pw[0] = p1;
+    pw[1] = p2;
+  }
+}
+
+static int apply_adam_launch(float* w, float* v, float* m, float* grads, const TensorTab& tt, const OptParams& op,
+                             const double* part, float* sumsq_out, int blocks, hipStream_t s) {
+  hipLaunchKernelGGL(k_apply_opt<1>, dim3(blocks), dim3(256), 0, s, w, v, m, grads, tt, part, op, sumsq_out);
+  A3C_CHECK(hipGetLastError());
+  return 0;
+}
+
+int a3c_apply_seq_adam_launch(const float* w, float* v, float* m, const float* g, int nranks, int64_t n,
+                              const float* sched, const double* pw, double beta1, double beta2, float eps,
+                              float* w_out, hipStream_t s) {
+  if (nranks > A3C_SEQ_MAX_RANKS) return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_apply_shard", "too many ranks");
+  if (n <= 0) return 0;
+  const int64_t blocks = (n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024;
+  hipLaunchKernelGGL(k_apply_seq_opt<1>, dim3((unsigned)blocks), dim3(256), 0, s, w, v, m, g, nranks, n, sched, pw,
+                     beta1, beta2, eps, w_out);
+  A3C_CHECK(hipGetLastError());
+  return 0;
+}
+
+int a3c_commit_adam_launch(const float* src, int64_t total, float* params, float* snap, float* target,
+                           const float* sched, int64_t* counters, int64_t dtau, int64_t dstep, double* pw,
+                           double beta1, double beta2, int nadv, hipStream_t s) {
+  const int64_t n4 = total >> 2;
+  int64_t blocks = (n4 + 255) / 256;
+  blocks = blocks > 1024 ? 1024 : (blocks < 1 ? 1 : blocks);
+  hipLaunchKernelGGL(k_commit_opt<1>, dim3((unsigned)blocks), dim3(256), 0, s, src, n4, params, snap, target, sched,
+                     counters, dtau, dstep, pw, beta1, beta2, nadv);
+  A3C_CHECK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int a3c_clip_adam_apply(float* params, float* m, float* v, float* grads, int n_tensors,
+                                   const int64_t* offsets, const int64_t* sizes, float alpha, float beta1,
+                                   float beta2, float eps, float clip, float* sumsq_out, void* workspace,
+                                   void* stream) {
+  TensorTab tt;
+  if (!params || !m || !v || !grads || !workspace || !offsets || !sizes || n_tensors <= 0 ||
+      n_tensors > A3C_MAX_TENSORS || a3c_make_tab(n_tensors, offsets, sizes, tab_total(n_tensors, offsets, sizes), &tt))
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_clip_adam_apply", "bad argument (offsets must be 4-aligned, ascending)");
+  OptParams op = {};
+  op.mode = OPT_CLIP | OPT_APPLY; op.clip = clip; op.lr = alpha; op.eps = eps;
+  op.adam = 1; op.beta1 = beta1; op.beta2 = beta2;
+  hipStream_t s = (hipStream_t)stream;
+  int rc = a3c_sumsq_launch(grads, tt, op, (double*)workspace, s);
+  if (rc) return rc;
+  return a3c_apply_launch(params, v, m, grads, tt, op, (double*)workspace, sumsq_out, s);
 }
 
 #ifdef A3C_WGLOG

@@ -11,6 +11,7 @@ accepted but the TF ps/worker cluster is replaced by one process per GPU under t
   python main.py --mode engine --env_name Catch-v0 --iterations 1000   the learnable device game
   python main.py --mode engine --algo q --q_nstep true --n_step 5 --env_name Catch-v0   n-step Q-learning
   python main.py --mode engine --algo q --sarsa true --n_step 5 --env_name Catch-v0     Sarsa (--q_nstep true: n-step)
+  python main.py --mode engine --algo q --optimizer adam --env_name Catch-v0             shared Adam instead of RMSProp
   python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 main.py --mode engine
   python main.py --mode engine --is_train false --n_episode 100     evaluate the newest checkpoint
   python main.py --mode engine --is_train false --play_refill true  ... refilling finished envs (no waves)
@@ -46,6 +47,15 @@ def parse_flags(argv=None):
   p.add_argument('--epsilon', type=float, default=0.1)
   p.add_argument('--momentum', type=float, default=0.0)
   p.add_argument('--beta', type=float, default=0.01)
+  p.add_argument('--optimizer', choices=['rmsprop', 'adam'], default='rmsprop',
+                 help='the shared optimizer of --mode engine and --mode agent: rmsprop (the reference: TF ApplyRMSProp '
+                      'with --decay, --momentum, --epsilon) or adam (TF1 ApplyAdam with --adam_beta1, --adam_beta2, '
+                      '--adam_epsilon on the same learning-rate schedule; --decay, --momentum and --epsilon are '
+                      "RMSProp's and ignored by it; not with --update hogwild; DESIGN §4j)")
+  p.add_argument('--adam_beta1', type=float, default=0.9, help='--optimizer adam: beta1, in [0, 1)')
+  p.add_argument('--adam_beta2', type=float, default=0.999, help='--optimizer adam: beta2, in [0, 1)')
+  p.add_argument('--adam_epsilon', type=float, default=1e-8,
+                 help='--optimizer adam: epsilon, > 0, added to sqrt(v) as TF does')
   # Distributed (accepted for compatibility; torchrun provides RANK/WORLD_SIZE)
   p.add_argument('--ps_hosts', default='0.0.0.0:2222')
   p.add_argument('--worker_hosts', default='0.0.0.0:2223,0.0.0.0:2224')
@@ -136,7 +146,11 @@ def engine_options(flags):
     raise ValueError('--sarsa is a Q-learning option (its target is a Q value, DESIGN §4i): use it with --algo q')
   if flags.sarsa and flags.double_q:
     raise ValueError('--sarsa with --double_q: double Q picks the argmax, Sarsa the taken action (DESIGN §4i)')
-  kw = dict(lstm=bool(flags.lstm))
+  adam = adam_options(flags)
+  if adam and flags.update == 'hogwild':
+    raise ValueError('--optimizer adam with --update hogwild: the lock-free shards keep no shared step count for '
+                     "Adam's bias correction (DESIGN §4j): use --update overlap or sync")
+  kw = dict(lstm=bool(flags.lstm), **adam)
   if flags.gae_lambda != 1.0:
     kw['gae_lambda'] = float(flags.gae_lambda)
   if flags.double_q:
@@ -148,6 +162,16 @@ def engine_options(flags):
   if flags.dqn_type == 'nature':
     kw['dqn_type'] = 'nature'
   return kw
+
+
+def adam_options(flags):
+  """--optimizer adam as keyword arguments (Engine's; AdamOptimizer's without the adam_ prefix), {} for
+  rmsprop.  Pure; ValueError for a beta outside [0, 1) or an epsilon <= 0."""
+  if getattr(flags, 'optimizer', 'rmsprop') != 'adam':
+    return {}
+  from src.optim import check_adam
+  b1, b2, eps = check_adam(flags.adam_beta1, flags.adam_beta2, flags.adam_epsilon)
+  return dict(optimizer='adam', adam_beta1=b1, adam_beta2=b2, adam_epsilon=eps)
 
 
 def play_options(flags, world=None):
@@ -389,12 +413,15 @@ def run_agent(config, flags):
   from src import distributed as D
   from src.agent import Agent, Supervisor
   from src.environment import GymEnvironment
-  from src.optim import RMSPropOptimizer
+  from src.optim import AdamOptimizer, RMSPropOptimizer
+  adam = adam_options(flags)
   rank, world, local = D.init_from_env()
   torch.cuda.set_device(local)
   random.seed(flags.random_seed + rank)
   env = GymEnvironment(config)
   optimizer = RMSPropOptimizer(None, decay=0.99, momentum=0, epsilon=0.1)     # main.py:64-65
+  if adam:
+    optimizer = AdamOptimizer(None, beta1=adam['adam_beta1'], beta2=adam['adam_beta2'], epsilon=adam['adam_epsilon'])
   agent = Agent(config, env, optimizer)
   agent.ep_end = random.sample([0.1, 0.01, 0.5], 1)[0]                        # main.py:68
   if world > 1:

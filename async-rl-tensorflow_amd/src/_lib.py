@@ -23,6 +23,8 @@ A3C_TRUNK_NATURE = 1
 A3C_LSTM_UNITS = 256
 A3C_GAME_SYNTH = 0   # the synthetic Atari stand-in
 A3C_GAME_CATCH = 1   # Catch (include/a3c_hip.h)
+A3C_OPT_RMSPROP = 0  # the engine's optimizer (a3c_engine_set_optimizer)
+A3C_OPT_ADAM = 1
 MAX_TENSORS = 16
 
 c_int, c_i64, c_u64, c_float, c_double, c_void_p = (ctypes.c_int, ctypes.c_int64, ctypes.c_uint64,
@@ -124,6 +126,9 @@ SIGNATURES = {
     'a3c_clip_rmsprop_apply': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.POINTER(c_i64),
                                        ctypes.POINTER(c_i64), c_float, c_float, c_float, c_float, c_float,
                                        c_void_p, c_void_p, c_void_p]),
+    'a3c_clip_adam_apply': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.POINTER(c_i64),
+                                    ctypes.POINTER(c_i64), c_float, c_float, c_float, c_float, c_float,
+                                    c_void_p, c_void_p, c_void_p]),
     'a3c_conv2d_forward': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 11 + [c_void_p]),
     'a3c_conv2d_backward': (c_int, [c_void_p] * 6 + [c_int] * 10 + [c_void_p]),
     'a3c_matmul': (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_int, c_int, c_int,
@@ -148,6 +153,9 @@ SIGNATURES = {
     'a3c_engine_create_opts': (c_int, [ctypes.POINTER(EngineConfig), ctypes.POINTER(EngineOpts),
                                        ctypes.POINTER(c_void_p)]),
     'a3c_engine_destroy': (c_int, [c_void_p]),
+    'a3c_engine_set_optimizer': (c_int, [c_void_p, c_int, c_double, c_double, c_double]),
+    'a3c_engine_adam_powers': (c_int, [c_void_p, ctypes.POINTER(c_double), ctypes.POINTER(c_double), c_void_p]),
+    'a3c_engine_set_adam_powers': (c_int, [c_void_p, c_double, c_double, c_void_p]),
     'a3c_engine_reset': (c_int, [c_void_p, c_void_p, c_void_p]),
     'a3c_engine_rollout_grad': (c_int, [c_void_p, c_void_p]),
     'a3c_engine_apply': (c_int, [c_void_p, c_void_p]),
@@ -211,7 +219,9 @@ OPTIONAL_IN_OLD_BUILDS = MEASUREMENT_ONLY + ('a3c_engine_exchange_split', 'a3c_e
                                              'a3c_engine_play_schedule', 'a3c_env_create_ex', 'a3c_engine_create_ex',
                                              'a3c_nstep_q_target', 'a3c_engine_opts_default',
                                              'a3c_engine_create_opts', 'a3c_engine_slot_boot_actions',
-                                             'a3c_boot_action', 'a3c_sarsa_target')
+                                             'a3c_boot_action', 'a3c_sarsa_target', 'a3c_clip_adam_apply',
+                                             'a3c_engine_set_optimizer', 'a3c_engine_adam_powers',
+                                             'a3c_engine_set_adam_powers')
 
 KER_CONV12_FWD, KER_FC_FWD, KER_ENV_STEP, KER_CONV_BWD, KER_HEAD_SCREEN, KER_HEAD_SCREEN_CONV12, KER_FC_PART = 0, 1, 2, 3, 4, 5, 6
 # nature trunk passes (include/a3c_hip.h A3C_KER_NAT_*)

@@ -20,7 +20,9 @@ keys are the TF variable names the reference's graph would give each tensor:
 * ``step``: the global step (the reference's ``step`` variable).
 
 Beyond what the reference's Saver keeps, the file also holds the RMSProp slots under TF1's slot
-names (``<var>/RMSProp`` = ms, ``<var>/RMSProp_1`` = momentum) and, for the batched engine, the
+names (``<var>/RMSProp`` = ms, ``<var>/RMSProp_1`` = momentum; with Adam ``<var>/Adam`` = m,
+``<var>/Adam_1`` = v and the fp64 ``beta1_power`` / ``beta2_power``; a file written by the other
+optimizer restores parameters and step only, with fresh slots) and, for the batched engine, the
 whole engine state (``__engine_state__``: counters, env state, frame ring, LSTM carry, the overlap
 pipeline's rollout in flight), so that a resumed run continues bit for bit.  With several GPUs each
 rank writes its own env shard's state to ``model.ckpt-<step>.rank<r>.npz``.  A ``checkpoint``
@@ -70,8 +72,15 @@ def tf_target_name(name):
     return 'target/target_%s/%s' % (layer, var)
 
 
-def slot_names(var):
-    """TF1 RMSPropOptimizer slot variables of ``var``: (rms, momentum)."""
+BETA_POWER_KEYS = ('beta1_power', 'beta2_power')      # TF1 AdamOptimizer's two non-slot variables
+
+
+def slot_names(var, optimizer='rmsprop'):
+    """TF1 slot variables of ``var`` in the order (engine ``ms`` buffer, engine ``mom`` buffer):
+    RMSPropOptimizer's (rms ``/RMSProp``, momentum ``/RMSProp_1``); AdamOptimizer's (v ``/Adam_1``,
+    m ``/Adam``)."""
+    if optimizer == 'adam':
+        return var + '/Adam_1', var + '/Adam'
     return var + '/RMSProp', var + '/RMSProp_1'
 
 
@@ -161,12 +170,16 @@ def engine_arrays(eng, names_shapes, with_state=True):
         return {name: f[off:off + sz].reshape(shp).copy()
                 for (name, shp), off, sz in zip(names_shapes, eng.offsets, eng.sizes)}
     P, MS, MOM = tensors(eng.params), tensors(eng.ms), tensors(eng.mom)
+    opt = getattr(eng, 'optimizer', 'rmsprop')
     out = {}
     for name, _ in names_shapes:
         tn = tf_name(name, algo, dqn)
         out[tn] = P[name]
-        rms, mom = slot_names(tn)
+        rms, mom = slot_names(tn, opt)
         out[rms], out[mom] = MS[name], MOM[name]
+    if opt == 'adam':
+        for key, p in zip(BETA_POWER_KEYS, eng.adam_powers):
+            out[key] = np.array(p, np.float64)
     if algo == 'q':
         T = tensors(eng.target_params)
         for name, _ in names_shapes:
@@ -217,11 +230,20 @@ def engine_restore(eng, names_shapes, arrays, state=None):
     if algo == 'q':
         T = flat(lambda n: arrays.get(tf_target_name(n)), P)
         eng.target_params.copy_(torch.as_tensor(T))
-    ms = flat(lambda n: arrays.get(slot_names(tf_name(n, algo, dqn))[0]))
-    mom = flat(lambda n: arrays.get(slot_names(tf_name(n, algo, dqn))[1]))
-    if ms is not None and mom is not None:
+    opt = getattr(eng, 'optimizer', 'rmsprop')
+    ms = flat(lambda n: arrays.get(slot_names(tf_name(n, algo, dqn), opt)[0]))
+    mom = flat(lambda n: arrays.get(slot_names(tf_name(n, algo, dqn), opt)[1]))
+    powers = [arrays.get(k) for k in BETA_POWER_KEYS] if opt == 'adam' else []
+    if ms is not None and mom is not None and all(p is not None for p in powers):
         eng.ms.copy_(torch.as_tensor(ms))
         eng.mom.copy_(torch.as_tensor(mom))
+        if opt == 'adam':
+            eng.adam_powers = [float(p) for p in powers]
+    else:
+        other = 'rmsprop' if opt == 'adam' else 'adam'
+        if any(slot_names(tf_name(n, algo, dqn), other)[0] in arrays for n, _ in names_shapes):
+            print('engine_restore: the checkpoint holds %s slots and the engine runs %s: parameters and step '
+                  'restored, optimizer slots fresh' % (other, opt), file=sys.stderr, flush=True)
     eng.set_step(step, int(arrays.get(WSTEP_KEY, step)))
     if torch.cuda.is_available():
         torch.cuda.synchronize()

@@ -23,6 +23,10 @@ one process (torch.distributed, backend "nccl" = RCCL over xGMI) and two exchang
   It learns up to W times slower per env-step and is kept only as the plain data-parallel
   baseline (tests/test_dist_gloo.py shows the two rules differ).
 
+Both work with the engine's Adam (``Engine(optimizer='adam')``) through the same calls:
+the W steps of a range are then W Adam steps, step q with the bias correction of the step count it
+brings the range to, and the commit advances the shared step count by W.
+
 ``sequential_apply`` is the agent-mode (one env per process) form of the PS rule: all-gather
 the clipped gradients, apply them in rank order.
 """
@@ -123,7 +127,9 @@ class PartitionedPS:
         """Every rank owns (updates) only its range of the RMSProp slots: gather the owned ranges
         of ms and mom into every replica's full buffers, so that a checkpoint (rank 0 writes the
         slots under TF1's slot names) holds the true slots of every range.  A collective: every
-        rank calls it at the same point, between iterations."""
+        rank calls it at the same point, between iterations.  With Adam ms holds v and mom
+        holds m, owned by range in the same way; the products beta^t are equal on every rank (each
+        commit advances them by the world size) and need no gather."""
         r = self.rank
         lo, n = self.lo[r], self.n[r]
         for t in (eng.ms, eng.mom):

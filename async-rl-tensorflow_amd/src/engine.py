@@ -25,6 +25,7 @@ import torch
 
 from . import _lib
 from ._lib import check, lib
+from .optim import check_adam
 
 GAMES = {  # ALE minimal action sets / starting lives
     'Pong-v0': (6, 0),
@@ -32,6 +33,7 @@ GAMES = {  # ALE minimal action sets / starting lives
     'SpaceInvaders-v0': (6, 3),
     'Catch-v0': (3, 0),
 }
+OPTIMIZERS = {'rmsprop': _lib.A3C_OPT_RMSPROP, 'adam': _lib.A3C_OPT_ADAM}
 GAME_IDS = {'synth': _lib.A3C_GAME_SYNTH, 'catch': _lib.A3C_GAME_CATCH}
 CATCH_FRAMES = 640
 
@@ -58,7 +60,17 @@ class Engine:
         start_lives 0, device envs, raw RGB pool; random_start is ignored).  num_frames=None: 1024
         frames (Catch needs its 640: a smaller explicit value is rejected by the library).
         sarsa=0|1 (algo q): Sarsa targets, with q_nstep=1 n-step Sarsa; an option of
-        a3c_engine_opts, not a field of the config."""
+        a3c_engine_opts, not a field of the config.
+        optimizer='rmsprop' | 'adam' (not given: RMSProp, and no call is made): Adam with TF1
+        ApplyAdam semantics, adam_beta1=0.9, adam_beta2=0.999, adam_epsilon=1e-8 and the learning rate of
+        the same schedule; ``mom`` is then m, ``ms`` is v and ``adam_powers`` the fp64 products beta1^t,
+        beta2^t.  decay, momentum and epsilon are RMSProp's and ignored by Adam."""
+        optimizer = overrides.pop('optimizer', None)
+        adam = check_adam(overrides.pop('adam_beta1', 0.9), overrides.pop('adam_beta2', 0.999),
+                          overrides.pop('adam_epsilon', 1e-8))
+        if optimizer is not None and optimizer not in OPTIMIZERS:
+            raise ValueError('unknown optimizer %r (the engine knows %s)' % (optimizer, sorted(OPTIMIZERS)))
+        self.optimizer = optimizer or 'rmsprop'
         _lib.require_device()
         if game not in GAME_IDS:
             raise ValueError('unknown game %r (the engine knows %s)' % (game, sorted(GAME_IDS)))
@@ -111,6 +123,8 @@ class Engine:
         else:
             check(lib().a3c_engine_create_ex(ctypes.byref(cfg), GAME_IDS[game], ctypes.byref(h)), 'a3c_engine_create_ex')
         self._h = h
+        if optimizer is not None:
+            check(lib().a3c_engine_set_optimizer(h, OPTIMIZERS[optimizer], *adam), 'a3c_engine_set_optimizer')
         b = _lib.EngineBuffers()
         check(lib().a3c_engine_get_buffers(h, ctypes.byref(b)), 'a3c_engine_get_buffers')
         self._b = b
@@ -408,6 +422,21 @@ class Engine:
         check(lib().a3c_engine_state_load(self._h, buf.ctypes.data_as(ctypes.c_void_p), buf.size,
                                           _lib.stream_handle()), 'a3c_engine_state_load')
 
+    @property
+    def adam_powers(self):
+        """(beta1^t, beta2^t) of the t Adam steps applied so far: the engine's fp64 device state, read
+        behind the work on the current stream; (1.0, 1.0) for RMSProp."""
+        p1, p2 = _lib.c_double(), _lib.c_double()
+        check(lib().a3c_engine_adam_powers(self._h, ctypes.byref(p1), ctypes.byref(p2), _lib.stream_handle()),
+              'a3c_engine_adam_powers')
+        return float(p1.value), float(p2.value)
+
+    @adam_powers.setter
+    def adam_powers(self, powers):
+        """Resume: the products a checkpoint stored (Adam engines, no gradient pending)."""
+        check(lib().a3c_engine_set_adam_powers(self._h, float(powers[0]), float(powers[1]), _lib.stream_handle()),
+              'a3c_engine_set_adam_powers')
+
     def advance(self):
         check(lib().a3c_engine_advance(self._h, _lib.stream_handle()), 'a3c_engine_advance')
 
@@ -421,6 +450,9 @@ class Engine:
         rollout k+1 -- the push and pull overlap the next rollout, at staleness 1 like the overlap
         mode (the reference's workers keep acting while the PS applies, main.py:60-65).  Rollout
         k+1 is enqueued behind that pull (the engine orders its rollout stream after the caller's)."""
+        if self.optimizer == 'adam':
+            raise ValueError('Hogwild applies RMSProp in its lock-free shards, which keep no shared step count for '
+                             "Adam's bias correction (DESIGN §4j): use iterate()")
         self.rollout_grad()
         if not self.grad_ready:
             return                      # overlap pipeline filling: no gradient yet

@@ -255,6 +255,13 @@ int a3c_clip_rmsprop_apply(float* params, float* ms, float* mom, float* grads, i
                            const int64_t* offsets, const int64_t* sizes, float lr, float rho,
                            float momentum, float eps, float clip, float* sumsq_out,
                            void* workspace, void* stream);
+/* The same pass with TF1 ApplyAdam: m += (g-m)(1-beta1); v += (g^2-v)(1-beta2);
+ * w -= m*alpha / (sqrt(v) + eps), in fp32.  m and v must be initialised to 0.  The caller forms
+ * alpha = lr * sqrt(1 - beta2^t) / (1 - beta1^t) of the step t = 1, 2, ... it applies. */
+int a3c_clip_adam_apply(float* params, float* m, float* v, float* grads, int n_tensors,
+                        const int64_t* offsets, const int64_t* sizes, float alpha, float beta1,
+                        float beta2, float eps, float clip, float* sumsq_out,
+                        void* workspace, void* stream);
 
 /* ----------------------------------------------------------------------------
  * Generic layer ops (ops.py:4-46 drop-ins, any shape; off the hot path).
@@ -462,9 +469,28 @@ typedef struct a3c_engine_opts { int size; int game; int sarsa; } a3c_engine_opt
 void a3c_engine_opts_default(a3c_engine_opts* opts);   /* size = sizeof, game = A3C_GAME_SYNTH, sarsa = 0 */
 int a3c_engine_create_opts(const a3c_engine_config* cfg, const a3c_engine_opts* opts, a3c_engine** out);
 int a3c_engine_destroy(a3c_engine* eng);
+/* The engine's optimizer.  A3C_OPT_RMSPROP (the default: cfg.decay / momentum / epsilon;
+ * beta1, beta2 and eps are then checked and otherwise unused) or A3C_OPT_ADAM, TF1 ApplyAdam with the
+ * lr of the same schedule: the `mom` buffer holds m, the `ms` buffer v, and the engine keeps the fp64
+ * running products beta1^t, beta2^t of its t applied steps on the device -- the schedule forms alpha
+ * from them, the apply (a3c_engine_apply_commit: by the nranks of its a3c_engine_apply_shard calls)
+ * advances them.  A setter, not an option of a struct: neither a3c_engine_config nor a3c_engine_opts
+ * can grow.  Legal whenever no gradient is pending (before or after a3c_engine_reset, between
+ * iterations): it re-initialises the two slots (RMSProp: ms = 1, mom = 0; Adam: both 0) and the
+ * products (1, 1) on the null stream and waits for them; a3c_engine_reset does the same for the
+ * optimizer set.  A3C_ERR_INVALID, before anything touches the device: kind unknown, a beta outside
+ * [0, 1), eps <= 0, eng NULL (checked in that order).  A3C_ERR_STATE: a computed gradient not yet applied.
+ * Engines that never call it launch what they launched without it.
+ * a3c_engine_adam_powers: the two products (1, 1 for RMSProp), after the work on `stream`;
+ * a3c_engine_set_adam_powers writes them (resume from a checkpoint; Adam engines only). */
+#define A3C_OPT_RMSPROP 0
+#define A3C_OPT_ADAM 1
+int a3c_engine_set_optimizer(a3c_engine* eng, int kind, double beta1, double beta2, double eps);
+int a3c_engine_adam_powers(a3c_engine* eng, double* beta1_power, double* beta2_power, void* stream);
+int a3c_engine_set_adam_powers(a3c_engine* eng, double beta1_power, double beta2_power, void* stream);
 /* fill the frame pool, reset the envs (new_random_game, environment.py:35-40), fill each
  * history with 4 copies of the first screen (agent.py:37-38) and initialise params
- * from host memory (nullable -> keep), rms slot = 1, mom = 0. */
+ * from host memory (nullable -> keep), rms slot = 1, mom = 0 (Adam: m = v = 0, products = 1). */
 int a3c_engine_reset(a3c_engine* eng, const float* host_params, void* stream);
 /* n rollout steps + bootstrap + loss + backward + per-tensor clip -> grads */
 int a3c_engine_rollout_grad(a3c_engine* eng, void* stream);
@@ -494,7 +520,11 @@ int a3c_engine_advance(a3c_engine* eng, void* stream);
  *   host: all-gather of every rank's w_out -> the full parameter vector;
  *   a3c_engine_apply_commit: params <- params_src (nullable: already there), overlap snapshot,
  *     target sync (q), counters -- the rest of a3c_engine_apply.
- * Both are no-ops when no gradient is pending (overlap pipeline filling). */
+ * Both are no-ops when no gradient is pending (overlap pipeline filling).  With A3C_OPT_ADAM the W
+ * steps are Adam steps, step q with the alpha of the step count advanced q + 1 times (at most 64
+ * ranks per call), and the commit advances the count by W; a commit of a pending gradient
+ * with no a3c_engine_apply_shard before it -- the Hogwild push, which applies RMSProp in its shards --
+ * returns A3C_ERR_STATE on an Adam engine. */
 int a3c_engine_apply_shard(a3c_engine* eng, const float* grads_by_rank, int nranks, int64_t lo, int64_t n,
                            float* w_out, void* stream);
 int a3c_engine_apply_commit(a3c_engine* eng, const float* params_src, void* stream);
