@@ -532,6 +532,7 @@ extern "C" int a3c_engine_create_opts(const a3c_engine_config* cfg, const a3c_en
   e->envp.action_repeat = cfg->action_repeat;
   e->envp.env_id_base = cfg->env_id_base;
   e->envp.game = e->game;
+  env_params_catch_default(e->envp);
   // per-env final epsilon (main.py:68 samples ep_end per worker from {0.1, 0.01, 0.5})
   std::vector<int32_t> idx(E);
   for (int64_t i = 0; i < E; ++i) idx[i] = (int32_t)i;
@@ -1332,6 +1333,32 @@ extern "C" int a3c_engine_set_adam_powers(a3c_engine* e, double beta1_power, dou
   return 0;
 }
 
+// Catch's rules: recorded only.  The pool, the envs and the play context follow at the
+// next a3c_engine_reset, which every entry that steps an env asks for until then (reset_done).
+extern "C" int a3c_engine_set_catch_rules(a3c_engine* e, int visible_rows, int frozen_rows) {
+  if (visible_rows < 1 || visible_rows > 10)
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_set_catch_rules", "visible_rows must be in 1..10");
+  if (frozen_rows < 0 || frozen_rows > 8)
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_set_catch_rules", "frozen_rows must be in 0..8");
+  if (!e) return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_set_catch_rules", "null");
+  if (e->game != A3C_GAME_CATCH)
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_set_catch_rules", "the engine's game is not Catch");
+  if (e->grad_ready && !e->grad_applied)
+    return a3c_set_error(A3C_ERR_STATE, "a3c_engine_set_catch_rules", "a gradient is pending: apply it first");
+  A3C_CHECK(hipDeviceSynchronize());      // (the engine's streams: nothing in flight steps an env)
+  e->envp.catch_visible = (int16_t)visible_rows;
+  e->envp.catch_frozen = (int16_t)frozen_rows;
+  // the captured graphs hold the other rules in their kernel arguments
+  for (int i = 0; i < NGRAPH; ++i)
+    if (e->captured[i]) {
+      (void)hipGraphExecDestroy(e->gexec[i]);
+      (void)hipGraphDestroy(e->graph[i]);
+      e->captured[i] = false;
+    }
+  e->reset_done = false;
+  return 0;
+}
+
 extern "C" int a3c_engine_reset(a3c_engine* e, const float* host_params, void* stream) {
   if (!e) return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_reset", "null");
   hipStream_t s = (hipStream_t)stream;
@@ -1348,7 +1375,7 @@ extern "C" int a3c_engine_reset(a3c_engine* e, const float* host_params, void* s
   A3C_CHECK(hipMemsetAsync(e->ring, 0, (size_t)e->E * e->R * PLANE, s));
   if (!e->ext) {
     rc = e->envp.game == A3C_GAME_CATCH     // (rendered from the frame index, not hashed: DESIGN §4g)
-             ? a3c_pool_render_catch_launch(e->pool, e->cfg.num_frames, s)
+             ? a3c_pool_render_catch_launch(e->pool, e->cfg.num_frames, e->envp.catch_visible, s)
              : a3c_pool_fill_launch(e->pool, e->cfg.num_frames, e->k0, e->k1, s, frame_bytes(e));
     if (rc) return rc;
     rc = a3c_env_init_launch(e->envp, e->env, e->E, e->pool, e->ring, e->R, e->counters, s, e->frame84);

@@ -388,11 +388,13 @@ int a3c_env_screen_launch(int E, const int32_t* frames, const uint8_t* pool, uin
 // the ball's cell (rows [21 r, 21 r + 21) x cols [20 c, 20 c + 20)) in (236,236,236), then the
 // paddle (rows [200, 210) x cols [20 p, 20 p + 20)) in (92,186,92) over it.  One 16-byte chunk per
 // thread and pass; frames >= CATCH_FRAMES of a larger pool are never read and stay as they are.
+// visible_rows (EnvParams.catch_visible): the ball's cell is drawn only in the frames of
+// ball rows r < visible_rows (10: every frame); the paddle always is.
 #define CATCH_CELL_W (SCREEN_W / CATCH_COLS)      // 20
 #define CATCH_CELL_H (SCREEN_H / CATCH_ROWS)      // 21
 #define CATCH_PADDLE_Y (SCREEN_H - 10)            // 200
 static_assert(CATCH_CELL_W * CATCH_COLS == SCREEN_W && CATCH_CELL_H * CATCH_ROWS == SCREEN_H, "Catch cells tile the screen");
-__global__ void __launch_bounds__(256) k_pool_render_catch(uint8_t* __restrict__ pool) {
+__global__ void __launch_bounds__(256) k_pool_render_catch(uint8_t* __restrict__ pool, int visible_rows) {
   constexpr int64_t CPF = SCREEN_H * SCREEN_W * 3 / 16;   // 6300 chunks per frame
   constexpr int64_t TOTAL = CPF * CATCH_FRAMES;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < TOTAL; i += (int64_t)gridDim.x * blockDim.x) {
@@ -404,7 +406,7 @@ __global__ void __launch_bounds__(256) k_pool_render_catch(uint8_t* __restrict__
       const int byte = 16 * j + k, pix = byte / 3, ch = byte - 3 * pix;
       const int y = pix / SCREEN_W, x = pix - y * SCREEN_W;
       uint32_t v = 0u;
-      if (y / CATCH_CELL_H == r && x / CATCH_CELL_W == c) v = 236u;
+      if (r < visible_rows && y / CATCH_CELL_H == r && x / CATCH_CELL_W == c) v = 236u;
       if (y >= CATCH_PADDLE_Y && x / CATCH_CELL_W == p) v = ch == 1 ? 186u : 92u;
       w[k >> 2] |= v << (8 * (k & 3));
     }
@@ -413,9 +415,9 @@ __global__ void __launch_bounds__(256) k_pool_render_catch(uint8_t* __restrict__
 }
 
 // P: the pool's frame count (>= CATCH_FRAMES, or nothing is written)
-int a3c_pool_render_catch_launch(uint8_t* pool, int P, hipStream_t s) {
+int a3c_pool_render_catch_launch(uint8_t* pool, int P, int visible_rows, hipStream_t s) {
   if (!pool || P < CATCH_FRAMES) return a3c_set_error(A3C_ERR_INVALID, "a3c_pool_render_catch", "the pool holds fewer than 640 frames");
-  hipLaunchKernelGGL(k_pool_render_catch, dim3(4096), dim3(256), 0, s, pool);
+  hipLaunchKernelGGL(k_pool_render_catch, dim3(4096), dim3(256), 0, s, pool, visible_rows);
   A3C_CHECK(hipGetLastError());
   return 0;
 }

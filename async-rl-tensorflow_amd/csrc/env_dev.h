@@ -107,6 +107,9 @@ __host__ __device__ inline void env_act(EnvState& s, const EnvParams& p, uint32_
 // step, one in a reset.  The act is split for the fused head kernels: catch_act_pre is everything
 // that does not depend on the action (rows, landing, terminal), catch_act_post the paddle move,
 // the reward and the frame index.
+// Two rule parameters (EnvParams; a3c_engine_set_catch_rules): the ball is drawn only in
+// rows < catch_visible (the pool render), the paddle moves only in steps from a row >= catch_frozen,
+// and the reset drops the ball where the paddle can still reach it.  10, 0 is the game above.
 #define CATCH_COLS 8
 #define CATCH_ROWS 10
 #define CATCH_FRAMES (CATCH_COLS * CATCH_ROWS * CATCH_COLS)   // 640
@@ -118,7 +121,12 @@ __host__ __device__ inline void catch_reset(EnvState& s, const EnvParams& p, uin
   s.ep_step = 0;
   s.ep_len = CATCH_ROWS - 1;
   s.lives = 0;
-  s.frame = (int32_t)((x.x % CATCH_COLS) * CATCH_ROWS * CATCH_COLS + x.y % CATCH_COLS);
+  // the ball's column: uniform over the columns within M = 9 - frozen of the paddle's, the paddle's
+  // free steps (frozen <= 2: M >= 7, lo = 0, hi = 7, c = x.x % 8)
+  const int pc = (int)(x.y % CATCH_COLS), m = CATCH_ROWS - 1 - (int)p.catch_frozen;
+  const int lo = pc - m > 0 ? pc - m : 0, hi = pc + m < CATCH_COLS - 1 ? pc + m : CATCH_COLS - 1;
+  const uint32_t c = (uint32_t)lo + x.x % (uint32_t)(hi - lo + 1);
+  s.frame = (int32_t)(c * CATCH_ROWS * CATCH_COLS + (uint32_t)pc);
   s.reward = 0.f;
   s.terminal = 0u;
 }
@@ -127,14 +135,15 @@ __host__ __device__ inline void catch_reset(EnvState& s, const EnvParams& p, uin
 // env_act_pre: stop at a terminal).  s.frame stays the pre-act frame, s.reward is 0 (the reward
 // needs the action).  Returns the word catch_act_post finishes the act from: the pre-act frame
 // reduced into [0, CATCH_FRAMES) | new row << 10 | paddle moves << 14 | landed in this act << 18.
-// A step on a landed state changes nothing: reward 0, terminal 1, no move.
-__host__ __device__ inline uint32_t catch_act_pre(EnvState& s, int repeat) {
+// A step on a landed state changes nothing: reward 0, terminal 1, no move.  `frozen`: a step from a
+// row < frozen advances the row and is no paddle move.
+__host__ __device__ inline uint32_t catch_act_pre(EnvState& s, int repeat, int frozen) {
   const uint32_t f = (uint32_t)s.frame % (uint32_t)CATCH_FRAMES;
   uint32_t r = (f / CATCH_COLS) % CATCH_ROWS, moves = 0, landed = 0;
   for (int k = 0; k < repeat; ++k) {
     if (r < CATCH_ROWS - 1) {
+      moves += (int)r >= frozen ? 1u : 0u;
       r += 1u;
-      moves += 1u;
       landed = r == CATCH_ROWS - 1 ? 1u : 0u;
     } else {
       landed = 0u;
@@ -162,8 +171,8 @@ __host__ __device__ inline int32_t catch_act_post(uint32_t w, uint32_t action, f
 
 // GymEnvironment.act for Catch (is_training makes no difference: no life is ever lost); repeat = 1
 // is the raw step of SimpleGymEnvironment.act
-__host__ __device__ inline void catch_act(EnvState& s, int repeat, uint32_t action) {
-  const uint32_t w = catch_act_pre(s, repeat);
+__host__ __device__ inline void catch_act(EnvState& s, int repeat, int frozen, uint32_t action) {
+  const uint32_t w = catch_act_pre(s, repeat, frozen);
   s.frame = catch_act_post(w, action, s.reward);
 }
 
@@ -188,7 +197,7 @@ template <int GAME>
 __host__ __device__ inline void game_act(EnvState& s, const EnvParams& p, uint32_t id, uint32_t action, bool training,
                                          bool simple = false) {
   if constexpr (GAME == A3C_GAME_CATCH) {
-    catch_act(s, simple ? 1 : p.action_repeat, action);
+    catch_act(s, simple ? 1 : p.action_repeat, p.catch_frozen, action);
   } else {
     if (simple) env_step_raw(s, p, id, action);
     else env_act(s, p, id, action, training);

@@ -125,6 +125,7 @@ extern "C" int a3c_hostenv_create(int num_envs, int action_size, int start_lives
   h->p.random_start = random_start;
   h->p.action_repeat = action_repeat;
   h->p.env_id_base = env_id_base;
+  env_params_catch_default(h->p);      // (never read: the host envs play the synthetic game)
   h->st.assign(num_envs, EnvState{0u, 0u, 0u, 0, 0, 0.f, 0u});
   try {
     h->pool.resize((size_t)num_frames * FRAME_BYTES);

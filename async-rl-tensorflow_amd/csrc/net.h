@@ -96,7 +96,14 @@ struct EnvParams {
   uint32_t k0, k1;
   int P, A, L0, random_start, action_repeat, env_id_base;
   int game;                 // A3C_GAME_*: picks the kernels' instantiation on the host (never read on device)
+  // Catch's rules (read by the Catch instantiations alone): the ball is drawn in rows
+  // < catch_visible, the paddle moves in steps from rows >= catch_frozen.  10, 0 is Catch-v0.  Two
+  // 16-bit words in the 4 bytes that padded the struct to the 8-byte alignment of what follows it
+  // in every kernel argument list and in HeadSelect: no kernel argument moves.
+  int16_t catch_visible, catch_frozen;
 };
+static_assert(sizeof(EnvParams) == 40, "EnvParams fills its padding, it does not grow");
+inline void env_params_catch_default(EnvParams& p) { p.catch_visible = 10; p.catch_frozen = 0; }
 
 struct EnvBufs {
   uint32_t* episode;
@@ -156,7 +163,9 @@ struct HeadSelect {
   const float* fc_bias;
   float* l3_out;
 };
-#define FC_NS 8                 // K-slices of the partial fc (= waves of k_head_screen_conv12)
+static_assert(__builtin_offsetof(HeadSelect, envb) - __builtin_offsetof(HeadSelect, envp) == sizeof(EnvParams),
+              "EnvParams' last 4 bytes were HeadSelect's padding");
+#define FC_NS 8                // K-slices of the partial fc (= waves of k_head_screen_conv12)
 
 // forward of B states; returns 0 or error
 // prep: the forward's prepared weights of `params` (a3c_prep_fwd_launch, PREP_BYTES):

@@ -556,7 +556,7 @@ __device__ inline int32_t head_act_env(const float* __restrict__ h3, const float
     EnvState s = env_load(sel.envb, cur);
     uint32_t draw;
     if constexpr (GAME == A3C_GAME_CATCH) {
-      draw = catch_act_pre(s, sel.envp.action_repeat);         // (the rewards: behind the barrier)
+      draw = catch_act_pre(s, sel.envp.action_repeat, sel.envp.catch_frozen);   // (the rewards: behind the barrier)
     } else {
       draw = env_act_pre(s, sel.envp, id, !PLAY);
       if constexpr (!PLAY) sel.rewards[e] = fmaxf(-1.0f, fminf(1.0f, s.reward));   // observe clip, agent.py:154

@@ -7,7 +7,7 @@
 #include "env_dev.h"
 
 int a3c_pool_fill_launch(uint8_t* pool, int P, uint32_t k0, uint32_t k1, hipStream_t s, int frame_bytes);
-int a3c_pool_render_catch_launch(uint8_t* pool, int P, hipStream_t s);
+int a3c_pool_render_catch_launch(uint8_t* pool, int P, int visible_rows, hipStream_t s);
 int a3c_launch_screen_atari(const uint8_t* rgb, const int32_t* idx, int64_t n, uint8_t* out, int64_t stride,
                             hipStream_t s);
 
@@ -49,7 +49,7 @@ __global__ void k_venv_act(EnvParams p, EnvBufs b, int E, const int32_t* __restr
   const uint32_t id = (uint32_t)(p.env_id_base + e);
   EnvState s = env_load(b, e);
   if constexpr (GAME == A3C_GAME_CATCH) {
-    catch_act(s, simple ? 1 : p.action_repeat, (uint32_t)actions[e]);
+    catch_act(s, simple ? 1 : p.action_repeat, p.catch_frozen, (uint32_t)actions[e]);
   } else {
     if (simple) env_step_raw(s, p, id, (uint32_t)actions[e]);
     else env_act(s, p, id, (uint32_t)actions[e], training != 0);
@@ -101,8 +101,9 @@ extern "C" int a3c_env_create_ex(int num_envs, int action_size, int start_lives,
   v->p.action_repeat = action_repeat;
   v->p.env_id_base = env_id_base;
   v->p.game = game;
+  env_params_catch_default(v->p);
   int rc = game == A3C_GAME_CATCH
-               ? a3c_pool_render_catch_launch(v->pool, num_frames, nullptr)
+               ? a3c_pool_render_catch_launch(v->pool, num_frames, v->p.catch_visible, nullptr)
                : a3c_pool_fill_launch(v->pool, num_frames, v->p.k0, v->p.k1, nullptr, SCREEN_H * SCREEN_W * 3);
   if (!rc) {
     hipLaunchKernelGGL(k_venv_zero, dim3((num_envs + 63) / 64), dim3(64), 0, nullptr, v->b, num_envs);
@@ -123,6 +124,21 @@ extern "C" int a3c_env_destroy(a3c_env* v) {
   (void)hipFree(v->mem);
   delete v;
   return 0;
+}
+
+// Catch's rules: the pool is rendered again on `stream`; the envs' states stay, the
+// caller starts new games
+extern "C" int a3c_env_set_catch_rules(a3c_env* v, int visible_rows, int frozen_rows, void* stream) {
+  if (visible_rows < 1 || visible_rows > 10)
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_env_set_catch_rules", "visible_rows must be in 1..10");
+  if (frozen_rows < 0 || frozen_rows > 8)
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_env_set_catch_rules", "frozen_rows must be in 0..8");
+  if (!v) return a3c_set_error(A3C_ERR_INVALID, "a3c_env_set_catch_rules", "null");
+  if (v->p.game != A3C_GAME_CATCH)
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_env_set_catch_rules", "the env's game is not Catch");
+  v->p.catch_visible = (int16_t)visible_rows;
+  v->p.catch_frozen = (int16_t)frozen_rows;
+  return a3c_pool_render_catch_launch(v->pool, v->p.P, visible_rows, (hipStream_t)stream);
 }
 
 extern "C" int a3c_env_new_game(a3c_env* v, const uint8_t* mask, int random, void* stream) {

@@ -12,6 +12,7 @@ accepted but the TF ps/worker cluster is replaced by one process per GPU under t
   python main.py --mode engine --algo q --q_nstep true --n_step 5 --env_name Catch-v0   n-step Q-learning
   python main.py --mode engine --algo q --sarsa true --n_step 5 --env_name Catch-v0     Sarsa (--q_nstep true: n-step)
   python main.py --mode engine --algo q --optimizer adam --env_name Catch-v0             shared Adam instead of RMSProp
+  python main.py --mode engine --lstm true --env_name CatchMemory-v0   Catch that only a head with memory learns
   python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 main.py --mode engine
   python main.py --mode engine --is_train false --n_episode 100     evaluate the newest checkpoint
   python main.py --mode engine --is_train false --play_refill true  ... refilling finished envs (no waves)
@@ -127,8 +128,8 @@ def engine_options(flags):
     raise ValueError('--dueling (agent.py:234-249) is not fused into the engine: use --mode agent')
   from src.environment import game_kind
   if game_kind(flags.env_name) == 'catch' and flags.envs_on != 'device':
-    raise ValueError('--env_name Catch-v0 is a device game: --envs_on %s is not supported (the host-thread '
-                     'emulator and gym know the Atari games only)' % flags.envs_on)
+    raise ValueError('--env_name %s is a device game: --envs_on %s is not supported (the host-thread '
+                     'emulator and gym know the Atari games only)' % (flags.env_name, flags.envs_on))
   if flags.dqn_type == 'nature' and (flags.algo != 'a3c' or flags.lstm):
     raise ValueError('--dqn_type nature: the A3C Network trunk (network.py:30-42) runs with --algo a3c and the '
                      'feed-forward head (the Q-net of agent.py:226-252 is nips only)')
@@ -206,13 +207,13 @@ def run_play(config, flags, play_kw):
   from src import checkpoint as C
   from src.base import BaseModel
   from src.engine import Engine
-  from src.environment import game_kind, game_spec
+  from src.environment import catch_rules_of, game_kind, game_spec
   from src.kernels import param_names_shapes
   torch.cuda.set_device(int(os.environ.get('LOCAL_RANK', '0')))
   A, lives = game_spec(config.env_name)
   eng = Engine(num_envs=flags.num_envs, n_step=flags.n_step, action_size=A, algo=flags.algo, start_lives=lives,
                num_frames=flags.num_frames, seed=flags.random_seed, overlap=False, **engine_options(flags),
-               game=game_kind(config.env_name),
+               game=game_kind(config.env_name), catch_rules=catch_rules_of(config.env_name),
                random_start=config.random_start, action_repeat=config.action_repeat)
   ns = param_names_shapes(A, flags.algo, lstm=eng.lstm, dqn_type=eng.dqn_type)
   ckdir = flags.checkpoint_dir or os.path.join(flags.logdir, BaseModel(config, verbose=False).model_dir)
@@ -290,7 +291,7 @@ def run_engine(config, flags):
   from src import distributed as D
   from src.base import BaseModel
   from src.engine import Engine
-  from src.environment import game_kind, game_spec
+  from src.environment import catch_rules_of, game_kind, game_spec
   from src.kernels import param_names_shapes
   rank, world, local = D.init_from_env()
   torch.cuda.set_device(local)
@@ -314,8 +315,8 @@ def run_engine(config, flags):
   pool = make_host_pool(config, flags, E, A, lives, rank) if host else None
   eng = Engine(num_envs=E, n_step=flags.n_step, action_size=A, algo=flags.algo, start_lives=lives,
                num_frames=1 if host else flags.num_frames, seed=flags.random_seed, env_id_base=rank * E,
-               world_size=world, overlap=overlap, external_env=host, game=game_kind(config.env_name), **net_kw,
-               **opts)
+               world_size=world, overlap=overlap, external_env=host, game=game_kind(config.env_name),
+               catch_rules=catch_rules_of(config.env_name), **net_kw, **opts)
   ns = param_names_shapes(A, flags.algo, lstm=eng.lstm, dqn_type=eng.dqn_type)
   # checkpoints: <logdir>/<model_dir> as the Supervisor's logdir (main.py:75), Saver max_to_keep
   # (agent.py:29); restored at start as managed_session does (main.py:90)

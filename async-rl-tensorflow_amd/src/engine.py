@@ -32,6 +32,7 @@ GAMES = {  # ALE minimal action sets / starting lives
     'Breakout-v0': (4, 5),
     'SpaceInvaders-v0': (6, 3),
     'Catch-v0': (3, 0),
+    'CatchMemory-v0': (3, 0),
 }
 OPTIMIZERS = {'rmsprop': _lib.A3C_OPT_RMSPROP, 'adam': _lib.A3C_OPT_ADAM}
 GAME_IDS = {'synth': _lib.A3C_GAME_SYNTH, 'catch': _lib.A3C_GAME_CATCH}
@@ -55,7 +56,7 @@ def _view(ptr, shape, dtype):
 class Engine:
     def __init__(self, num_envs=256, n_step=5, action_size=6, algo='a3c', start_lives=0, num_frames=None,
                  seed=123, env_id_base=0, world_size=1, use_graph=False, overlap=False, lstm=False,
-                 external_env=False, dqn_type='nips', game='synth', **overrides):
+                 external_env=False, dqn_type='nips', game='synth', catch_rules=None, **overrides):
         """game: 'synth' (the synthetic Atari stand-in) or 'catch' (Catch-v0, DESIGN §4g: action_size 3,
         start_lives 0, device envs, raw RGB pool; random_start is ignored).  num_frames=None: 1024
         frames (Catch needs its 640: a smaller explicit value is rejected by the library).
@@ -64,7 +65,19 @@ class Engine:
         optimizer='rmsprop' | 'adam' (not given: RMSProp, and no call is made): Adam with TF1
         ApplyAdam semantics, adam_beta1=0.9, adam_beta2=0.999, adam_epsilon=1e-8 and the learning rate of
         the same schedule; ``mom`` is then m, ``ms`` is v and ``adam_powers`` the fp64 products beta1^t,
-        beta2^t.  decay, momentum and epsilon are RMSProp's and ignored by Adam."""
+        beta2^t.  decay, momentum and epsilon are RMSProp's and ignored by Adam.
+        catch_rules=None | (visible_rows, frozen_rows) (game 'catch'; None: Catch-v0's (10, 0),
+        and no call is made): a3c_engine_set_catch_rules right after the create -- the ball is drawn in
+        rows < visible_rows only, the paddle is frozen in the first frozen_rows steps; kept as
+        ``catch_rules``.  environment.catch_rules_of(env_name) is the pair of a game's name."""
+        if catch_rules is not None:
+            if game != 'catch':
+                raise ValueError('catch_rules are the rules of game catch, not of %r' % (game,))
+            v, f = (int(x) for x in catch_rules)
+            if not (1 <= v <= 10 and 0 <= f <= 8):
+                raise ValueError('catch_rules %r: visible_rows in 1..10, frozen_rows in 0..8' % (tuple(catch_rules),))
+            catch_rules = (v, f)
+        self.catch_rules = catch_rules
         optimizer = overrides.pop('optimizer', None)
         adam = check_adam(overrides.pop('adam_beta1', 0.9), overrides.pop('adam_beta2', 0.999),
                           overrides.pop('adam_epsilon', 1e-8))
@@ -125,6 +138,8 @@ class Engine:
         self._h = h
         if optimizer is not None:
             check(lib().a3c_engine_set_optimizer(h, OPTIMIZERS[optimizer], *adam), 'a3c_engine_set_optimizer')
+        if catch_rules is not None:
+            check(lib().a3c_engine_set_catch_rules(h, *catch_rules), 'a3c_engine_set_catch_rules')
         b = _lib.EngineBuffers()
         check(lib().a3c_engine_get_buffers(h, ctypes.byref(b)), 'a3c_engine_get_buffers')
         self._b = b

@@ -14,6 +14,9 @@ BILINEAR 84x84 image (:49-53, bit-exact).  Screens are u8 [84,84] device tensors
 ``env_name = 'Catch-v0'`` selects Catch instead (a3c_env_create_ex): a game with real
 dynamics -- 3 actions, no lives, 9-step episodes, reward +-1 at the landing -- behind the same
 interface; ``new_game`` / ``new_random_game`` are its reset, and ``random_start`` is ignored.
+``'CatchMemory-v0'`` is Catch with the rules of CATCH_RULES (a3c_env_set_catch_rules):
+the ball is drawn in its first row only and the paddle is frozen for the first four steps, so only a
+policy with memory can catch it.
 """
 import ctypes
 
@@ -28,8 +31,10 @@ GAMES = {  # ALE minimal action sets and starting lives
     'Breakout-v0': (4, 5),
     'SpaceInvaders-v0': (6, 3),
     'Catch-v0': (3, 0),       # the learnable device game: stay / left / right, no lives
+    'CatchMemory-v0': (3, 0),  # Catch that needs memory
 }
-GAME_KINDS = {'Catch-v0': 'catch'}     # every other name plays the synthetic stand-in ('synth')
+GAME_KINDS = {'Catch-v0': 'catch', 'CatchMemory-v0': 'catch'}     # every other name plays the synthetic stand-in ('synth')
+CATCH_RULES = {'CatchMemory-v0': (1, 4)}     # (visible_rows, frozen_rows); not listed: Catch's own (10, 0), no call
 GAME_IDS = {'synth': _lib.A3C_GAME_SYNTH, 'catch': _lib.A3C_GAME_CATCH}
 CATCH_FRAMES = 640                     # Catch's state is its frame index: the pool must hold them all
 
@@ -46,9 +51,15 @@ def game_kind(env_name):
   return GAME_KINDS.get(env_name, 'synth')
 
 
+def catch_rules_of(env_name):
+  """(visible_rows, frozen_rows) of a Catch variant (Engine(catch_rules=...), a3c_env_set_catch_rules),
+  None for every other name -- Catch-v0 included, whose rules are the library's default."""
+  return CATCH_RULES.get(env_name)
+
+
 class BatchedEnvironment(object):
-  """E device envs: the synthetic Atari stand-in, or Catch for env_name 'Catch-v0' (random_start is
-  ignored there: the reset is the random start)."""
+  """E device envs: the synthetic Atari stand-in, or Catch for env_name 'Catch-v0' and
+  'CatchMemory-v0' (random_start is ignored there: the reset is the random start)."""
 
   def __init__(self, config, num_envs=1, env_id_base=0, seed=None, num_frames=None):
     _lib.require_device()
@@ -69,6 +80,10 @@ class BatchedEnvironment(object):
     check(lib().a3c_env_create_ex(self.E, self.action_size_, self.start_lives, self.random_start, self.action_repeat,
                                   nf, seed, int(env_id_base), GAME_IDS[self.game], ctypes.byref(h)), 'a3c_env_create_ex')
     self._h = h
+    self.catch_rules = catch_rules_of(config.env_name)
+    if self.catch_rules is not None:      # (before any game is started: the pool is rendered again)
+      check(lib().a3c_env_set_catch_rules(h, int(self.catch_rules[0]), int(self.catch_rules[1]), _lib.stream_handle()),
+            'a3c_env_set_catch_rules')
     ptrs = [ctypes.c_void_p() for _ in range(7)]
     check(lib().a3c_env_buffers(h, *[ctypes.byref(p) for p in ptrs]), 'a3c_env_buffers')
     from .engine import _view

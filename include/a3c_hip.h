@@ -361,6 +361,21 @@ int a3c_env_create(int num_envs, int action_size, int start_lives, int random_st
 /* a3c_env_create with the game as an argument; a3c_env_create is game = A3C_GAME_SYNTH. */
 int a3c_env_create_ex(int num_envs, int action_size, int start_lives, int random_start, int action_repeat,
                       int num_frames, uint64_t seed, int env_id_base, int game, a3c_env** out);
+/* Catch's two rule parameters, visible_rows V in 1..10 and frozen_rows F in 0..8; V = 10,
+ * F = 0 is the game above, bit for bit, and "CatchMemory-v0" is V = 1, F = 4.
+ *  render: the ball's cell is drawn only in the frames of ball rows r < V; the paddle always is.
+ *  step:   in one elementary step the paddle moves only if the row before the step is >= F; the
+ *          row always advances.  Landing, reward and terminal are unchanged.
+ *  reset:  the same Philox draw; p = x1 % 8, M = 9 - F, lo = max(0, p - M), hi = min(7, p + M),
+ *          c = lo + x0 % (hi - lo + 1): the ball falls where the paddle can still reach it
+ *          (F <= 2: c = x0 % 8).
+ * With F >= V + 3 and action_repeat 1 no 4-frame state in which an action moves the paddle shows
+ * the ball: a policy without memory cannot do better than chance, one with memory reaches +1.
+ * a3c_env_set_catch_rules records the rules and renders the pool again on `stream`; the envs' states
+ * stay as they are, the caller starts new games afterwards.  A3C_ERR_INVALID, before anything
+ * touches the device and in this order: V outside 1..10, F outside 0..8, env NULL, an env whose
+ * game is not Catch.  An env that never calls it is V = 10, F = 0. */
+int a3c_env_set_catch_rules(a3c_env* env, int visible_rows, int frozen_rows, void* stream);
 int a3c_env_destroy(a3c_env* env);
 int a3c_env_new_game(a3c_env* env, const uint8_t* mask, int random, void* stream);
 int a3c_env_act(a3c_env* env, const int32_t* actions, int is_training, int simple, float* rewards,
@@ -488,6 +503,16 @@ int a3c_engine_destroy(a3c_engine* eng);
 int a3c_engine_set_optimizer(a3c_engine* eng, int kind, double beta1, double beta2, double eps);
 int a3c_engine_adam_powers(a3c_engine* eng, double* beta1_power, double* beta2_power, void* stream);
 int a3c_engine_set_adam_powers(a3c_engine* eng, double beta1_power, double beta2_power, void* stream);
+/* Catch's rule parameters for the engine's device envs (a3c_env_set_catch_rules has the rules; DESIGN
+ * 4k).  A setter as the optimizer's, for the same reason.  It only records the rules: until the next
+ * a3c_engine_reset -- which renders the pool with them, resets the envs and zeroes the play context --
+ * rollout, iterate, play and every other entry that needs a reset return A3C_ERR_STATE.
+ * A3C_ERR_INVALID, before anything touches the device and in this order: visible_rows outside 1..10,
+ * frozen_rows outside 0..8, eng NULL, an engine whose game is not Catch.  A3C_ERR_STATE: a computed
+ * gradient not yet applied.  A hyperparameter: not in the checkpoint's state.  An engine that never
+ * calls it launches what it launched without it, and its state blob is byte for byte the same.
+ * python async-rl-tensorflow_amd/main.py --mode engine --lstm true --env_name CatchMemory-v0 */
+int a3c_engine_set_catch_rules(a3c_engine* eng, int visible_rows, int frozen_rows);
 /* fill the frame pool, reset the envs (new_random_game, environment.py:35-40), fill each
  * history with 4 copies of the first screen (agent.py:37-38) and initialise params
  * from host memory (nullable -> keep), rms slot = 1, mom = 0 (Adam: m = v = 0, products = 1). */
