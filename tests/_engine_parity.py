@@ -71,8 +71,9 @@ REF_KEYS = ('target_q_update_step', 'learning_rate', 'frame84', 'double_q', 'ep_
             'literal_adv', 'random_start', 'action_repeat')
 
 
-def build(algo, A, E, n, lives, seed, frames=48, use_graph=False, scale=4.0, **kw):
-    """An engine and an oracle from the same seed and initial parameters (stddev 0.02*scale).
+def build(algo, A, E, n, lives, seed, frames=48, use_graph=False, scale=4.0, params=None, **kw):
+    """An engine and an oracle from the same seed and initial parameters (stddev 0.02*scale, or
+    params(names_shapes) -> {name: array} where given).
     external_env=True: the engine's frames come from host-stepped envs (no device frame pool)."""
     from src.engine import Engine
     from src.initializers import init_params, flatten_host
@@ -81,7 +82,7 @@ def build(algo, A, E, n, lives, seed, frames=48, use_graph=False, scale=4.0, **k
     eng = Engine(num_envs=E, n_step=n, action_size=A, algo=algo, start_lives=lives, num_frames=eng_frames, seed=seed,
                  use_graph=use_graph, **kw)
     ns = param_names_shapes(A, algo, dqn_type=kw.get('dqn_type', 'nips'))
-    p = init_params(ns, seed=seed, stddev=0.02 * scale)
+    p = init_params(ns, seed=seed, stddev=0.02 * scale) if params is None else params(ns)
     eng.reset(flatten_host(ns, eng.offsets, eng.params.numel(), p))
     ref = EngineRef(p, E, n, A, algo, lives, frames, seed, **{k: v for k, v in kw.items() if k in REF_KEYS})
     ref.reset()
