@@ -1346,7 +1346,7 @@ extern "C" int a3c_engine_set_catch_rules(a3c_engine* e, int visible_rows, int f
   if (e->grad_ready && !e->grad_applied)
     return a3c_set_error(A3C_ERR_STATE, "a3c_engine_set_catch_rules", "a gradient is pending: apply it first");
   A3C_CHECK(hipDeviceSynchronize());      // (the engine's streams: nothing in flight steps an env)
-  e->envp.catch_visible = (int16_t)visible_rows;
+  e->envp.catch_visible = (int16_t)(visible_rows | (e->envp.catch_visible & CATCH_FIRST_SCREEN_BIT));
   e->envp.catch_frozen = (int16_t)frozen_rows;
   // the captured graphs hold the other rules in their kernel arguments
   for (int i = 0; i < NGRAPH; ++i)
@@ -1356,6 +1356,27 @@ extern "C" int a3c_engine_set_catch_rules(a3c_engine* e, int visible_rows, int f
       e->captured[i] = false;
     }
   e->reset_done = false;
+  return 0;
+}
+
+// first_screen: a bit of the Catch-only word of envp, read by the Catch instantiations of
+// the training head kernels at a terminal.  No reset: it changes what the next terminal writes.
+extern "C" int a3c_engine_set_first_screen(a3c_engine* e, int on) {
+  if (on != 0 && on != 1) return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_set_first_screen", "on must be 0 or 1");
+  if (!e) return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_set_first_screen", "null");
+  if (e->game != A3C_GAME_CATCH)
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_set_first_screen", "the engine's game is not Catch");
+  if (e->grad_ready && !e->grad_applied)
+    return a3c_set_error(A3C_ERR_STATE, "a3c_engine_set_first_screen", "a gradient is pending: apply it first");
+  A3C_CHECK(hipDeviceSynchronize());      // (the engine's streams: nothing in flight steps an env)
+  e->envp.catch_visible = (int16_t)(catch_visible_rows(e->envp) | (on ? CATCH_FIRST_SCREEN_BIT : 0));
+  // the captured graphs hold the other value in their kernel arguments
+  for (int i = 0; i < NGRAPH; ++i)
+    if (e->captured[i]) {
+      (void)hipGraphExecDestroy(e->gexec[i]);
+      (void)hipGraphDestroy(e->graph[i]);
+      e->captured[i] = false;
+    }
   return 0;
 }
 
@@ -1375,7 +1396,7 @@ extern "C" int a3c_engine_reset(a3c_engine* e, const float* host_params, void* s
   A3C_CHECK(hipMemsetAsync(e->ring, 0, (size_t)e->E * e->R * PLANE, s));
   if (!e->ext) {
     rc = e->envp.game == A3C_GAME_CATCH     // (rendered from the frame index, not hashed: DESIGN §4g)
-             ? a3c_pool_render_catch_launch(e->pool, e->cfg.num_frames, e->envp.catch_visible, s)
+             ? a3c_pool_render_catch_launch(e->pool, e->cfg.num_frames, catch_visible_rows(e->envp), s)
              : a3c_pool_fill_launch(e->pool, e->cfg.num_frames, e->k0, e->k1, s, frame_bytes(e));
     if (rc) return rc;
     rc = a3c_env_init_launch(e->envp, e->env, e->E, e->pool, e->ring, e->R, e->counters, s, e->frame84);

@@ -104,6 +104,13 @@ struct EnvParams {
 };
 static_assert(sizeof(EnvParams) == 40, "EnvParams fills its padding, it does not grow");
 inline void env_params_catch_default(EnvParams& p) { p.catch_visible = 10; p.catch_frozen = 0; }
+// first_screen (a3c_engine_set_first_screen) rides in bit 4 of catch_visible, whose rule
+// value is at most 10: no kernel argument moves.  No device code reads the rule value (the pool
+// render gets it from the host), so catch_first_screen is the word's only device reader, and only in
+// the Catch instantiations of the training head kernels.
+#define CATCH_FIRST_SCREEN_BIT 16
+__host__ __device__ inline int catch_visible_rows(const EnvParams& p) { return p.catch_visible & (CATCH_FIRST_SCREEN_BIT - 1); }
+__host__ __device__ inline bool catch_first_screen(const EnvParams& p) { return (p.catch_visible & CATCH_FIRST_SCREEN_BIT) != 0; }
 
 struct EnvBufs {
   uint32_t* episode;

@@ -572,6 +572,11 @@ __device__ inline int32_t head_act_env(const float* __restrict__ h3, const float
       s_term = s.terminal;
       if (s.terminal) {
         game_new_random_game<GAME>(s, sel.envp, id);           // agent.py:66-67
+        if constexpr (GAME == A3C_GAME_CATCH) {
+          // first_screen: the history gets the new game's first screen (agent.py:366-367's
+          // rule, in training); its frame + 1 rides above s_term's terminal bit across the barrier
+          if (catch_first_screen(sel.envp)) s_term = 1u | (uint32_t)(s.frame + 1) << 1;
+        }
         env_store(sel.envb, nxt, s);
       } else {
         env_store(sel.envb, nxt, s, false);                    // frame: after the action draw
@@ -585,6 +590,9 @@ __device__ inline int32_t head_act_env(const float* __restrict__ h3, const float
     float reward = 0.f;
     if constexpr (GAME == A3C_GAME_CATCH) {
       frame = catch_act_post(s_draw, (uint32_t)s_act, reward);   // < CATCH_FRAMES <= the pool's frames
+      if constexpr (!PLAY) {
+        if (s_term >> 1) frame = (int32_t)(s_term >> 1) - 1;     // catch_reset's frame: row 0, < CATCH_FRAMES
+      }
     } else {
       frame = env_frame_of(s_draw + sel.frame_salt, (uint32_t)s_act, sel.envp);
 #ifdef A3C_ABL_FRAME

@@ -211,7 +211,13 @@ __device__ inline int32_t head_act(float myz, int lane, int A, const HeadSelect&
       sel.terms[e] = (uint8_t)s.terminal;
       sel.frames_out[e] = s.frame;
       frame = s.frame;
-      if (s.terminal) game_new_random_game<GAME>(s, sel.envp, id);    // agent.py:66-67
+      if (s.terminal) {
+        game_new_random_game<GAME>(s, sel.envp, id);                  // agent.py:66-67
+        if constexpr (GAME == A3C_GAME_CATCH) {
+          // first_screen: the screen that enters the ring is the new game's first
+          if (catch_first_screen(sel.envp)) sel.frames_out[e] = frame = s.frame;
+        }
+      }
       env_store(sel.envb, nxt, s);
     }
   }

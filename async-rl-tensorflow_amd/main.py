@@ -13,6 +13,8 @@ accepted but the TF ps/worker cluster is replaced by one process per GPU under t
   python main.py --mode engine --algo q --sarsa true --n_step 5 --env_name Catch-v0     Sarsa (--q_nstep true: n-step)
   python main.py --mode engine --algo q --optimizer adam --env_name Catch-v0             shared Adam instead of RMSProp
   python main.py --mode engine --lstm true --env_name CatchMemory-v0   Catch that only a head with memory learns
+  python main.py --mode engine --lstm true --env_name CatchMemory-v0 --first_screen true   ... with each episode's first
+                 screen shown to the training rollouts, without which it is not learned
   python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 main.py --mode engine
   python main.py --mode engine --is_train false --n_episode 100     evaluate the newest checkpoint
   python main.py --mode engine --is_train false --play_refill true  ... refilling finished envs (no waves)
@@ -104,6 +106,10 @@ def parse_flags(argv=None):
                       'PS semantics); sum = one all-reduce, one RMSProp step of the summed gradients')
   p.add_argument('--lstm', type=str2bool, default=False,
                  help='engine mode, a3c: the 256-cell LSTM policy head (BASELINE config 5, DESIGN §4b)')
+  p.add_argument('--first_screen', type=str2bool, default=False,
+                 help='engine mode, Catch-v0 / CatchMemory-v0 on the device: at a terminal the training rollout adds '
+                      "the new game's first screen to the history (as play does, agent.py:366-367) where the "
+                      "reference loop (agent.py:59-67) adds the landing's; play ignores it (DESIGN §4l)")
   p.add_argument('--dqn_type', choices=['nips', 'nature'], default='nips',
                  help="conv trunk of network.py:30-50 (Network(DQN_type=...)): nips (fused kernels) or nature "
                       "(implicit-GEMM kernels, nature.hip; --algo a3c)")
@@ -147,6 +153,12 @@ def engine_options(flags):
     raise ValueError('--sarsa is a Q-learning option (its target is a Q value, DESIGN §4i): use it with --algo q')
   if flags.sarsa and flags.double_q:
     raise ValueError('--sarsa with --double_q: double Q picks the argmax, Sarsa the taken action (DESIGN §4i)')
+  first_screen = bool(getattr(flags, 'first_screen', False))
+  if first_screen and game_kind(flags.env_name) != 'catch':
+    raise ValueError('--first_screen is an option of the device game Catch (--env_name Catch-v0 or CatchMemory-v0, '
+                     "DESIGN §4l): %s's frames are hashed, and host or gym envs are not covered" % flags.env_name)
+  if first_screen and flags.envs_on != 'device':
+    raise ValueError('--first_screen needs --envs_on device (got %s)' % flags.envs_on)
   adam = adam_options(flags)
   if adam and flags.update == 'hogwild':
     raise ValueError('--optimizer adam with --update hogwild: the lock-free shards keep no shared step count for '
@@ -162,6 +174,8 @@ def engine_options(flags):
     kw['sarsa'] = 1
   if flags.dqn_type == 'nature':
     kw['dqn_type'] = 'nature'
+  if first_screen:
+    kw['first_screen'] = True
   return kw
 
 
@@ -446,6 +460,8 @@ def main(argv=None):
     raise ValueError('--q_nstep is an engine option: --mode agent is the per-step Q-learning loop (one-step targets)')
   if flags.mode == 'agent' and flags.sarsa:
     raise ValueError('--sarsa is an engine option: --mode agent is the per-step Q-learning loop (max targets)')
+  if flags.mode == 'agent' and flags.first_screen:
+    raise ValueError('--first_screen is an engine option: --mode agent is the reference loop (agent.py:59-67) as it stands')
   random.seed(flags.random_seed)
   np.random.seed(flags.random_seed)
   from config import get_config

@@ -158,6 +158,7 @@ SIGNATURES = {
     'a3c_engine_adam_powers': (c_int, [c_void_p, ctypes.POINTER(c_double), ctypes.POINTER(c_double), c_void_p]),
     'a3c_engine_set_adam_powers': (c_int, [c_void_p, c_double, c_double, c_void_p]),
     'a3c_engine_set_catch_rules': (c_int, [c_void_p, c_int, c_int]),
+    'a3c_engine_set_first_screen': (c_int, [c_void_p, c_int]),
     'a3c_engine_reset': (c_int, [c_void_p, c_void_p, c_void_p]),
     'a3c_engine_rollout_grad': (c_int, [c_void_p, c_void_p]),
     'a3c_engine_apply': (c_int, [c_void_p, c_void_p]),
@@ -224,7 +225,7 @@ OPTIONAL_IN_OLD_BUILDS = MEASUREMENT_ONLY + ('a3c_engine_exchange_split', 'a3c_e
                                              'a3c_boot_action', 'a3c_sarsa_target', 'a3c_clip_adam_apply',
                                              'a3c_engine_set_optimizer', 'a3c_engine_adam_powers',
                                              'a3c_engine_set_adam_powers', 'a3c_engine_set_catch_rules',
-                                             'a3c_env_set_catch_rules')
+                                             'a3c_env_set_catch_rules', 'a3c_engine_set_first_screen')
 
 KER_CONV12_FWD, KER_FC_FWD, KER_ENV_STEP, KER_CONV_BWD, KER_HEAD_SCREEN, KER_HEAD_SCREEN_CONV12, KER_FC_PART = 0, 1, 2, 3, 4, 5, 6
 # nature trunk passes (include/a3c_hip.h A3C_KER_NAT_*)

@@ -56,7 +56,7 @@ def _view(ptr, shape, dtype):
 class Engine:
     def __init__(self, num_envs=256, n_step=5, action_size=6, algo='a3c', start_lives=0, num_frames=None,
                  seed=123, env_id_base=0, world_size=1, use_graph=False, overlap=False, lstm=False,
-                 external_env=False, dqn_type='nips', game='synth', catch_rules=None, **overrides):
+                 external_env=False, dqn_type='nips', game='synth', catch_rules=None, first_screen=None, **overrides):
         """game: 'synth' (the synthetic Atari stand-in) or 'catch' (Catch-v0, DESIGN §4g: action_size 3,
         start_lives 0, device envs, raw RGB pool; random_start is ignored).  num_frames=None: 1024
         frames (Catch needs its 640: a smaller explicit value is rejected by the library).
@@ -69,7 +69,14 @@ class Engine:
         catch_rules=None | (visible_rows, frozen_rows) (game 'catch'; None: Catch-v0's (10, 0),
         and no call is made): a3c_engine_set_catch_rules right after the create -- the ball is drawn in
         rows < visible_rows only, the paddle is frozen in the first frozen_rows steps; kept as
-        ``catch_rules``.  environment.catch_rules_of(env_name) is the pair of a game's name."""
+        ``catch_rules``.  environment.catch_rules_of(env_name) is the pair of a game's name.
+        first_screen=None | False | True (game 'catch'; None: off, and no call is made):
+        a3c_engine_set_first_screen right after the create -- at a terminal the training rollout writes
+        the new game's first screen into the history where the reference loop (agent.py:59-67) writes
+        the landing's, as Agent.play does (agent.py:366-367); kept as ``first_screen``.  Play ignores it."""
+        if first_screen is not None and game != 'catch':
+            raise ValueError('first_screen is an option of game catch, not of %r' % (game,))
+        self.first_screen = bool(first_screen)
         if catch_rules is not None:
             if game != 'catch':
                 raise ValueError('catch_rules are the rules of game catch, not of %r' % (game,))
@@ -140,6 +147,8 @@ class Engine:
             check(lib().a3c_engine_set_optimizer(h, OPTIMIZERS[optimizer], *adam), 'a3c_engine_set_optimizer')
         if catch_rules is not None:
             check(lib().a3c_engine_set_catch_rules(h, *catch_rules), 'a3c_engine_set_catch_rules')
+        if first_screen is not None:
+            check(lib().a3c_engine_set_first_screen(h, int(bool(first_screen))), 'a3c_engine_set_first_screen')
         b = _lib.EngineBuffers()
         check(lib().a3c_engine_get_buffers(h, ctypes.byref(b)), 'a3c_engine_get_buffers')
         self._b = b
@@ -171,6 +180,11 @@ class Engine:
                      'episode': _view(b.env_episode, (2, E), torch.int32),
                      'ep_step': _view(b.env_step, (2, E), torch.int32),
                      'ep_len': _view(b.env_len, (2, E), torch.int32)}
+
+    def set_first_screen(self, on):
+        """a3c_engine_set_first_screen between iterations: no reset, the next terminal follows it."""
+        check(lib().a3c_engine_set_first_screen(self._h, int(bool(on))), 'a3c_engine_set_first_screen')
+        self.first_screen = bool(on)
 
     def _slot_views(self, k):
         b = _lib.EngineBuffers()

@@ -513,6 +513,22 @@ int a3c_engine_set_adam_powers(a3c_engine* eng, double beta1_power, double beta2
  * calls it launches what it launched without it, and its state blob is byte for byte the same.
  * python async-rl-tensorflow_amd/main.py --mode engine --lstm true --env_name CatchMemory-v0 */
 int a3c_engine_set_catch_rules(a3c_engine* eng, int visible_rows, int frozen_rows);
+/* first_screen: what a Catch engine's training rollouts write into the history at a
+ * terminal.  on = 0, the default, is the reference worker loop (agent.py:59-67): the landing's screen
+ * is added and the new game started at agent.py:66-67 shows nothing until its first act, so the first
+ * frame of an episode that training sees is its row 1.  on = 1: at a terminal of env e in rollout step
+ * t the screen written to ring slot (tau + t + 1) % R is that of the new game's first state -- the rule
+ * Agent.play follows at agent.py:366-367 -- and the landing's screen, whose only reader is a next state
+ * that every target multiplies by (1 - terminal), is not written.  One slot, not four: the three older
+ * planes belong to the states before.  Reward, terminal, env state, action draw, the LSTM carry and
+ * the target cadence are unchanged; the per-step frame indices the engine records are those of the
+ * screens written.  Play is not affected.  A setter, as the two above: it needs no reset and takes
+ * effect at the next terminal; it drops captured graphs.  A3C_ERR_INVALID, before anything touches the
+ * device and in this order: on not 0 or 1, eng NULL, an engine whose game is not Catch (the external-
+ * env engine included).  A3C_ERR_STATE: a computed gradient not yet applied.  A hyperparameter: not in
+ * the checkpoint's state.  An engine that never calls it launches what it launched without it.
+ * python async-rl-tensorflow_amd/main.py --mode engine --lstm true --env_name CatchMemory-v0 --first_screen true */
+int a3c_engine_set_first_screen(a3c_engine* eng, int on);
 /* fill the frame pool, reset the envs (new_random_game, environment.py:35-40), fill each
  * history with 4 copies of the first screen (agent.py:37-38) and initialise params
  * from host memory (nullable -> keep), rms slot = 1, mom = 0 (Adam: m = v = 0, products = 1). */
