@@ -94,7 +94,7 @@ extern "C" int a3c_forward(const a3c_net_desc* net, const float* params, const u
   int rc = a3c_prep_fwd_launch(L, params, prep, (hipStream_t)stream);
   if (rc) return rc;
   return a3c_forward_launch(L, params, prep, contiguous_states(states, B), B, act_l1, act_l2, act_l3, z, sel,
-                            (hipStream_t)stream);
+                            (hipStream_t)stream, LAUNCH_ALONE);
 }
 
 extern "C" int a3c_select_action(int mode, const float* z, int64_t B, int zs, int A, const float* eps,
@@ -184,5 +184,5 @@ extern "C" int a3c_loss_backward(const a3c_net_desc* net, const float* params, c
   a3c_init_once();
   return a3c_backward_launch(L, params, contiguous_states(states, B), B, act_l1, act_l2, act_l3, z, actions,
                              target, beta, literal_adv, grads, loss_out, align_ws(workspace),
-                             (hipStream_t)stream);
+                             (hipStream_t)stream, LAUNCH_ALONE);
 }

@@ -24,7 +24,7 @@
 
 void a3c_init_once();
 int a3c_fc_fwd_launch(const float* A, const float* W, const float* bias, float* C, int64_t M, hipStream_t s,
-                      const float* Wrows = nullptr);
+                      const LaunchMode& m, const float* Wrows = nullptr);
 
 // Per-rollout buffers.  Sync mode has one slot whose params are the live parameters and whose
 // tau is the live frame counter.  Overlap mode (cfg.overlap = 1) has two: rollout k fills slot
@@ -103,6 +103,7 @@ struct a3c_engine {
   EnvBufs env;
   EnvParams envp;
   int overlap, nslot;
+  LaunchMode mode;         // the kernel variants of every launch of this engine (fixed at create)
   int fused_screen;        // 1: screen kernel fused into the head (k_head_screen)
   int frame84;             // cfg.frame84: pre-sized 84x84 pool frames (measurement mode M2)
   int game;                // A3C_GAME_*: the device envs' game (a3c_engine_create_ex)
@@ -226,14 +227,21 @@ extern "C" void a3c_engine_config_default(a3c_engine_config* c) {
   c->split_exchange = 1;   // several GPUs: the fc / head exchange under the conv backward
 }
 
-extern "C" int a3c_engine_destroy(a3c_engine* e) {
-  if (!e) return 0;
-  if (e->rs) (void)hipStreamSynchronize(e->rs);
+// the captured graphs hold their launches' kernel arguments: dropped when a setter changes one
+// (the next run_graph captures again)
+static void drop_graphs(a3c_engine* e) {
   for (int i = 0; i < NGRAPH; ++i)
     if (e->captured[i]) {
       (void)hipGraphExecDestroy(e->gexec[i]);
       (void)hipGraphDestroy(e->graph[i]);
+      e->captured[i] = false;
     }
+}
+
+extern "C" int a3c_engine_destroy(a3c_engine* e) {
+  if (!e) return 0;
+  if (e->rs) (void)hipStreamSynchronize(e->rs);
+  drop_graphs(e);
   if (e->rs) (void)hipStreamDestroy(e->rs);
   if (e->gs) (void)hipStreamDestroy(e->gs);
   if (e->ev_gfork) (void)hipEventDestroy(e->ev_gfork);
@@ -251,6 +259,7 @@ extern "C" int a3c_engine_destroy(a3c_engine* e) {
 static int frame_bytes(const a3c_engine* e) { return e->frame84 ? PLANE : SCREEN_H * SCREEN_W * 3; }
 
 static bool boot_bwd(const a3c_engine* e);
+static bool bwd_bound(const a3c_engine* e);
 static int l2bits_choice(const a3c_engine* e);
 extern "C" void a3c_engine_opts_default(a3c_engine_opts* o) {
   memset(o, 0, sizeof(*o));
@@ -279,65 +288,41 @@ extern "C" int a3c_engine_create_opts(const a3c_engine_config* cfg, const a3c_en
   a3c_engine* e = new (std::nothrow) a3c_engine();
   if (!e) return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_create", "oom");
   e->cfg = *cfg;
+  // the one failure exit (a3c_engine_destroy frees whatever the engine holds by then)
+  auto fail = [&](const char* msg, int code = A3C_ERR_INVALID) {
+    a3c_engine_destroy(e);
+    return a3c_set_error(code, "a3c_engine_create", msg);
+  };
   if (a3c_make_layout(&cfg->net, &e->L) || cfg->num_envs < 1 || cfg->n_step < 1 || cfg->n_step > 64 ||
       cfg->num_frames < 1 || cfg->random_start < 1 || cfg->action_repeat < 1 || cfg->world_size < 1 ||
       (cfg->overlap && cfg->external_env) || (cfg->overlap && cfg->net.lstm_units && cfg->net.algo != A3C_ALGO_A3C) ||
-      (cfg->net.lstm_units && !cfg->overlap && cfg->n_step < 2)) {   // sync n=1 would read and
-                                                                       // write one state buffer
-    delete e;
-    return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_create", "bad config");
-  }
-  if (cfg->double_q && cfg->net.algo != A3C_ALGO_Q) {
-    delete e;
-    return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_create", "double_q is a Q-learning option (agent.py:176-184)");
-  }
-  if (!(cfg->gae_lambda >= 0.f && cfg->gae_lambda <= 1.f)) {
-    delete e;
-    return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_create", "gae_lambda must be in [0, 1]");
-  }
-  if (cfg->gae_lambda != 1.f && cfg->net.algo != A3C_ALGO_A3C) {
-    delete e;
-    return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_create", "gae_lambda != 1 is an a3c option (algo q has one-step TD targets)");
-  }
-  if (cfg->gae_lambda != 1.f && cfg->literal_adv) {
-    delete e;
-    return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_create",
-                         "gae_lambda != 1 with literal_adv: the lambda-return is a constant of the gradient");
-  }
-  if (cfg->q_nstep != 0 && cfg->q_nstep != 1) {
-    delete e;
-    return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_create", "q_nstep must be 0 or 1");
-  }
-  if (cfg->q_nstep && cfg->net.algo != A3C_ALGO_Q) {
-    delete e;
-    return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_create",
-                         "q_nstep is a Q-learning option (algo a3c has its n-step returns already)");
-  }
-  if (game != A3C_GAME_SYNTH && game != A3C_GAME_CATCH) {
-    delete e;
-    return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_create", "unknown game");
-  }
-  if (sarsa != 0 && sarsa != 1) {
-    delete e;
-    return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_create", "sarsa must be 0 or 1");
-  }
-  if (sarsa && cfg->net.algo != A3C_ALGO_Q) {
-    delete e;
-    return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_create", "sarsa is a Q-learning option (its target is a Q value)");
-  }
-  if (sarsa && cfg->double_q) {
-    delete e;
-    return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_create",
-                         "sarsa with double_q: double Q picks the argmax, Sarsa the taken action");
-  }
+      (cfg->net.lstm_units && !cfg->overlap && cfg->n_step < 2))   // (sync n=1 would read and write
+    return fail("bad config");                                     // one state buffer)
+  if (cfg->double_q && cfg->net.algo != A3C_ALGO_Q)
+    return fail("double_q is a Q-learning option (agent.py:176-184)");
+  if (!(cfg->gae_lambda >= 0.f && cfg->gae_lambda <= 1.f))
+    return fail("gae_lambda must be in [0, 1]");
+  if (cfg->gae_lambda != 1.f && cfg->net.algo != A3C_ALGO_A3C)
+    return fail("gae_lambda != 1 is an a3c option (algo q has one-step TD targets)");
+  if (cfg->gae_lambda != 1.f && cfg->literal_adv)
+    return fail("gae_lambda != 1 with literal_adv: the lambda-return is a constant of the gradient");
+  if (cfg->q_nstep != 0 && cfg->q_nstep != 1)
+    return fail("q_nstep must be 0 or 1");
+  if (cfg->q_nstep && cfg->net.algo != A3C_ALGO_Q)
+    return fail("q_nstep is a Q-learning option (algo a3c has its n-step returns already)");
+  if (game != A3C_GAME_SYNTH && game != A3C_GAME_CATCH)
+    return fail("unknown game");
+  if (sarsa != 0 && sarsa != 1)
+    return fail("sarsa must be 0 or 1");
+  if (sarsa && cfg->net.algo != A3C_ALGO_Q)
+    return fail("sarsa is a Q-learning option (its target is a Q value)");
+  if (sarsa && cfg->double_q)
+    return fail("sarsa with double_q: double Q picks the argmax, Sarsa the taken action");
   // Catch: its frame index is its state, f < 640 -- the pool must hold those frames, as
   // raw RGB, on the device
   if (game == A3C_GAME_CATCH && (cfg->num_frames < 640 || cfg->net.action_size != 3 || cfg->start_lives != 0 ||
-                                      cfg->frame84 || cfg->external_env)) {
-    delete e;
-    return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_create",
-                         "Catch needs num_frames >= 640, action_size 3, start_lives 0, no frame84, no external_env");
-  }
+                                      cfg->frame84 || cfg->external_env))
+    return fail("Catch needs num_frames >= 640, action_size 3, start_lives 0, no frame84, no external_env");
   e->game = game;
   e->sarsa = sarsa;
   a3c_init_once();
@@ -365,15 +350,11 @@ extern "C" int a3c_engine_create_opts(const a3c_engine_config* cfg, const a3c_en
   if (e->nat) {
     e->fuse_conv = 0;
     e->fc_split = 0;
-    if (e->ext) {
-      delete e;
-      return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_create", "the nature trunk runs with device envs");
-    }
+    if (e->ext)
+      return fail("the nature trunk runs with device envs");
   }
-  if (e->frame84 && (e->ext || !e->fused_screen)) {   // the copy lives in the fused head kernels
-    delete e;
-    return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_create", "frame84 needs device envs and the fused screen");
-  }
+  if (e->frame84 && (e->ext || !e->fused_screen))   // the copy lives in the fused head kernels
+    return fail("frame84 needs device envs and the fused screen");
   e->nslot = e->overlap ? 2 : 1;
   // ring: the states of one rollout (frames tau-3 .. tau+n); overlap keeps two rollouts' frames
   e->R = (e->overlap ? 2 * e->n : e->n) + HIST + (cfg->net.algo == A3C_ALGO_Q ? 1 : 0);
@@ -472,32 +453,29 @@ extern "C" int a3c_engine_create_opts(const a3c_engine_config* cfg, const a3c_en
   ALLOC(e->fctick, fctick_bytes(E));
   if (e->sarsa)   // (behind everything an engine without it allocates)
     for (int k = 0; k < e->nslot; ++k) ALLOC(e->slot[k].boot_action, E * 4);
-  if (hipError_t st = hipMemset(e->fctick, 0, fctick_bytes(E))) {
-    a3c_engine_destroy(e);
-    return a3c_set_error((int)st, "a3c_engine_create", "hipMemset failed");
-  }
+  if (hipError_t st = hipMemset(e->fctick, 0, fctick_bytes(E)))
+    return fail("hipMemset failed", (int)st);
 #undef ALLOC
   if (a3c_make_tab(L.nt, L.off, L.size, L.total, &e->tt) ||
-      (e->nat ? a3c_nat_fused_tab(L, &e->tt_f) : a3c_fused_tab(L, &e->tt_f))) {
-    a3c_engine_destroy(e);
-    return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_create", "tensor table");
-  }
+      (e->nat ? a3c_nat_fused_tab(L, &e->tt_f) : a3c_fused_tab(L, &e->tt_f)))
+    return fail("tensor table");
   {
     bool ok = hipStreamCreateWithFlags(&e->gs, hipStreamNonBlocking) == hipSuccess &&
               hipEventCreateWithFlags(&e->ev_gfork, hipEventDisableTiming) == hipSuccess &&
               hipEventCreateWithFlags(&e->ev_gjoin, hipEventDisableTiming) == hipSuccess;
-    if (!ok) {
-      a3c_engine_destroy(e);
-      return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_create", "stream/event creation failed");
-    }
+    if (!ok)
+      return fail("stream/event creation failed");
   }
   // the split exchange needs eager launches (its event is recorded mid-backward) and a peer
   e->split = cfg->split_exchange && cfg->world_size > 1 && !cfg->use_graph && !e->nat;
   e->l2bits = e->nat ? 0 : l2bits_choice(e);
-  if (e->split && hipEventCreateWithFlags(&e->ev_head, hipEventDisableTiming) != hipSuccess) {
-    a3c_engine_destroy(e);
-    return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_create", "event creation failed");
-  }
+  // One mode for every launch of the engine -- rollout, backward, play, the host-env path, the
+  // timing hook: its three inputs are fixed by now, and no phase needs a value of its own.
+  // fcp_split is read by the two fc_part launchers alone, which the gradient path and play never
+  // reach (they pass no fc_part buffer), and bwd_bound inside a3c_backward_launch alone.
+  e->mode = {e->overlap != 0, bwd_bound(e), e->frame84 ? 2 : 4};
+  if (e->split && hipEventCreateWithFlags(&e->ev_head, hipEventDisableTiming) != hipSuccess)
+    return fail("event creation failed");
   if (e->overlap) {
     // the rollout is a serial chain of small kernels: give its stream the higher priority so
     // its workgroups are dispatched first when the concurrent backward frees CU resources
@@ -519,10 +497,8 @@ extern "C" int a3c_engine_create_opts(const a3c_engine_config* cfg, const a3c_en
     e->wait_value = e->cfg.world_size == 1;
     e->wait_value = A3C_KNOB("A3C_WAIT_VALUE", e->wait_value) != 0;
 
-    if (!ok) {
-      a3c_engine_destroy(e);
-      return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_create", "stream/event creation failed");
-    }
+    if (!ok)
+      return fail("stream/event creation failed");
   }
   e->envp.k0 = e->k0; e->envp.k1 = e->k1;
   e->envp.P = e->cfg.num_frames;
@@ -536,20 +512,16 @@ extern "C" int a3c_engine_create_opts(const a3c_engine_config* cfg, const a3c_en
   // per-env final epsilon (main.py:68 samples ep_end per worker from {0.1, 0.01, 0.5})
   std::vector<int32_t> idx(E);
   for (int64_t i = 0; i < E; ++i) idx[i] = (int32_t)i;
-  if (hipMemcpy(e->ext_idx, idx.data(), E * 4, hipMemcpyHostToDevice) != hipSuccess) {
-    a3c_engine_destroy(e);
-    return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_create", "hipMemcpy");
-  }
+  if (hipMemcpy(e->ext_idx, idx.data(), E * 4, hipMemcpyHostToDevice) != hipSuccess)
+    return fail("hipMemcpy");
   std::vector<float> ee(E);
   static const float choices[3] = {0.1f, 0.01f, 0.5f};
   for (int64_t i = 0; i < E; ++i) {
     u32x4 x = philox4x32((uint32_t)(cfg->env_id_base + i), 0u, 0u, 11u, e->k0, e->k1);
     ee[i] = choices[x.x % 3u];
   }
-  if (hipMemcpy(e->ep_end, ee.data(), E * 4, hipMemcpyHostToDevice) != hipSuccess) {
-    a3c_engine_destroy(e);
-    return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_create", "hipMemcpy");
-  }
+  if (hipMemcpy(e->ep_end, ee.data(), E * 4, hipMemcpyHostToDevice) != hipSuccess)
+    return fail("hipMemcpy");
   *out = e;
   return 0;
 }
@@ -621,14 +593,27 @@ __global__ void __launch_bounds__(256) k_stats(const float* __restrict__ rraw, c
   }
 }
 
-// the epsilon schedule of agent.py:142-144 at the worker's own step, evaluated by the head kernel
-// (sel_eps in net_fwd.hip): the workers' base step counters[2] plus the env steps taken so far
-// (tau - (HIST-1)).  A separate per-step schedule kernel cost Q sync 3% (round-5 bisect).
-static void set_eps_schedule(const a3c_engine* e, HeadSelect& sel) {
-  sel.ep_end = e->ep_end;
-  sel.ep_start = e->cfg.ep_start;
-  sel.ep_end_t = e->cfg.ep_end_t;
-  sel.learn_start = e->cfg.learn_start;
+// The action draw of the engine's envs at step *tau_ptr + tau_add: the fields every draw shares.
+// eps: the per-env epsilon (play).  Null: mode 1 takes the epsilon schedule of agent.py:142-144 at
+// the worker's own step, evaluated by the head kernel (sel_eps in net_fwd.hip): the workers' base
+// step counters[2] plus the env steps taken so far (tau - (HIST-1)); q engines are synchronous.  A
+// separate per-step schedule kernel cost Q sync 3% (round-5 bisect).
+static HeadSelect head_select(const a3c_engine* e, int mode, const int64_t* tau_ptr, int64_t tau_add,
+                              const float* eps = nullptr) {
+  HeadSelect sel = {};
+  sel.mode = mode;
+  sel.k0 = e->k0; sel.k1 = e->k1;
+  sel.tau_ptr = tau_ptr; sel.tau_add = tau_add;
+  sel.env_id_base = e->cfg.env_id_base; sel.E = e->E;
+  if (eps) {
+    sel.eps = eps;
+  } else if (mode == 1) {
+    sel.ep_end = e->ep_end;
+    sel.ep_start = e->cfg.ep_start;
+    sel.ep_end_t = e->cfg.ep_end_t;
+    sel.learn_start = e->cfg.learn_start;
+  }
+  return sel;
 }
 
 static StateAddr ring_addr(const a3c_engine* e, int tau_offset, const int64_t* tau_ptr) {
@@ -704,18 +689,6 @@ static OptParams opt_params(const a3c_engine* e, const Slot& sl) {
   return op;
 }
 
-// n env steps of every env (forward + action draw + env act fused into the head, then the
-// Environment.screen of the new frames into the ring) and the bootstrap forward.
-static int enqueue_rollout_impl(a3c_engine* e, const Slot& sl, hipStream_t s);
-static int enqueue_rollout(a3c_engine* e, const Slot& sl, hipStream_t s) {
-  a3c_set_shared_gpu(e->overlap != 0);
-  a3c_set_fcp_split(e->frame84 ? 2 : 4);
-  int rc = enqueue_rollout_impl(e, sl, s);
-  a3c_set_shared_gpu(false);
-  a3c_set_fcp_split(2);
-  return rc;
-}
-
 // the slot holding the rollout before sl's (its last LSTM state is sl's carry-in)
 static const Slot& prev_slot(const a3c_engine* e, const Slot& sl) {
   return e->nslot == 2 ? e->slot[&sl == &e->slot[0] ? 1 : 0] : sl;
@@ -727,7 +700,6 @@ static const Slot& prev_slot(const a3c_engine* e, const Slot& sl) {
 // M1 4.42-4.53M -> 4.56-4.57M), and rollout k+1's prep kernel bumps the sequence itself
 // (kernel_go: no write-value operation on the rollout stream); with an exchange, right behind
 // rollout k on the rollout stream
-static bool bwd_bound(const a3c_engine* e);
 static bool late_go(const a3c_engine* e) {
   static const int env = (int)A3C_AB_KNOB("A3C_LATE_GO", -1);   // A/B override
   // one GPU: M1 and M2 (M2 5.77M -> 5.83M since the conv backward runs one workgroup per CU);
@@ -763,17 +735,11 @@ static int enqueue_rollout_begin(a3c_engine* e, const Slot& sl, hipStream_t s) {
 static bool l2bits_on(const a3c_engine* e);
 static int l2bits_choice(const a3c_engine* e);
 static int enqueue_step(a3c_engine* e, const Slot& sl, int t, hipStream_t s) {
-  const a3c_engine_config& c = e->cfg;
   const NetLayout& L = e->L;
   const int E = e->E, n = e->n, zs = L.zs;
   const bool q = L.algo == A3C_ALGO_Q;
   const bool dev_env = !e->ext;
-  HeadSelect sel = {};
-  sel.mode = q ? 1 : 0;
-  sel.k0 = e->k0; sel.k1 = e->k1;
-  sel.tau_ptr = e->counters; sel.tau_add = t;
-  sel.env_ids = nullptr; sel.env_id_base = c.env_id_base; sel.E = E;
-  if (q) set_eps_schedule(e, sel);   // epsilon of this step, in the head (q engines are synchronous)
+  HeadSelect sel = head_select(e, q ? 1 : 0, e->counters, t);   // (q: epsilon of this step, in the head)
   const int64_t o = (int64_t)t * E;
   sel.actions = sl.actions + o;
   sel.env_on = dev_env ? 1 : 0;
@@ -825,10 +791,10 @@ static int enqueue_step(a3c_engine* e, const Slot& sl, int t, hipStream_t s) {
   if (e->nat)
     rc = a3c_nat_forward_launch(L, sl.P, nat_step_addr(e, t), E, sl.act_l1 + o * NT_A1,
                                 sl.act_l2 + o * NT_A2, sl.act_l3 + o * NT_FLAT, sl.act_l4 + o * NT_FC, sl.z + o * zs, sel,
-                                (const uint16_t*)sl.prep, e->nat_fws, s);
+                                (const uint16_t*)sl.prep, e->nat_fws, s, e->mode);
   else
     rc = a3c_forward_launch(L, sl.P, sl.prep, ring_addr(e, t, e->counters), E, sl.act_l1 + o * C1_P * C1_N,
-                              sl.act_l2 + o * FLAT, sl.act_l3 + o * FC, sl.z + o * zs, sel, s,
+                              sl.act_l2 + o * FLAT, sl.act_l3 + o * FC, sl.z + o * zs, sel, s, e->mode,
                               L.lstm ? &ls : nullptr, fuse && t > 0, has_next ? &nx : nullptr,
                               fc_split(e) ? e->fcpart : nullptr, l2bits_on(e) ? sl.l2m + o * C2_Q : nullptr);
   if (rc) return rc;
@@ -844,7 +810,8 @@ static int enqueue_rollout_end(a3c_engine* e, const Slot& sl, hipStream_t s) {
   const NetLayout& L = e->L;
   const int E = e->E, n = e->n;
   if (boot_bwd(e))      // the fc of s_n (conv ran in the last step's kernel) + the tau advance
-    return a3c_fc_part_launch(sl.scr_l2, (const float*)(sl.prep + PREP_W1S_BYTES), sl.fcboot, E, s, e->counters, n);
+    return a3c_fc_part_launch(sl.scr_l2, (const float*)(sl.prep + PREP_W1S_BYTES), sl.fcboot, E, s, e->mode,
+                              e->counters, n);
   if (L.algo != A3C_ALGO_Q) {
     const int64_t lastE = (int64_t)(n - 1) * E;
     HeadSelect none = {};
@@ -866,10 +833,10 @@ static int enqueue_rollout_end(a3c_engine* e, const Slot& sl, hipStream_t s) {
       // (no span record: s_n is the next rollout's s_0, whose step-0 launch keys the same record)
       return a3c_nat_forward_launch(L, sl.P, ring_addr(e, n, e->counters), E, x, x + E * NT_A1,
                                     x + E * (NT_A1 + NT_A2), x + E * (NT_A1 + NT_A2 + NT_FLAT), sl.z + e->nE * L.zs,
-                                    none, (const uint16_t*)sl.prep, e->nat_fws, s);
+                                    none, (const uint16_t*)sl.prep, e->nat_fws, s, e->mode);
     }
     int rc = a3c_forward_launch(L, sl.P, sl.prep, ring_addr(e, n, e->counters), E, nullptr, sl.scr_l2,
-                                sl.scr_l3, sl.z + e->nE * L.zs, none, s, L.lstm ? &ls : nullptr,
+                                sl.scr_l3, sl.z + e->nE * L.zs, none, s, e->mode, L.lstm ? &ls : nullptr,
                                 conv_fused(e),   // s_n's convs ran in the last step's kernel
                                 nullptr, fc_split(e) ? e->fcpart : nullptr);
     return rc;
@@ -935,7 +902,9 @@ extern "C" int64_t a3c_debug_wglog(void* host, int on, int reset) {
 }
 #endif
 
-static int enqueue_rollout_impl(a3c_engine* e, const Slot& sl, hipStream_t s) {
+// n env steps of every env (forward + action draw + env act fused into the head, then the
+// Environment.screen of the new frames into the ring) and the bootstrap forward.
+static int enqueue_rollout(a3c_engine* e, const Slot& sl, hipStream_t s) {
   mark(0, s);
   int rc = enqueue_rollout_begin(e, sl, s);
   for (int t = 0; t < e->n && !rc; ++t) rc = enqueue_step(e, sl, t, s);
@@ -944,9 +913,6 @@ static int enqueue_rollout_impl(a3c_engine* e, const Slot& sl, hipStream_t s) {
   return rc;
 }
 
-// returns / TD target, loss + backward over the slot's n*E samples, per-tensor norms (+ the
-// per-worker clip when gradients are exchanged across GPUs).
-static int enqueue_grad_impl(a3c_engine* e, const Slot& sl, hipStream_t s);
 // Overlapped runs where the backward stream, not the rollout, bounds the iteration: mode M2 (a
 // shorter rollout) and several GPUs (the exchange -- all-to-all, sharded apply, all-gather -- runs on
 // the backward's stream).  There the three backward GEMMs run as one launch with their folds
@@ -957,16 +923,6 @@ static bool bwd_bound(const a3c_engine* e) {
   static const int env = (int)A3C_AB_KNOB("A3C_BWD_BOUND", -1);   // A/B override
   if (env >= 0) return e->overlap && env != 0;
   return e->overlap && (e->frame84 || e->cfg.world_size > 1);
-}
-static int enqueue_grad(a3c_engine* e, const Slot& sl, hipStream_t s) {
-  // overlap: the backward shares CUs with the next rollout -> small-footprint kernel variants
-  a3c_set_shared_gpu(e->overlap != 0);
-  a3c_set_bwd_bound(bwd_bound(e));
-  mark(2, s);
-  int rc = enqueue_grad_impl(e, sl, s);
-  a3c_set_shared_gpu(false);
-  a3c_set_bwd_bound(false);
-  return rc;
 }
 
 #ifdef A3C_HOG
@@ -1054,8 +1010,12 @@ static int l2bits_choice(const a3c_engine* e) {   // at create (a test compares 
   return A3C_KNOB("A3C_L2BITS", bwd_bound(e) ? 1 : 0) != 0;
 }
 
-static int enqueue_grad_impl(a3c_engine* e, const Slot& sl, hipStream_t s) {
+// returns / TD target, loss + backward over the slot's n*E samples, per-tensor norms (+ the
+// per-worker clip when gradients are exchanged across GPUs).  Overlap: the backward shares CUs
+// with the next rollout -> small-footprint kernel variants (e->mode).
+static int enqueue_grad(a3c_engine* e, const Slot& sl, hipStream_t s) {
   const a3c_engine_config& c = e->cfg;
+  mark(2, s);
 #ifdef A3C_HOG
   {
     static const int hog_type = getenv("A3C_HOG_TYPE") ? atoi(getenv("A3C_HOG_TYPE")) : -1;
@@ -1078,75 +1038,43 @@ static int enqueue_grad_impl(a3c_engine* e, const Slot& sl, hipStream_t s) {
   const int E = e->E, n = e->n, zs = L.zs;
   const bool q = L.algo == A3C_ALGO_Q;
   int rc;
-  if (q && e->sarsa) {
-    // Sarsa: the slot's own parameters on s_n (double Q's launch); the target network on
-    // s_1..s_n (q_nstep: on s_n alone); then one kernel draws, from the slot's rows, the action the
-    // rollout's head would draw in s_n, at the slot's tau + n (sl.tau holds tau alone: the schedule's base
-    // step comes from the counters, where only a3c_engine_set_step writes it), and forms the targets at
-    // the taken actions -- as many launches as double Q
+  if (q) {
+    // The Q targets: [the slot's own parameters on s_n], the target network's prep + forward, the
+    // target kernel.
     HeadSelect none = {};
     none.mode = -1;
     none.E = E;
-    rc = a3c_forward_launch(L, sl.P, sl.prep, ring_addr(e, n, sl.tau), E, nullptr, sl.scr_l2, sl.scr_l3,
-                            sl.z + e->nE * zs, none, s);
-    if (rc) return rc;
-    HeadSelect sel = {};
-    sel.mode = 1;
-    sel.k0 = e->k0; sel.k1 = e->k1;
-    sel.tau_ptr = e->counters;
-    sel.env_ids = nullptr; sel.env_id_base = c.env_id_base; sel.E = E;
-    set_eps_schedule(e, sel);
-    const BootDraw bd = {sel, sl.tau, sl.z + e->nE * zs, sl.boot_action};
+    float* zboot = sl.z + e->nE * zs;   // the slot's bootstrap row block
+    // Sarsa draws a_n from the slot's own Q rows of s_n; double Q (agent.py:176-184) takes
+    // its argmax from the online net's q of s_{t+1}: rows t+1 of the rollout's own q (the slot's
+    // parameters, those the loss is taken at), and for t = n-1 this forward of s_n with them
+    if (e->sarsa || c.double_q) {
+      rc = a3c_forward_launch(L, sl.P, sl.prep, ring_addr(e, n, sl.tau), E, nullptr, sl.scr_l2, sl.scr_l3, zboot,
+                              none, s, e->mode);
+      if (rc) return rc;
+    }
+    // the target network on s_{t+1} of every transition (agent.py:186: n*E rows from s_1), or with
+    // q_nstep (Algorithm S2) on the one bootstrap state s_n of every env (E rows)
     rc = a3c_prep_fwd_launch(L, e->tparams, e->prep_t, s);
     if (rc) return rc;
     rc = a3c_forward_launch(L, e->tparams, e->prep_t, ring_addr(e, c.q_nstep ? n : 1, sl.tau), c.q_nstep ? E : e->nE,
-                            nullptr, sl.scr_l2, sl.scr_l3, e->zt, none, s);
+                            nullptr, sl.scr_l2, sl.scr_l3, e->zt, none, s, e->mode);
     if (rc) return rc;
-    rc = a3c_sarsa_target_launch(sl.rewards, sl.terms, sl.actions, nullptr, e->zt, c.q_nstep, n, E, L.A, zs,
-                                 c.discount, sl.R_buf, s, &bd);
-    if (rc) return rc;
-  } else if (q && c.q_nstep) {
-    // n-step Q-learning (Algorithm S2): the target network on the one bootstrap state s_n of
-    // every env (E rows, not n*E), double Q: the slot's own parameters on the same state for the
-    // argmax; then the rollout's n-step returns from it
-    HeadSelect none = {};
-    none.mode = -1;
-    none.E = E;
-    const float* qsel = nullptr;
-    if (c.double_q) {
-      rc = a3c_forward_launch(L, sl.P, sl.prep, ring_addr(e, n, sl.tau), E, nullptr, sl.scr_l2, sl.scr_l3,
-                              sl.z + e->nE * zs, none, s);
-      if (rc) return rc;
-      qsel = sl.z + e->nE * zs;
+    if (e->sarsa) {
+      // one kernel draws, from the slot's rows, the action the rollout's head would draw in s_n, at the
+      // slot's tau + n (sl.tau holds tau alone: the schedule's base step comes from the counters, where
+      // only a3c_engine_set_step writes it), and forms the targets at the taken actions -- as many
+      // launches as double Q
+      const BootDraw bd = {head_select(e, 1, e->counters, 0), sl.tau, zboot, sl.boot_action};
+      rc = a3c_sarsa_target_launch(sl.rewards, sl.terms, sl.actions, nullptr, e->zt, c.q_nstep, n, E, L.A, zs,
+                                   c.discount, sl.R_buf, s, &bd);
+    } else if (c.q_nstep) {   // the rollout's n-step returns from s_n's rows
+      rc = a3c_nstep_q_target_launch(sl.rewards, sl.terms, e->zt, c.double_q ? zboot : nullptr, n, E, L.A, zs,
+                                     c.discount, sl.R_buf, s);
+    } else {
+      rc = a3c_td_target_launch(sl.rewards, sl.terms, e->zt, e->nE, L.A, zs, c.discount, sl.R_buf, s,
+                                c.double_q ? sl.z + (int64_t)E * zs : nullptr);
     }
-    rc = a3c_prep_fwd_launch(L, e->tparams, e->prep_t, s);
-    if (rc) return rc;
-    rc = a3c_forward_launch(L, e->tparams, e->prep_t, ring_addr(e, n, sl.tau), E, nullptr, sl.scr_l2, sl.scr_l3,
-                            e->zt, none, s);
-    if (rc) return rc;
-    rc = a3c_nstep_q_target_launch(sl.rewards, sl.terms, e->zt, qsel, n, E, L.A, zs, c.discount, sl.R_buf, s);
-    if (rc) return rc;
-  } else if (q) {
-    // target network on s_{t+1} for every transition (agent.py:186)
-    HeadSelect none = {};
-    none.mode = -1;
-    none.E = E;
-    const float* qsel = nullptr;
-    if (c.double_q) {
-      // double Q (agent.py:176-184): the online net's q of s_{t+1} -- rows t+1 of the rollout's own
-      // q (the slot's parameters, those the loss is taken at), and for t = n-1 one forward of s_n
-      // with them into the slot's bootstrap row block
-      rc = a3c_forward_launch(L, sl.P, sl.prep, ring_addr(e, n, sl.tau), E, nullptr, sl.scr_l2, sl.scr_l3,
-                              sl.z + e->nE * zs, none, s);
-      if (rc) return rc;
-      qsel = sl.z + (int64_t)E * zs;
-    }
-    rc = a3c_prep_fwd_launch(L, e->tparams, e->prep_t, s);
-    if (rc) return rc;
-    rc = a3c_forward_launch(L, e->tparams, e->prep_t, ring_addr(e, 1, sl.tau), e->nE, nullptr, sl.scr_l2,
-                            sl.scr_l3, e->zt, none, s);
-    if (rc) return rc;
-    rc = a3c_td_target_launch(sl.rewards, sl.terms, e->zt, e->nE, L.A, zs, c.discount, sl.R_buf, s, qsel);
     if (rc) return rc;
   }
   if (boot_bwd(e)) {   // V(s_n) of the slot (its fc partials: the rollout's last kernel)
@@ -1191,8 +1119,8 @@ static int enqueue_grad_impl(a3c_engine* e, const Slot& sl, hipStream_t s) {
                                  (const uint16_t*)sl.prep);
   else
   rc = a3c_backward_launch(L, sl.P, bsa, e->nE, sl.act_l1, sl.act_l2, sl.act_l3, sl.z,
-                           sl.actions, sl.R_buf, c.beta, c.literal_adv, e->grads, e->loss, e->ws, s, &ra,
-                           fork && !e->split ? e->gs : nullptr, fork && !e->split ? e->ev_gfork : nullptr,
+                           sl.actions, sl.R_buf, c.beta, c.literal_adv, e->grads, e->loss, e->ws, s, e->mode,
+                           &ra, fork && !e->split ? e->gs : nullptr, fork && !e->split ? e->ev_gfork : nullptr,
                            fork && !e->split ? e->ev_gjoin : nullptr, L.lstm ? &lb : nullptr, &sf,
                            e->split ? &sp : nullptr, l2bits_on(e) ? sl.l2m : nullptr);
   if (rc) return rc;
@@ -1295,13 +1223,7 @@ extern "C" int a3c_engine_set_optimizer(a3c_engine* e, int kind, double beta1, d
   e->adam_b2 = beta2;
   e->adam_eps = (float)eps;
   e->shard_nranks = 0;
-  // the captured graphs hold the other optimizer's launches
-  for (int i = 0; i < NGRAPH; ++i)
-    if (e->captured[i]) {
-      (void)hipGraphExecDestroy(e->gexec[i]);
-      (void)hipGraphDestroy(e->graph[i]);
-      e->captured[i] = false;
-    }
+  drop_graphs(e);   // (they hold the other optimizer's launches)
   if (int rc = init_slots(e, nullptr)) return rc;
   A3C_CHECK(hipStreamSynchronize(nullptr));
   return 0;
@@ -1348,13 +1270,7 @@ extern "C" int a3c_engine_set_catch_rules(a3c_engine* e, int visible_rows, int f
   A3C_CHECK(hipDeviceSynchronize());      // (the engine's streams: nothing in flight steps an env)
   e->envp.catch_visible = (int16_t)(visible_rows | (e->envp.catch_visible & CATCH_FIRST_SCREEN_BIT));
   e->envp.catch_frozen = (int16_t)frozen_rows;
-  // the captured graphs hold the other rules in their kernel arguments
-  for (int i = 0; i < NGRAPH; ++i)
-    if (e->captured[i]) {
-      (void)hipGraphExecDestroy(e->gexec[i]);
-      (void)hipGraphDestroy(e->graph[i]);
-      e->captured[i] = false;
-    }
+  drop_graphs(e);   // (they hold the other rules in their kernel arguments)
   e->reset_done = false;
   return 0;
 }
@@ -1370,13 +1286,7 @@ extern "C" int a3c_engine_set_first_screen(a3c_engine* e, int on) {
     return a3c_set_error(A3C_ERR_STATE, "a3c_engine_set_first_screen", "a gradient is pending: apply it first");
   A3C_CHECK(hipDeviceSynchronize());      // (the engine's streams: nothing in flight steps an env)
   e->envp.catch_visible = (int16_t)(catch_visible_rows(e->envp) | (on ? CATCH_FIRST_SCREEN_BIT : 0));
-  // the captured graphs hold the other value in their kernel arguments
-  for (int i = 0; i < NGRAPH; ++i)
-    if (e->captured[i]) {
-      (void)hipGraphExecDestroy(e->gexec[i]);
-      (void)hipGraphDestroy(e->graph[i]);
-      e->captured[i] = false;
-    }
+  drop_graphs(e);   // (they hold the other value in their kernel arguments)
   return 0;
 }
 
@@ -2075,12 +1985,7 @@ static int enqueue_play_step(a3c_engine* e, int mode, int t, int32_t* actions, f
   const PlayCtx& c = e->play;
   const NetLayout& L = e->L;
   const int E = e->E, par = t & 1;
-  HeadSelect sel = {};
-  sel.mode = mode;
-  sel.k0 = e->k0; sel.k1 = e->k1;
-  sel.tau_ptr = c.counters; sel.tau_add = 0;
-  sel.env_ids = nullptr; sel.env_id_base = e->cfg.env_id_base; sel.E = E;
-  sel.eps = c.eps;
+  HeadSelect sel = head_select(e, mode, c.counters, 0, c.eps);
   sel.actions = actions;
   sel.env_on = 1;
   sel.par_E = E;
@@ -2102,7 +2007,7 @@ static int enqueue_play_step(a3c_engine* e, int mode, int t, int32_t* actions, f
   int rc;
   if (e->nat) {
     rc = a3c_nat_forward_launch(L, e->params, sa, E, c.a1, c.a2, c.a3, c.a4, z, sel, (const uint16_t*)c.prep,
-                                c.nat_fws, s, frozen);
+                                c.nat_fws, s, e->mode, frozen);
   } else {
     LstmStep ls = {};
     if (L.lstm) {
@@ -2110,8 +2015,8 @@ static int enqueue_play_step(a3c_engine* e, int mode, int t, int32_t* actions, f
       ls.h_src = c.lh + par * hc; ls.c_src = c.lc + par * hc;
       ls.h = c.lh + (par ^ 1) * hc; ls.c = c.lc + (par ^ 1) * hc;
     }
-    rc = a3c_forward_launch(L, e->params, c.prep, sa, E, nullptr, c.a2, c.a3, z, sel, s, L.lstm ? &ls : nullptr,
-                            false, nullptr, nullptr, nullptr, frozen);
+    rc = a3c_forward_launch(L, e->params, c.prep, sa, E, nullptr, c.a2, c.a3, z, sel, s, e->mode,
+                            L.lstm ? &ls : nullptr, false, nullptr, nullptr, nullptr, frozen);
   }
   if (rc) return rc;
   if (rf)
@@ -2275,10 +2180,8 @@ extern "C" int a3c_engine_play_ex(a3c_engine* e, const a3c_play_config* cfg, int
   if (!e->reset_done) return a3c_set_error(A3C_ERR_STATE, "a3c_engine_play", "call a3c_engine_reset first");
   hipStream_t s = (hipStream_t)stream;
   if (int rc = play_alloc(e, s)) return rc;
-  // overlap: a training rollout may be in flight on the rollout stream -> the small-footprint forms
-  a3c_set_shared_gpu(e->overlap != 0);
+  // (overlap: a training rollout may be in flight on the rollout stream -> e->mode's small-footprint forms)
   int rc = play_impl(e, *cfg, refill, returns, lengths, terminated, trace_actions, trace_z, s);
-  a3c_set_shared_gpu(false);
   if (rc) return rc;
   A3C_CHECK(hipStreamSynchronize(s));
   return 0;
@@ -2319,6 +2222,27 @@ extern "C" int a3c_engine_play_buffers(a3c_engine* e, a3c_play_buffers* b) {
 }
 
 // ---- profiling hook: average duration of one engine kernel, HIP events on the caller's stream ----
+// one warm launch, then the average of iters launches of go() on s
+template <class F>
+static int time_launches(F&& go, int iters, hipStream_t s, float* avg_ms) {
+  int rc = go();   // warm
+  if (rc) return rc;
+  hipEvent_t a, b;
+  A3C_CHECK(hipEventCreate(&a));
+  A3C_CHECK(hipEventCreate(&b));
+  A3C_CHECK(hipEventRecord(a, s));
+  for (int i = 0; i < iters && !rc; ++i) rc = go();
+  A3C_CHECK(hipEventRecord(b, s));
+  A3C_CHECK(hipEventSynchronize(b));
+  float ms = 0.f;
+  A3C_CHECK(hipEventElapsedTime(&ms, a, b));
+  (void)hipEventDestroy(a);
+  (void)hipEventDestroy(b);
+  if (rc) return rc;
+  *avg_ms = ms / (float)iters;
+  return 0;
+}
+
 extern "C" int a3c_engine_time_kernel(a3c_engine* e, int kernel, int iters, void* stream, float* avg_ms) {
   if (!e || !avg_ms || iters < 1 || !e->reset_done)
     return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_time_kernel", "bad argument");
@@ -2327,12 +2251,7 @@ extern "C" int a3c_engine_time_kernel(a3c_engine* e, int kernel, int iters, void
   const int E = e->E;
   const Slot& sl = e->slot[0];
   if (e->rs) A3C_CHECK(hipStreamSynchronize(e->rs));
-  a3c_set_shared_gpu(e->overlap != 0);      // time the variants the engine runs
-  a3c_set_bwd_bound(bwd_bound(e));
-  a3c_set_fcp_split(e->frame84 ? 2 : 4);
-  struct ResetShared {
-    ~ResetShared() { a3c_set_shared_gpu(false); a3c_set_bwd_bound(false); a3c_set_fcp_split(2); }
-  } reset_shared;
+  const LaunchMode& m = e->mode;            // time the variants the engine runs
   if (e->nat != (kernel >= A3C_KER_NAT_C1F))
     return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_time_kernel", "kernel id of another trunk");
   if (e->nat) {   // one pass of the nature trunk: forward over E states, backward passes over n*E samples
@@ -2352,22 +2271,7 @@ extern "C" int a3c_engine_time_kernel(a3c_engine* e, int kernel, int iters, void
                  : a3c_nat_pass_launch(pass, L, bs.P, sa, e->nE, bs.act_l1, bs.act_l2, bs.act_l3, bs.act_l4,
                                        (const uint16_t*)bs.prep, nullptr, e->ws, s);
     };
-    int rc = go();
-    if (rc) return rc;
-    hipEvent_t a, b;
-    A3C_CHECK(hipEventCreate(&a));
-    A3C_CHECK(hipEventCreate(&b));
-    A3C_CHECK(hipEventRecord(a, s));
-    for (int i = 0; i < iters && !rc; ++i) rc = go();
-    A3C_CHECK(hipEventRecord(b, s));
-    A3C_CHECK(hipEventSynchronize(b));
-    float ms = 0.f;
-    A3C_CHECK(hipEventElapsedTime(&ms, a, b));
-    (void)hipEventDestroy(a);
-    (void)hipEventDestroy(b);
-    if (rc) return rc;
-    *avg_ms = ms / (float)iters;
-    return 0;
+    return time_launches(go, iters, s, avg_ms);
   }
   if (kernel == A3C_KER_CONV12_FWD || kernel == A3C_KER_FC_FWD || kernel == A3C_KER_HEAD_SCREEN_CONV12) {
     int rc0 = a3c_prep_fwd_launch(L, e->params, sl.prep, s);
@@ -2380,12 +2284,12 @@ extern "C" int a3c_engine_time_kernel(a3c_engine* e, int kernel, int iters, void
     salt += 4099u;
     switch (kernel) {
       case A3C_KER_CONV12_FWD:
-        return a3c_conv12_launch(L, e->params, sl.prep, ring_addr(e, 0, e->counters), E, sl.act_l1, sl.act_l2, s);
+        return a3c_conv12_launch(L, e->params, sl.prep, ring_addr(e, 0, e->counters), E, sl.act_l1, sl.act_l2, s, m);
       case A3C_KER_FC_FWD:
         return a3c_fc_fwd_launch(sl.act_l2, (const float*)(sl.prep + PREP_W1S_BYTES), e->params + L.off[T_FCB],
-                                 sl.act_l3, E, s, e->params + L.off[T_FCW]);
+                                 sl.act_l3, E, s, m, e->params + L.off[T_FCW]);
       case A3C_KER_FC_PART:
-        return a3c_fc_part_launch(sl.act_l2, (const float*)(sl.prep + PREP_W1S_BYTES), e->fcpart, E, s);
+        return a3c_fc_part_launch(sl.act_l2, (const float*)(sl.prep + PREP_W1S_BYTES), e->fcpart, E, s, m);
       case A3C_KER_ENV_STEP:
         if (e->frame84) return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_time_kernel", "no screen kernel in frame84 mode");
         return a3c_env_screen_launch(E, sl.frames, e->pool, e->ring, e->R, e->counters, 0, s);
@@ -2393,12 +2297,8 @@ extern "C" int a3c_engine_time_kernel(a3c_engine* e, int kernel, int iters, void
       case A3C_KER_HEAD_SCREEN_CONV12: {
         // head + action draw + env act + Environment.screen as in rollout step 0 (idempotent:
         // the env state is read from the tau-parity half and written to the other one)
-        HeadSelect sel = {};
-        sel.mode = L.algo == A3C_ALGO_Q ? 1 : 0;
-        sel.k0 = e->k0; sel.k1 = e->k1;
-        sel.tau_ptr = e->counters; sel.tau_add = 0;
-        sel.env_id_base = e->cfg.env_id_base; sel.E = E; sel.par_E = E;
-        if (sel.mode) set_eps_schedule(e, sel);
+        HeadSelect sel = head_select(e, L.algo == A3C_ALGO_Q ? 1 : 0, e->counters, 0);
+        sel.par_E = E;
         sel.actions = sl.actions;
         sel.env_on = 1;
         sel.envp = e->envp; sel.envb = e->env;
@@ -2408,7 +2308,7 @@ extern "C" int a3c_engine_time_kernel(a3c_engine* e, int kernel, int iters, void
         sel.frame84 = e->frame84;
         sel.frame_salt = salt;
         if (kernel == A3C_KER_HEAD_SCREEN)
-          return a3c_head_screen_launch(L, e->params, L.lstm ? sl.lh : sl.act_l3, E, sl.z, sel, s);
+          return a3c_head_screen_launch(L, e->params, L.lstm ? sl.lh : sl.act_l3, E, sl.z, sel, s, m);
         // + conv1 + conv2 of the next states into step 1's activation rows (as rollout step 0)
         Conv12Next nx = {};
         nx.sa = ring_addr(e, 1, e->counters);
@@ -2425,28 +2325,14 @@ extern "C" int a3c_engine_time_kernel(a3c_engine* e, int kernel, int iters, void
       }
       case A3C_KER_CONV_BWD: {
         const BwdPlan p = a3c_bwd_plan(L, e->nE);
-        return a3c_conv_bwd_launch(L, e->params, ring_addr(e, 0, e->counters), e->nE, sl.act_l1, e->ws + p.dl2, e->ws, s);
+        return a3c_conv_bwd_launch(L, e->params, ring_addr(e, 0, e->counters), e->nE, sl.act_l1, e->ws + p.dl2, e->ws, s,
+                                   m);
       }
       default:
         return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_time_kernel", "unknown kernel id");
     }
   };
-  int rc = launch();   // warm
-  if (rc) return rc;
-  hipEvent_t a, b;
-  A3C_CHECK(hipEventCreate(&a));
-  A3C_CHECK(hipEventCreate(&b));
-  A3C_CHECK(hipEventRecord(a, s));
-  for (int i = 0; i < iters && !rc; ++i) rc = launch();
-  A3C_CHECK(hipEventRecord(b, s));
-  A3C_CHECK(hipEventSynchronize(b));
-  float ms = 0.f;
-  A3C_CHECK(hipEventElapsedTime(&ms, a, b));
-  (void)hipEventDestroy(a);
-  (void)hipEventDestroy(b);
-  if (rc) return rc;
-  *avg_ms = ms / (float)iters;
-  return 0;
+  return time_launches(launch, iters, s, avg_ms);
 }
 
 // Live launch spans of the engine's dominant kernels (which 0: k_conv_bwd, 1:

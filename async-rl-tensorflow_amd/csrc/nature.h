@@ -38,7 +38,8 @@ inline int64_t nat_act_floats() { return (int64_t)NT_A1 + NT_A2 + NT_FLAT + NT_F
 int64_t a3c_nat_fwd_ws_floats(int64_t B);
 int a3c_nat_forward_launch(const NetLayout& L, const float* P, const StateAddr& sa, int64_t B, float* l1, float* l2,
                            float* l3, float* l4, float* z, const HeadSelect& sel, const uint16_t* w1t, float* ws,
-                           hipStream_t s, const uint8_t* play_frozen = nullptr);   // (play: as a3c_forward_launch)
+                           hipStream_t s, const LaunchMode& m,   // (m: the step tail's head + screen variant)
+                           const uint8_t* play_frozen = nullptr);   // (play: as a3c_forward_launch)
 
 struct ReturnsArgs;
 struct SumsqFused;

@@ -1676,7 +1676,7 @@ int a3c_nat_prep_launch(const NetLayout& L, const float* P, uint16_t* w1t, const
 // ---------------------------------------------------------------------------------------
 int a3c_nat_forward_launch(const NetLayout& L, const float* P, const StateAddr& sa, int64_t B, float* l1, float* l2,
                            float* l3, float* l4, float* z, const HeadSelect& sel, const uint16_t* w1t, float* ws,
-                           hipStream_t s, const uint8_t* play_frozen) {
+                           hipStream_t s, const LaunchMode& m, const uint8_t* play_frozen) {
   if (L.trunk != A3C_TRUNK_NATURE || B <= 0 || B * NT1_P > 0x7fffffffLL)
     return a3c_set_error(A3C_ERR_INVALID, "a3c_nat_forward", "nature trunk, 0 < B, B * 400 < 2^31");
   if (play_frozen && !(sel.mode >= 0 && sel.env_on && sel.pool))
@@ -1704,14 +1704,14 @@ int a3c_nat_forward_launch(const NetLayout& L, const float* P, const StateAddr& 
     gf.nsplit = fcs; gf.slab = ws; gf.defer_reduce = 1;
     if (int rc = a3c_gemm(true, true, gf, s)) return rc;
     return a3c_head_screen_fold_launch(ws, fcs, P + L.off[N_FCB], l4, P + L.off[N_HW], P + L.off[N_HB],
-                                       P + L.off[N_VW], P + L.off[N_VB], L.A, L.zs, B, z, sel, s);
+                                       P + L.off[N_VW], P + L.off[N_VB], L.A, L.zs, B, z, sel, s, m);
   }
   if (play_frozen)   // Agent.play's step tail (agent.py:371-377)
     return a3c_head_screen_play_launch(NT_FC, l4, P + L.off[N_HW], P + L.off[N_HB], P + L.off[N_VW], P + L.off[N_VB],
-                                       L.A, L.zs, B, z, sel, play_frozen, s);
+                                       L.A, L.zs, B, z, sel, play_frozen, s, m);
   if (step_tail)   // head + act + Environment.screen
     return a3c_head_screen_wide_launch(l4, P + L.off[N_HW], P + L.off[N_HB], P + L.off[N_VW], P + L.off[N_VB], L.A,
-                                       L.zs, B, z, sel, s);
+                                       L.zs, B, z, sel, s, m);
   if (sel.mode >= 0 && sel.env_on && sel.envp.game == A3C_GAME_CATCH)   // (the Catch form: end of this file)
     return nat_head_catch_launch(L, P, l4, B, z, sel, s);
   hipLaunchKernelGGL(k_nat_head<>, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, s, l4, B, P + L.off[N_HW],
@@ -1894,7 +1894,7 @@ extern "C" int a3c_nature_forward(const a3c_net_desc* net, const float* params, 
   sel.mode = -1;
   sel.E = 1;
   return a3c_nat_forward_launch(L, params, nat_states(states, B), B, l1, l2, l3, l4, z, sel, nullptr,
-                                nat_align(workspace), (hipStream_t)stream);
+                                nat_align(workspace), (hipStream_t)stream, LAUNCH_ALONE);
 }
 
 extern "C" int a3c_nature_loss_backward(const a3c_net_desc* net, const float* params, const uint8_t* states,

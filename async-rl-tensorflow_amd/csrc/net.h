@@ -185,6 +185,17 @@ static_assert(__builtin_offsetof(HeadSelect, envb) - __builtin_offsetof(HeadSele
 #define W2F_ELEMS (2 * 8 * 64 * 8)      // conv2 weights (16x16x32), as three bf16 terms each
 #define PREP_BYTES (PREP_W2F_OFF + W2F_ELEMS * 3 * 2)
 struct LstmStep;
+// Which variant of a kernel a launch takes, where a launcher has more than one.  The caller owns
+// it (an engine fixes its own at create) and every launcher that reads a field, itself or through
+// a callee, takes it beside the stream: the variants of a kernel agree to fp32 summation order, so
+// a wrongly chosen one costs speed and fails no oracle test.
+struct LaunchMode {
+  bool shared_gpu;   // the launch runs beside another stream's work (engine overlap): small-footprint variants
+  bool bwd_bound;    // the backward, not the rollout, bounds the overlapped iteration (M2, several GPUs)
+  int  fcp_split;    // K splits of the partial fc (k_fc_part<KS>)
+};
+// a launch on its own, outside an engine (the C-ABI's one-off entry points)
+constexpr LaunchMode LAUNCH_ALONE = {false, false, 2};
 // the next state's conv1 + conv2, fused into rollout step t's head + screen kernel
 // (k_head_screen_conv12): s_{t+1} addressing, conv weights (prep'd W1 terms) and outputs
 struct Conv12Next {
@@ -203,39 +214,33 @@ struct Conv12Next {
 // with play_frozen[e] != 0 left untouched (no z row, action, env state or ring slot written)
 int a3c_forward_launch(const NetLayout& L, const float* params, const uint8_t* prep, const StateAddr& sa,
                        int64_t B, float* act_l1, float* act_l2, float* act_l3, float* z, const HeadSelect& sel,
-                       hipStream_t s, const LstmStep* ls = nullptr, bool skip_conv12 = false,
+                       hipStream_t s, const LaunchMode& m, const LstmStep* ls = nullptr, bool skip_conv12 = false,
                        const Conv12Next* next = nullptr, float* fc_part = nullptr, uint32_t* l2m = nullptr,
                        const uint8_t* play_frozen = nullptr);
 // the play step's tail alone: W = FC (NIPS trunk / LSTM head rows) or NT_FC (nature trunk)
 int a3c_head_screen_play_launch(int W, const float* h, const float* Wp, const float* bp, const float* Wv,
                                 const float* bv, int A, int zs, int64_t B, float* z, const HeadSelect& sel,
-                                const uint8_t* frozen, hipStream_t s);
+                                const uint8_t* frozen, hipStream_t s, const LaunchMode& m);
 // fc layer as FC_NS K-slice partials part[x][M][FC] (folded by k_head_screen_conv12's head)
 // adv_ptr: the launch also advances the device tau counter by adv_n (thread 0 of block 0; the fc
 // reads no tau) -- the rollout's last kernel when the bootstrap head runs on the backward stream
 int a3c_fc_part_launch(const float* A, const float* Wp, float* part, int64_t M, hipStream_t s,
-                       int64_t* adv_ptr = nullptr, int adv_n = 0);
+                       const LaunchMode& m, int64_t* adv_ptr = nullptr, int adv_n = 0);
 // the policy / value head of B states from the fc's K-slice partials (fold + bias + ReLU + head,
 // k_head_fwd): z rows, no action draw
 // the same with the fold in the launch (C5): each tile's last K-slice workgroup folds the FC_NS
 // partials in slice order + fbias + ReLU into fout[M][FC]; tick: one zeroed word per 32 x 64 tile,
 // (ceil(M / 32) * 4), left zeroed by the launch
 int a3c_fc_part_fold_launch(const float* A, const float* Wp, float* part, int64_t M, unsigned* tick,
-                            const float* fbias, float* fout, hipStream_t s);
+                            const float* fbias, float* fout, hipStream_t s, const LaunchMode& m);
 int a3c_head_fold_launch(const NetLayout& L, const float* P, const float* fc_part, int64_t B, float* z,
                          hipStream_t s);
-int a3c_fcp_split();
-void a3c_set_fcp_split(int ks);
 // tau_src / tau_dst (nullable): *tau_dst = *tau_src as well (the overlap rollout's tau snapshot);
 // sig (nullable): *sig += 1 (a system-scope atomic: the engine's rollout sequence)
 int a3c_prep_fwd_launch(const NetLayout& L, const float* P, uint8_t* prep, hipStream_t s,
                         const int64_t* tau_src = nullptr, int64_t* tau_dst = nullptr,
                         uint32_t* sig = nullptr);
-// true while enqueuing work that runs concurrently with another stream (engine overlap mode)
-bool a3c_shared_gpu();
-void a3c_set_shared_gpu(bool v);
 bool a3c_lean_cbwd();
-void a3c_set_bwd_bound(bool v);
 
 // stage the HIST u8 planes of state b into LDS (HIST x 441 uint4)
 __device__ inline void stage_state(const StateAddr& sa, int64_t b, int64_t tau0, uint8_t* x8) {

@@ -96,7 +96,7 @@ int a3c_backward_launch(const NetLayout& L, const float* params, const StateAddr
                         const float* act_l1, const float* act_l2, const float* act_l3,
                         const float* z, const int32_t* actions, const float* target, float beta,
                         int literal, float* grads, float* loss_out, float* ws, hipStream_t s,
-                        const ReturnsArgs* ra = nullptr,
+                        const LaunchMode& m, const ReturnsArgs* ra = nullptr,
                         hipStream_t side = nullptr, hipEvent_t ev_fork = nullptr, hipEvent_t ev_join = nullptr,
                         const LstmBwd* lb = nullptr, const SumsqFused* sf = nullptr,
                         const SplitBwd* sp = nullptr, const uint32_t* l2m = nullptr);
@@ -135,17 +135,18 @@ void a3c_conv12_set_smem();
 void a3c_conv_bwd_set_smem();
 int a3c_head_screen_fold_launch(const float* part, int nsplit, const float* fbias, float* l4, const float* Wp,
                                 const float* bp, const float* Wv, const float* bv, int A, int zs, int64_t B, float* z,
-                                const HeadSelect& sel, hipStream_t s);
+                                const HeadSelect& sel, hipStream_t s, const LaunchMode& m);
 int a3c_head_screen_wide_launch(const float* l4, const float* Wp, const float* bp, const float* Wv, const float* bv,
-                                int A, int zs, int64_t B, float* z, const HeadSelect& sel, hipStream_t s);
+                                int A, int zs, int64_t B, float* z, const HeadSelect& sel, hipStream_t s,
+                                const LaunchMode& m);
 int a3c_head_screen_launch(const NetLayout& L, const float* P, const float* act_l3, int64_t B, float* z,
-                           const HeadSelect& sel, hipStream_t s);
+                           const HeadSelect& sel, hipStream_t s, const LaunchMode& m);
 int a3c_head_screen_conv12_launch(const NetLayout& L, const float* P, const float* act_l3, int64_t B, float* z,
                                   const HeadSelect& sel, const Conv12Next& nx, hipStream_t s);
 int a3c_conv12_launch(const NetLayout& L, const float* P, const uint8_t* prep, const StateAddr& sa, int64_t B,
-                      float* act_l1, float* act_l2, hipStream_t s, uint32_t* l2m = nullptr);
+                      float* act_l1, float* act_l2, hipStream_t s, const LaunchMode& m, uint32_t* l2m = nullptr);
 int a3c_conv_bwd_launch(const NetLayout& L, const float* P, const StateAddr& sa, int64_t B, const float* act_l1,
-                        const float* dl2, float* ws, hipStream_t s);
+                        const float* dl2, float* ws, hipStream_t s, const LaunchMode& m);
 
 // shared with the nature trunk (nature.hip): the head backward at width 256 (FC) or 512, the
 // deterministic slab grouping, and k_finalize (segments + loss terms + fused norms / schedule)

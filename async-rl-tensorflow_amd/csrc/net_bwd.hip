@@ -1,4 +1,3 @@
-#include <algorithm>
 #include <cstdlib>
 // Loss + backward of the NIPS trunk on gfx950.
 //
@@ -994,20 +993,16 @@ BwdPlan a3c_bwd_plan(const NetLayout& L, int64_t B, bool wks) {
   // 3.45M with 448 two-per-CU workgroups (those alone are faster, 92 vs 132 us, but leave no LDS
   // for the rollout).  Round 2, with the partial fc: 192 (-> 183 workgroups of 7 samples at
   // n*E = 1280) 4.37M env-steps/s vs 4.29M for 224 (214 x 6), 4.14M for 160 (160 x 8), 4.00M for 256.
-  // The slab workspace is sized for the larger count, so the plan's offsets do not depend on the mode.
   static const int env_nwg = (int)A3C_AB_KNOB("A3C_CB_NWG", 0);
   // Round 3, with one compact workgroup per CU guaranteed (CB_SMEM_SOLO): 256 (5 samples each at
-  // n*E = 1280) -- M2 5.36M -> 5.77M, M1 4.62M -> 4.66M against 183 x 7 (214 x 6: 5.71M / 4.65M)
-  const int nwg_shared = env_nwg ? env_nwg : 256, nwg_own = env_nwg ? env_nwg : 256;
-  auto count = [&](int nwg_max, int& per) {
-    int nwg = (int)(B < nwg_max ? B : nwg_max);
-    if (nwg < 1) nwg = 1;
-    per = (int)((B + nwg - 1) / nwg);
-    return (int)((B + per - 1) / per);
-  };
-  int per_alloc = 0;
-  const int nwg_alloc = std::max(count(nwg_shared, per_alloc), count(nwg_own, per_alloc));
-  p.nwg = count(a3c_shared_gpu() ? nwg_shared : nwg_own, p.per_wg);
+  // n*E = 1280) -- M2 5.36M -> 5.77M, M1 4.62M -> 4.66M against 183 x 7 (214 x 6: 5.71M / 4.65M).
+  // Sync and overlap take the one count, so the plan depends on no launch mode: the one that
+  // sizes the workspace at create is the one every launch computes.
+  const int nwg_max = env_nwg ? env_nwg : 256;
+  int nwg = (int)(B < nwg_max ? B : nwg_max);
+  if (nwg < 1) nwg = 1;
+  p.per_wg = (int)((B + nwg - 1) / nwg);
+  p.nwg = (int)((B + p.per_wg - 1) / p.per_wg);
   p.head_split = a3c_gemm_effective_split((int)B, a3c_gemm_plan_split(FC, L.zs, (int)B, 128));
   // wks: the fc weight GEMM (K = B) splits K inside its workgroups (k_gemm_f32_wks) -- no slab
   // round trip through HBM, no fold kernel; else split-K slabs + k_reduce_slabs.  The slab and column
@@ -1023,9 +1018,9 @@ BwdPlan a3c_bwd_plan(const NetLayout& L, int64_t B, bool wks) {
   p.hslab = take(p.head_split > 1 ? (int64_t)p.head_split * FC * L.zs : 0);
   p.fccol = take((int64_t)fc_split_slab * FC);
   p.fcslab = take(fc_split_slab > 1 ? (int64_t)fc_split_slab * FLAT * FC : 0);
-  p.cslab = take((int64_t)nwg_alloc * CB_SLAB);
+  p.cslab = take((int64_t)p.nwg * CB_SLAB);
   p.groups = p.nwg < 16 ? p.nwg : 16;
-  p.cgroup = take((int64_t)16 * CB_SLAB);    // groups <= 16 in either mode
+  p.cgroup = take((int64_t)16 * CB_SLAB);    // groups <= 16
   p.total = o;
   return p;
 }
@@ -1036,7 +1031,7 @@ BwdPlan a3c_bwd_plan(const NetLayout& L, int64_t B, bool wks) {
 // grads[:cut].  Every fold, partial and clip value is the one-pass path's, so the gradients are
 // bit-identical (tests/test_gpu_multirank.py).
 static int backward_split(const NetLayout& L, const float* P, const StateAddr& sa, int64_t B, const float* act_l1,
-                          float* ws, hipStream_t s, const BwdPlan& p, GemmArgs gh, GemmArgs gf, GemmArgs gd,
+                          float* ws, hipStream_t s, const LaunchMode& m, const BwdPlan& p, GemmArgs gh, GemmArgs gf, GemmArgs gd,
                           float* grads, const float* terms, float* loss_out, const SumsqFused* sf, const SplitBwd* sp) {
   const bool a3c = L.algo == A3C_ALGO_A3C;
   // the head weight GEMM's split-K partials are folded by the finalize segments (the same
@@ -1095,7 +1090,7 @@ static int backward_split(const NetLayout& L, const float* P, const StateAddr& s
     A3C_CHECK(hipEventRecord(sp->ev_head, s));
   }
   // (2) conv tensors
-  rc = a3c_conv_bwd_launch(L, P, sa, B, act_l1, ws + p.dl2, ws, s);
+  rc = a3c_conv_bwd_launch(L, P, sa, B, act_l1, ws + p.dl2, ws, s, m);
   if (rc) return rc;
   const int per = (p.nwg + p.groups - 1) / p.groups;
   hipLaunchKernelGGL(k_slab_group, dim3((CB_SLAB + 255) / 256, p.groups), dim3(256), 0, s, ws + p.cslab, p.nwg, per,
@@ -1119,14 +1114,34 @@ static int backward_split(const NetLayout& L, const float* P, const StateAddr& s
   }
 }
 
-static bool xcd_gemm();   // (below, beside the other mode knobs)
-static bool dwfc_late_knob();
-static bool bwd_bound_knob();
+// Kernel variant choice (LaunchMode, net.h).  shared_gpu: the launch will run concurrently with
+// another stream's work (engine overlap mode) -- then the kernels take their smaller-footprint
+// variants so both streams' workgroups co-reside on the CUs.
+// bwd_bound: the backward stream, not the rollout, bounds the overlapped iteration (mode M2,
+// several GPUs): there the three weight/input GEMMs run as one launch with their folds behind the
+// conv backward (as in sync mode); A3C_CB_LEAN, A3C_GEMM_MULTI, A3C_GEMM_XCD and A3C_DWFC_LATE
+// (0/1) override the choices
+static int env_knob(const char* name) { return (int)A3C_AB_KNOB(name, -1); }   // (A/B builds only)
+bool a3c_lean_cbwd() {   // (every overlap mode since the 256-workgroup plan: M1 4.63M -> 4.66M)
+  static const int env = env_knob("A3C_CB_LEAN");
+  return env >= 0 ? env != 0 : true;
+}
+static bool xcd_gemm(const LaunchMode& m) {
+  static const int env = env_knob("A3C_GEMM_XCD");
+  return env >= 0 ? env != 0 : m.bwd_bound;
+}
+// the fc weight GEMM behind the conv backward (M2: 5.15-5.18M -> 5.20-5.22M; M1 neutral)
+static bool dwfc_late_knob(const LaunchMode& m) {
+  static const int env = env_knob("A3C_DWFC_LATE");
+  return env >= 0 ? env != 0 : m.bwd_bound;
+}
+static bool bwd_bound_knob(const LaunchMode& m) { return m.bwd_bound; }
+
 int a3c_backward_launch(const NetLayout& L, const float* params, const StateAddr& sa, int64_t B,
                         const float* act_l1, const float* act_l2, const float* act_l3,
                         const float* z, const int32_t* actions, const float* target, float beta,
                         int literal, float* grads, float* loss_out, float* ws, hipStream_t s,
-                        const ReturnsArgs* ra_in, hipStream_t side, hipEvent_t ev_fork, hipEvent_t ev_join,
+                        const LaunchMode& m, const ReturnsArgs* ra_in, hipStream_t side, hipEvent_t ev_fork, hipEvent_t ev_join,
                         const LstmBwd* lb, const SumsqFused* sf, const SplitBwd* sp, const uint32_t* l2m) {
   ReturnsArgs ra = {};
   if (ra_in) ra = *ra_in;
@@ -1136,7 +1151,7 @@ int a3c_backward_launch(const NetLayout& L, const float* params, const StateAddr
   // that bounds it the 1,420-workgroup launch slows it more than it gains (M1: 4.62M -> 4.45M),
   // and so do the folds moved behind the conv backward alone (A3C_FOLD_LATE: 4.62M -> 4.45M)
   static const int env_multi = (int)A3C_AB_KNOB("A3C_GEMM_MULTI", -1);
-  const bool multi0 = env_multi >= 0 ? env_multi != 0 : !a3c_shared_gpu() || bwd_bound_knob();
+  const bool multi0 = env_multi >= 0 ? env_multi != 0 : !m.shared_gpu || bwd_bound_knob(m);
   // the in-workgroup split-K fc weight GEMM where its launch stands alone anyway (the M1 overlap
   // backward), not in the single three-GEMM launch.  The split backward (SplitBwd) takes the form
   // the one-phase backward of the same configuration takes (multi0 does not depend on sp), so the
@@ -1191,7 +1206,7 @@ int a3c_backward_launch(const NetLayout& L, const float* params, const StateAddr
   gf.M = FLAT; gf.N = FC; gf.K = (int)B;
   gf.epi = EPI_STORE; gf.slab = ws + p.fcslab; gf.nsplit = p.fc_split; gf.colsum = ws + p.fccol;
   gf.wg_split = wks ? 4 : 0;
-  gf.xcd = xcd_gemm() ? 1 : 0;          // the 4 column tiles of an l2 strip on one XCD
+  gf.xcd = xcd_gemm(m) ? 1 : 0;          // the 4 column tiles of an l2 strip on one XCD
   // The in-workgroup split-K form in XCD-grouped order (its 4 N tiles share the 64-row strip of l2,
   // fetched once per XCD instead of once per N tile): HBM bytes per launch 58.5 -> 26.6 MB (PMC,
   // profiles/round5_ab/gemm_knobs.txt; the 8-XCD floor is 26.5: l2 13.3 + dl3 1.3 per XCD + dW
@@ -1210,25 +1225,25 @@ int a3c_backward_launch(const NetLayout& L, const float* params, const StateAddr
   if (l2m) {   // the forward's ReLU bits (engine): 415 KB instead of re-reading l2's 13.3 MB (E=256)
     gd.epi = EPI_MASKBITS; gd.maskbits = l2m; gd.mask = nullptr; gd.ldm = FLAT / 32;
   }
-  gd.xcd = xcd_gemm() ? 2 : 0;          // the 20 row tiles of a W strip on one XCD
+  gd.xcd = xcd_gemm(m) ? 2 : 0;          // the 20 row tiles of a W strip on one XCD
   {
     // overlap, A3C_GEMM_BIG=1: 128x128 tiles (210 workgroups instead of 820 beside the rollout;
     // bit-identical).  Off: +0.5 % on one box (4.79-4.81M -> 4.82-4.83M), -0.8 % on another
     // (4.80-4.83M -> 4.75-4.79M) -- the tile GEMM takes 62 us instead of ~35 and the caller
     // stream's loop (go -> backward -> apply -> hop) then bounds M1 again (tools/wglog.py)
     static const int env_big = (int)A3C_AB_KNOB("A3C_GEMM_BIG", 0);
-    gd.big = a3c_shared_gpu() && env_big != 0;
+    gd.big = m.shared_gpu && env_big != 0;
     static const int env_bigf = (int)A3C_AB_KNOB("A3C_GEMM_BIG_FC", 0);
-    gf.big = a3c_shared_gpu() && env_bigf != 0;
+    gf.big = m.shared_gpu && env_bigf != 0;
   }
   {
     static const int env_wgs = (int)A3C_AB_KNOB("A3C_GEMM_WGS", 0);
-    if (a3c_shared_gpu()) gh.max_wgs = gf.max_wgs = gd.max_wgs = env_wgs;
+    if (m.shared_gpu) gh.max_wgs = gf.max_wgs = gd.max_wgs = env_wgs;
   }
   int rc;
   if (sp) {
     if (!sf || fork) return a3c_set_error(A3C_ERR_INVALID, "a3c_loss_backward", "split backward: fused norms, no fork");
-    return backward_split(L, P, sa, B, act_l1, ws, s, p, gh, gf, gd, grads, terms, loss_out, sf, sp);
+    return backward_split(L, P, sa, B, act_l1, ws, s, m, p, gh, gf, gd, grads, terms, loss_out, sf, sp);
   }
   static const int env_late = (int)A3C_AB_KNOB("A3C_FOLD_LATE", -1);
   // The head weight GEMM folds its own split-K slabs (k_reduce_slabs behind it) instead of the
@@ -1251,7 +1266,7 @@ int a3c_backward_launch(const NetLayout& L, const float* params, const StateAddr
       if (!rc) rc = a3c_gemm(true, false, gd, s);
     }
     if (rc) return rc;
-    rc = a3c_conv_bwd_launch(L, P, sa, B, act_l1, dl2, ws, s);
+    rc = a3c_conv_bwd_launch(L, P, sa, B, act_l1, dl2, ws, s, m);
     if (rc) return rc;
     rc = a3c_gemm_reduce(gf, s);       // (gh: folded by the finalize)
     if (rc) return rc;
@@ -1263,7 +1278,7 @@ int a3c_backward_launch(const NetLayout& L, const float* params, const StateAddr
 #endif
     // dwfc_late: the fc weight GEMM (+ its fold) behind the conv backward -- only dl2 stands
     // between the head and the conv
-    const bool dwfc_late = dwfc_late_knob() && !fork;
+    const bool dwfc_late = dwfc_late_knob(m) && !fork;
     hfold = env_hfold && p.head_split > 1;
     if (hfold) gh.defer_reduce = 0;
     rc = abl_gemm ? 0 : a3c_gemm(false, true, gh, ws_s);
@@ -1278,7 +1293,7 @@ int a3c_backward_launch(const NetLayout& L, const float* params, const StateAddr
 #ifdef A3C_MARKERS
     a3c_mark(4, s);
 #endif
-    rc = a3c_conv_bwd_launch(L, P, sa, B, act_l1, dl2, ws, s);
+    rc = a3c_conv_bwd_launch(L, P, sa, B, act_l1, dl2, ws, s, m);
     if (rc) return rc;
 #ifdef A3C_MARKERS
     a3c_mark(5, s);
@@ -1341,37 +1356,8 @@ int a3c_backward_launch(const NetLayout& L, const float* params, const StateAddr
   return 0;
 }
 
-// Kernel variant choice: a3c_shared_gpu() is true while the engine enqueues work that will run
-// concurrently with another stream (overlap mode) -- then the kernels take their smaller-footprint
-// variants so both streams' workgroups co-reside on the CUs.  Thread-local switch set by the engine
-// around its enqueue calls (captured into the graphs).
-static thread_local bool t_shared_gpu = false;
-bool a3c_shared_gpu() { return t_shared_gpu; }
-void a3c_set_shared_gpu(bool v) { t_shared_gpu = v; }
-// set by the engine where the backward stream, not the rollout, bounds the overlapped iteration
-// (mode M2, several GPUs): there the three weight/input GEMMs run as one launch with their folds
-// behind the conv backward (as in sync mode); A3C_CB_LEAN, A3C_GEMM_MULTI, A3C_GEMM_XCD and
-// A3C_DWFC_LATE (0/1) override the choices
-static thread_local bool t_bwd_bound = false;
-static int env_knob(const char* name) { return (int)A3C_AB_KNOB(name, -1); }   // (A/B builds only)
-bool a3c_lean_cbwd() {   // (every overlap mode since the 256-workgroup plan: M1 4.63M -> 4.66M)
-  static const int env = env_knob("A3C_CB_LEAN");
-  return env >= 0 ? env != 0 : true;
-}
-static bool xcd_gemm() {
-  static const int env = env_knob("A3C_GEMM_XCD");
-  return env >= 0 ? env != 0 : t_bwd_bound;
-}
-// the fc weight GEMM behind the conv backward (M2: 5.15-5.18M -> 5.20-5.22M; M1 neutral)
-static bool dwfc_late_knob() {
-  static const int env = env_knob("A3C_DWFC_LATE");
-  return env >= 0 ? env != 0 : t_bwd_bound;
-}
-static bool bwd_bound_knob() { return t_bwd_bound; }
-void a3c_set_bwd_bound(bool v) { t_bwd_bound = v; }
-
 int a3c_conv_bwd_launch(const NetLayout& L, const float* P, const StateAddr& sa, int64_t B, const float* act_l1,
-                        const float* dl2, float* ws, hipStream_t s) {
+                        const float* dl2, float* ws, hipStream_t s, const LaunchMode& m) {
   const BwdPlan p = a3c_bwd_plan(L, B);
 #ifdef A3C_MARKERS
   static const bool ablate = getenv("A3C_ABL_CBWD") != nullptr;   // measurement only: no conv backward
@@ -1380,14 +1366,14 @@ int a3c_conv_bwd_launch(const NetLayout& L, const float* P, const StateAddr& sa,
   // sync: the DMA-prefetching kernel at 8 waves (2 per SIMD) owns the GPU; overlap: the compact
   // 4-wave kernel leaves registers and LDS for the concurrent rollout (measured, tools/ab.sh)
   static const int env_nw = (int)A3C_AB_KNOB("A3C_CB_WAVES", 0);
-  const int nw = env_nw ? env_nw : (a3c_shared_gpu() ? 4 : 8);
-  if (a3c_shared_gpu() && nw == 4 && a3c_lean_cbwd())
+  const int nw = env_nw ? env_nw : (m.shared_gpu ? 4 : 8);
+  if (m.shared_gpu && nw == 4 && a3c_lean_cbwd())
     hipLaunchKernelGGL((k_conv_bwd<false, 4, true>), dim3((unsigned)p.nwg), dim3(256), cb_smem(CB_SMEM_COMPACT_LX), s, sa, B,
                        p.per_wg, act_l1, dl2, P + L.off[T_L2W], ws + p.cslab);
-  else if (a3c_shared_gpu() && nw == 4)
+  else if (m.shared_gpu && nw == 4)
     hipLaunchKernelGGL((k_conv_bwd<false, 4, false>), dim3((unsigned)p.nwg), dim3(256), cb_smem(CB_SMEM_COMPACT), s, sa, B,
                        p.per_wg, act_l1, dl2, P + L.off[T_L2W], ws + p.cslab);
-  else if (a3c_shared_gpu())
+  else if (m.shared_gpu)
     hipLaunchKernelGGL((k_conv_bwd<false, 8, true>), dim3((unsigned)p.nwg), dim3(512), cb_smem(CB_SMEM_COMPACT_LX), s, sa, B,
                        p.per_wg, act_l1, dl2, P + L.off[T_L2W], ws + p.cslab);
   else if (nw == 4)

@@ -841,7 +841,7 @@ __global__ void __launch_bounds__(256) k_select(const float* __restrict__ z, int
 }
 
 int a3c_fc_fwd_launch(const float* A, const float* W, const float* bias, float* C, int64_t M, hipStream_t s,
-                      const float* Wrows = nullptr);
+                      const LaunchMode& m, const float* Wrows = nullptr);
 
 // skip_conv12: conv1 + conv2 of these states already ran (fused into the previous step's
 // k_head_screen_conv12); next: fuse the next states' conv1 + conv2 into this step's head + screen
@@ -896,9 +896,9 @@ static void catch_set_smem();
 
 int a3c_head_screen_fold_launch(const float* part, int nsplit, const float* fbias, float* l4, const float* Wp,
                                 const float* bp, const float* Wv, const float* bv, int A, int zs, int64_t B, float* z,
-                                const HeadSelect& sel, hipStream_t s) {
+                                const HeadSelect& sel, hipStream_t s, const LaunchMode& m) {
   static const int env_t = (int)A3C_AB_KNOB("A3C_HS_THREADS", 0);
-  const int nt = env_t ? env_t : (a3c_shared_gpu() ? 512 : 1024);
+  const int nt = env_t ? env_t : (m.shared_gpu ? 512 : 1024);
   const int64_t ps = B * 512;
   if (catch_on(sel)) return catch_fold_launch(part, nsplit, fbias, l4, Wp, bp, Wv, bv, A, zs, B, z, sel, nt, s);
   if (nt == 1024)
@@ -913,9 +913,10 @@ int a3c_head_screen_fold_launch(const float* part, int nsplit, const float* fbia
 
 // the same for the nature trunk's 512-wide fc output (nature.hip's rollout steps)
 int a3c_head_screen_wide_launch(const float* l4, const float* Wp, const float* bp, const float* Wv, const float* bv,
-                                int A, int zs, int64_t B, float* z, const HeadSelect& sel, hipStream_t s) {
+                                int A, int zs, int64_t B, float* z, const HeadSelect& sel, hipStream_t s,
+                                const LaunchMode& m) {
   static const int env_t = (int)A3C_AB_KNOB("A3C_HS_THREADS", 0);
-  const int nt = env_t ? env_t : (a3c_shared_gpu() ? 512 : 1024);
+  const int nt = env_t ? env_t : (m.shared_gpu ? 512 : 1024);
   if (catch_on(sel)) return catch_head_screen_launch(512, l4, Wp, bp, Wv, bv, A, zs, B, z, sel, nt, s);
   if (nt == 1024)
     hipLaunchKernelGGL((k_head_screen<1024, 512>), dim3((unsigned)B), dim3(1024), SCREEN_FRAME_SMEM, s, l4, Wp, bp,
@@ -929,12 +930,12 @@ int a3c_head_screen_wide_launch(const float* l4, const float* Wp, const float* b
 
 int a3c_head_screen_play_launch(int W, const float* h, const float* Wp, const float* bp, const float* Wv,
                                 const float* bv, int A, int zs, int64_t B, float* z, const HeadSelect& sel,
-                                const uint8_t* frozen, hipStream_t s) {
+                                const uint8_t* frozen, hipStream_t s, const LaunchMode& m) {
   if (B <= 0) return 0;
   if (!frozen || !sel.tau_ptr || !sel.env_on || !sel.ring || !sel.pool || !sel.rewards_raw || !sel.terms ||
       !sel.frames_out || !sel.actions || sel.mode < 0 || sel.par_E < B || (W != FC && W != 512))
     return a3c_set_error(A3C_ERR_INVALID, "a3c_head_screen_play", "bad argument");
-  const int nt = a3c_shared_gpu() ? 512 : 1024;
+  const int nt = m.shared_gpu ? 512 : 1024;
   if (catch_on(sel)) return catch_play_launch(W, h, Wp, bp, Wv, bv, A, zs, B, z, sel, frozen, nt, s);
 #define HSP_GO(T, WW) hipLaunchKernelGGL((k_head_screen_play<T, WW>), dim3((unsigned)B), dim3(T), SCREEN_FRAME_SMEM, s, h, \
                                          Wp, bp, Wv, bv, A, zs, z, sel, frozen)
@@ -954,8 +955,8 @@ int a3c_head_screen_conv12_launch(const NetLayout& L, const float* P, const floa
                                   const HeadSelect& sel, const Conv12Next& nx, hipStream_t s);
 int a3c_forward_launch(const NetLayout& L, const float* params, const uint8_t* prep, const StateAddr& sa,
                        int64_t B, float* act_l1, float* act_l2, float* act_l3, float* z, const HeadSelect& sel,
-                       hipStream_t s, const LstmStep* ls, bool skip_conv12, const Conv12Next* next,
-                       float* fc_part, uint32_t* l2m, const uint8_t* play_frozen) {
+                       hipStream_t s, const LaunchMode& m, const LstmStep* ls, bool skip_conv12,
+                       const Conv12Next* next, float* fc_part, uint32_t* l2m, const uint8_t* play_frozen) {
   if (B <= 0) return 0;
   if (play_frozen && (next || fc_part || skip_conv12 || sel.mode < 0 || !sel.env_on || !sel.ring))
     return a3c_set_error(A3C_ERR_INVALID, "a3c_forward", "the play step runs unfused, with the device env and the fused screen");
@@ -963,7 +964,7 @@ int a3c_forward_launch(const NetLayout& L, const float* params, const uint8_t* p
     return a3c_set_error(A3C_ERR_INVALID, "a3c_forward", "the LSTM head needs its recurrent state");
   const float* P = params;
   if (!skip_conv12) {
-    int rc0 = a3c_conv12_launch(L, P, prep, sa, B, act_l1, act_l2, s, l2m);
+    int rc0 = a3c_conv12_launch(L, P, prep, sa, B, act_l1, act_l2, s, m, l2m);
     if (rc0) return rc0;
   }
   // fused overlap rollout: the fc as K-slice partials, folded by the head of k_head_screen_conv12
@@ -974,9 +975,9 @@ int a3c_forward_launch(const NetLayout& L, const float* params, const uint8_t* p
   // (with ls->fc_tick the fc's last K-slice workgroup per tile folds them instead: k_fc_part_fold)
   const bool fold_fc = part_lstm && ls->fc_tick;
   int rc = fold_fc ? a3c_fc_part_fold_launch(act_l2, (const float*)(prep + PREP_W1S_BYTES), fc_part, B, ls->fc_tick,
-                                             P + L.off[T_FCB], act_l3, s)
-         : part ? a3c_fc_part_launch(act_l2, (const float*)(prep + PREP_W1S_BYTES), fc_part, B, s)
-                : a3c_fc_fwd_launch(act_l2, (const float*)(prep + PREP_W1S_BYTES), P + L.off[T_FCB], act_l3, B, s,
+                                             P + L.off[T_FCB], act_l3, s, m)
+         : part ? a3c_fc_part_launch(act_l2, (const float*)(prep + PREP_W1S_BYTES), fc_part, B, s, m)
+                : a3c_fc_fwd_launch(act_l2, (const float*)(prep + PREP_W1S_BYTES), P + L.off[T_FCB], act_l3, B, s, m,
                                     P + L.off[T_FCW]);
   if (rc) return rc;
   const float* head_in = act_l3;
@@ -1005,9 +1006,9 @@ int a3c_forward_launch(const NetLayout& L, const float* params, const uint8_t* p
   if (next) return a3c_set_error(A3C_ERR_INVALID, "a3c_forward", "conv fusion needs the fused env screen");
   if (play_frozen)
     return a3c_head_screen_play_launch(FC, head_in, P + L.off[T_HW], P + L.off[T_HB], Wv, bv, L.A, L.zs, B, z, sel,
-                                       play_frozen, s);
+                                       play_frozen, s, m);
   if (sel.mode >= 0 && sel.env_on && sel.ring)
-    return a3c_head_screen_launch(L, P, head_in, B, z, sel, s);
+    return a3c_head_screen_launch(L, P, head_in, B, z, sel, s, m);
   else {
     HeadSelect hs = sel;
     if (part && !part_lstm) {
@@ -1026,12 +1027,12 @@ int a3c_forward_launch(const NetLayout& L, const float* params, const uint8_t* p
 
 // the fused head + env act + screen of one rollout step (profiling hook; see engine.hip)
 int a3c_head_screen_launch(const NetLayout& L, const float* P, const float* act_l3, int64_t B, float* z,
-                           const HeadSelect& sel, hipStream_t s) {
+                           const HeadSelect& sel, hipStream_t s, const LaunchMode& m) {
   const float* Wv = L.algo == A3C_ALGO_A3C ? P + L.off[T_VW] : nullptr;
   const float* bv = L.algo == A3C_ALGO_A3C ? P + L.off[T_VB] : nullptr;
   // 1024 threads when the step owns the GPU; 512 leave room for the concurrent backward
   static const int env_t = (int)A3C_AB_KNOB("A3C_HS_THREADS", 0);
-  const int nt = env_t ? env_t : (a3c_shared_gpu() ? 512 : 1024);
+  const int nt = env_t ? env_t : (m.shared_gpu ? 512 : 1024);
   if (catch_on(sel))
     return catch_head_screen_launch(FC, act_l3, P + L.off[T_HW], P + L.off[T_HB], Wv, bv, L.A, L.zs, B, z, sel, nt, s);
   if (nt == 1024)
@@ -1064,10 +1065,10 @@ int a3c_head_screen_conv12_launch(const NetLayout& L, const float* P, const floa
 }
 
 int a3c_conv12_launch(const NetLayout& L, const float* P, const uint8_t* prep, const StateAddr& sa, int64_t B,
-                      float* act_l1, float* act_l2, hipStream_t s, uint32_t* l2m) {
+                      float* act_l1, float* act_l2, hipStream_t s, const LaunchMode& m, uint32_t* l2m) {
   if (!prep) return a3c_set_error(A3C_ERR_INVALID, "a3c_conv12_launch", "prepared forward weights missing");
   const uint16_t* w1s = (const uint16_t*)prep;
-  const bool ew = !a3c_shared_gpu();
+  const bool ew = !m.shared_gpu;
   // overlap mode: the 60 KB u8-plane variant (co-resides with the backward's workgroups)
   static const int env_u8 = (int)A3C_AB_KNOB("A3C_C12_U8", -1);
   const bool u8 = env_u8 >= 0 ? env_u8 != 0 : !ew;
@@ -1460,20 +1461,18 @@ k_fc_part_fold(const float* __restrict__ A, const float* __restrict__ Wp, float*
   fc_part_body<KS, true>(A, Wp, part, M, nullptr, 0, tick, fbias, fout);
 }
 
-// K splits of the partial fc, set by the engine per frame mode (a3c_set_fcp_split; A3C_FCP_KS
-// overrides): M1 4 (4.72-4.75M -> 4.76-4.81M env-steps/s against 2), M2 2 (6.02-6.03M vs 5.99-6.00M)
-static thread_local int t_fcp_split = 2;
-int a3c_fcp_split() { return t_fcp_split; }
-void a3c_set_fcp_split(int ks) { t_fcp_split = ks; }
+// K splits of the partial fc: LaunchMode::fcp_split, which the engine picks per frame mode
+// (A3C_FCP_KS overrides): M1 4 (4.72-4.75M -> 4.76-4.81M env-steps/s against 2), M2 2 (6.02-6.03M
+// vs 5.99-6.00M)
 
 int a3c_fc_part_fold_launch(const float* A, const float* Wp, float* part, int64_t M, unsigned* tick,
-                            const float* fbias, float* fout, hipStream_t s) {
+                            const float* fbias, float* fout, hipStream_t s, const LaunchMode& m) {
   if (M <= 0) return 0;
   if (!tick || !fbias || !fout || (((uintptr_t)fbias | (uintptr_t)fout) & 15))
     return a3c_set_error(A3C_ERR_INVALID, "a3c_fc_part_fold", "bad argument");
   const int nrb = (int)((M + FCP_RB - 1) / FCP_RB);
   static const int env_ks = (int)A3C_AB_KNOB("A3C_FCP_KS", 0);
-  const int ks = env_ks ? env_ks : a3c_fcp_split();
+  const int ks = env_ks ? env_ks : m.fcp_split;
   const dim3 grid((unsigned)(FC_NS * nrb * (FC / FCP_CB)));
   if (ks == 4) hipLaunchKernelGGL(k_fc_part_fold<4>, grid, dim3(1024), 0, s, A, Wp, part, (int)M, tick, fbias, fout);
   else if (ks == 2) hipLaunchKernelGGL(k_fc_part_fold<2>, grid, dim3(512), 0, s, A, Wp, part, (int)M, tick, fbias, fout);
@@ -1482,8 +1481,8 @@ int a3c_fc_part_fold_launch(const float* A, const float* Wp, float* part, int64_
   return 0;
 }
 
-int a3c_fc_part_launch(const float* A, const float* Wp, float* part, int64_t M, hipStream_t s, int64_t* adv_ptr,
-                       int adv_n) {
+int a3c_fc_part_launch(const float* A, const float* Wp, float* part, int64_t M, hipStream_t s, const LaunchMode& m,
+                       int64_t* adv_ptr, int adv_n) {
   if (M <= 0) return 0;
 #ifdef A3C_MARKERS
   static const bool ablate = getenv("A3C_ABL_FC") != nullptr;   // measurement only: no fc
@@ -1491,7 +1490,7 @@ int a3c_fc_part_launch(const float* A, const float* Wp, float* part, int64_t M, 
 #endif
   const int nrb = (int)((M + FCP_RB - 1) / FCP_RB);
   static const int env_ks = (int)A3C_AB_KNOB("A3C_FCP_KS", 0);
-  const int ks = env_ks ? env_ks : a3c_fcp_split();
+  const int ks = env_ks ? env_ks : m.fcp_split;
   const dim3 grid((unsigned)(FC_NS * nrb * (FC / FCP_CB)));
   if (ks == 4) hipLaunchKernelGGL(k_fc_part<4>, grid, dim3(1024), 0, s, A, Wp, part, (int)M, adv_ptr, adv_n);
   else if (ks == 2) hipLaunchKernelGGL(k_fc_part<2>, grid, dim3(512), 0, s, A, Wp, part, (int)M, adv_ptr, adv_n);
@@ -1579,14 +1578,14 @@ __global__ void __launch_bounds__(256) k_fc_fwd_rows(const float* __restrict__ A
 }
 
 int a3c_fc_fwd_launch(const float* A, const float* W, const float* bias, float* C, int64_t M, hipStream_t s,
-                      const float* Wrows) {
+                      const LaunchMode& m, const float* Wrows) {
   if (M <= 0) return 0;
 #ifdef A3C_MARKERS
   static const bool ablate = getenv("A3C_ABL_FC") != nullptr;   // measurement only: no fc
   if (ablate) return 0;
 #endif
   static const int env_nw = (int)A3C_AB_KNOB("A3C_FC_WAVES", -1);
-  const int nw = env_nw >= 0 ? env_nw : (a3c_shared_gpu() ? 4 : 8);
+  const int nw = env_nw >= 0 ? env_nw : (m.shared_gpu ? 4 : 8);
   if (nw == 0 && Wrows)
     hipLaunchKernelGGL(k_fc_fwd_rows, dim3(FC / 16, (unsigned)((M + 15) / 16)), dim3(256), 0, s, A, Wrows, bias, C,
                        (int)M);

@@ -113,7 +113,7 @@ def test_overlap_with_zero_lr_equals_sync():
     """With learning_rate 0 staleness is invisible: the pipelined engine must reproduce the
     synchronous engine's rollouts exactly (actions, rewards) one call later, and its returns,
     losses and gradients to fp32 summation order (the two modes run different-footprint kernel
-    variants, see a3c_shared_gpu)."""
+    variants: LaunchMode::shared_gpu in csrc/net.h, which each engine fixes at create)."""
     s, _, _ = build('a3c', 6, 16, 5, 0, seed=31, learning_rate=0.0)
     o, _, _ = build('a3c', 6, 16, 5, 0, seed=31, learning_rate=0.0, overlap=True)
     assert o.ring_slots == 2 * 5 + 4 and s.ring_slots == 5 + 4
@@ -233,3 +233,32 @@ def test_bench_shape_is_deterministic(overlap, frame84):
     for name in ('params', 'ms', 'mom', 'frame_ring', 'loss', 'counters', 'actions', 'z', 'act_l3'):
         assert torch.equal(getattr(a, name), getattr(b, name)), name
     assert torch.isfinite(a.params).all() and torch.isfinite(a.loss).all()
+
+
+def test_engines_of_both_modes_interleave_bit_exact():
+    """The kernel variants a launch takes (LaunchMode, csrc/net.h) belong to the engine, not to the
+    calling thread: a sync and an overlap engine driven in turn from one thread, with a play() and a
+    time_kernel() between their iterations, train bit for bit as their twins (same seed, same mode)
+    do when each runs on its own.  Both sides are the same build: no tolerance."""
+    from src import _lib
+
+    def pair():
+        return (build('a3c', 6, 16, 5, 0, seed=41, frames=256)[0],
+                build('a3c', 6, 16, 5, 0, seed=43, frames=256, overlap=True)[0])
+    a_sync, a_over = pair()
+    b_sync, b_over = pair()
+    for eng in (a_sync, a_over):
+        for _ in range(5):
+            eng.iterate()
+    for r in range(5):
+        b_sync.iterate()
+        b_over.iterate()
+        if r == 2:
+            # neither touches the training state that outlives the next rollout: play() has a context of
+            # its own, the timed head + screen launches write what rollout step 0 writes again
+            b_over.play(n_episode=16, n_step=8)
+            b_sync.time_kernel(_lib.KER_HEAD_SCREEN, 2)
+    torch.cuda.synchronize()
+    for a, b, mode in ((a_sync, b_sync, 'sync'), (a_over, b_over, 'overlap')):
+        for name in ('params', 'ms', 'mom', 'frame_ring', 'loss', 'counters', 'actions', 'z'):
+            assert torch.equal(getattr(a, name), getattr(b, name)), (mode, name)
