@@ -195,17 +195,58 @@ struct WgLog {
 #define WGLOG(kind) ((void)0)
 #endif
 
-// Stores of activations that the next kernel reads on other XCDs (l1, l2, l3, the frame ring):
-// non-temporal with A3C_NT_STORE (bypass the writing XCD's L2, so the end-of-kernel release has
-// fewer dirty lines to write back) -- an A/B switch.
-template <typename T>
-__device__ inline void st_act(T* p, T v) {
-#ifdef A3C_NT_STORE
-  __builtin_nontemporal_store(v, p);
-#else
-  *p = v;
+// Stores of bulk outputs that a later kernel reads (on other XCDs): ST_WT_<group>(lvalue, value).
+// With the group's bit set in A3C_WT the store is write-through (sc1), so the line does not stay
+// dirty in the writing XCD's L2 for the end-of-kernel release to write back; with the bit clear the
+// macro is the plain assignment, token for token.  Groups (write-through A/B): R rollout
+// activations, fc partials and prepared weights; G backward GEMM epilogues and the head backward's
+// dl3; C conv-backward slabs and the slab folds; O the optimizer's apply pass.  4 and 8 bytes per
+// lane are relaxed agent-scope atomic stores (global_store_dword / dwordx2 ... sc1); the compiler
+// does not merge those, so a site that holds 16 bytes per lane uses the 16-byte form (s_nop 1: the
+// store reads its data registers after issue).  Only sites whose lanes write runs of >= 64
+// contiguous bytes per instruction are converted.
+#define A3C_WT_R 1
+#define A3C_WT_G 2
+#define A3C_WT_C 4
+#define A3C_WT_O 8
+#ifndef A3C_WT   // default: all four on (the highest median of the leave-one-out A/B)
+#define A3C_WT (A3C_WT_R | A3C_WT_G | A3C_WT_C | A3C_WT_O)
 #endif
+template <typename T, typename U>
+__device__ inline void st_sc1(T* p, U value) {
+  static_assert(sizeof(T) == 4 || sizeof(T) == 8 || sizeof(T) == 16, "4, 8 or 16 bytes per lane");
+  const T v = value;
+  if constexpr (sizeof(T) == 4) {
+    __hip_atomic_store((uint32_t*)p, __builtin_bit_cast(uint32_t, v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  } else if constexpr (sizeof(T) == 8) {
+    __hip_atomic_store((uint64_t*)p, __builtin_bit_cast(uint64_t, v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  } else {
+    const f32x4 x = __builtin_bit_cast(f32x4, v);
+    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(x) : "memory");
+  }
 }
+#define A3C_ST_PLAIN(lv, v) ((lv) = (v))
+#define A3C_ST_SC1(lv, v) st_sc1(&(lv), (v))
+#if A3C_WT & A3C_WT_R
+#define ST_WT_R A3C_ST_SC1
+#else
+#define ST_WT_R A3C_ST_PLAIN
+#endif
+#if A3C_WT & A3C_WT_G
+#define ST_WT_G A3C_ST_SC1
+#else
+#define ST_WT_G A3C_ST_PLAIN
+#endif
+#if A3C_WT & A3C_WT_C
+#define ST_WT_C A3C_ST_SC1
+#else
+#define ST_WT_C A3C_ST_PLAIN
+#endif
+#if A3C_WT & A3C_WT_O
+#define ST_WT_O A3C_ST_SC1
+#else
+#define ST_WT_O A3C_ST_PLAIN
+#endif
 
 // one 16-byte-per-lane global -> LDS DMA wave-instruction: lane l's 16 bytes land at
 // lds_base + 16 l (lds_base wave-uniform), no VGPR destination

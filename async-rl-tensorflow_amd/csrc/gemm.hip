@@ -92,7 +92,7 @@ __device__ inline void gemm_tile(const GemmArgs& g, int bx, int by, int bz, floa
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       int row = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-      if (row < g.M && col < g.N) out[(int64_t)row * g.N + col] = acc[r];
+      if (row < g.M && col < g.N) ST_WT_G(out[(int64_t)row * g.N + col], acc[r]);
     }
   } else {
 #pragma unroll
@@ -106,7 +106,7 @@ __device__ inline void gemm_tile(const GemmArgs& g, int bx, int by, int bz, floa
 #ifndef A3C_NO_MASKBITS
       else if (g.epi == EPI_MASKBITS) v = (g.maskbits[(int64_t)row * g.ldm + (col >> 5)] >> (col & 31)) & 1u ? v : 0.f;
 #endif
-        g.C[(int64_t)row * g.ldc + col] = v;
+        ST_WT_G(g.C[(int64_t)row * g.ldc + col], v);
       }
     }
   }
@@ -220,7 +220,7 @@ __global__ void __launch_bounds__(256 * KS) k_gemm_f32_wks(GemmArgs g) {
 #ifndef A3C_NO_MASKBITS
       else if (g.epi == EPI_MASKBITS) v = (g.maskbits[(int64_t)row * g.ldm + (col >> 5)] >> (col & 31)) & 1u ? v : 0.f;
 #endif
-      g.C[(int64_t)row * g.ldc + col] = v;
+      ST_WT_G(g.C[(int64_t)row * g.ldc + col], v);
     }
   }
   if (do_colsum && tid < BN && n0 + tid < g.N) g.colsum[n0 + tid] = csum;
@@ -329,7 +329,7 @@ __global__ void __launch_bounds__(256) k_gemm_f32_big(GemmArgs g) {
         if (row >= g.M || col >= g.N) continue;
         float v = acc[i][j][r];
         if (g.nsplit > 1) {
-          g.slab[(int64_t)ks * g.M * g.N + (int64_t)row * g.N + col] = v;
+          ST_WT_G(g.slab[(int64_t)ks * g.M * g.N + (int64_t)row * g.N + col], v);
         } else {
           if (g.epi == EPI_BIAS_RELU) v = fmaxf(v + g.bias[col], 0.f);
           else if (g.epi == EPI_BIAS) v = v + g.bias[col];
@@ -337,7 +337,7 @@ __global__ void __launch_bounds__(256) k_gemm_f32_big(GemmArgs g) {
 #ifndef A3C_NO_MASKBITS
       else if (g.epi == EPI_MASKBITS) v = (g.maskbits[(int64_t)row * g.ldm + (col >> 5)] >> (col & 31)) & 1u ? v : 0.f;
 #endif
-          g.C[(int64_t)row * g.ldc + col] = v;
+          ST_WT_G(g.C[(int64_t)row * g.ldc + col], v);
         }
       }
     }
@@ -435,7 +435,7 @@ __global__ void k_reduce_slabs(const float* __restrict__ slab, int nsplit, int M
 #ifndef A3C_NO_MASKBITS
   else if (epi == EPI_MASKBITS) v = (maskbits[(int64_t)row * ldm + (col >> 5)] >> (col & 31)) & 1u ? v : 0.f;
 #endif
-  C[(int64_t)row * ldc + col] = v;
+  ST_WT_C(C[(int64_t)row * ldc + col], v);
 }
 
 int a3c_gemm_plan_split(int M, int N, int K, int target_blocks) {

@@ -170,7 +170,7 @@ __global__ void __launch_bounds__(256) k_head_bwd(const float* __restrict__ z, i
 #pragma unroll
       for (int i = 0; i < 4; ++i) g[i] = h[i] > 0.f ? g[i] : 0.f;
     }
-    *(f32x4*)(dh3 + b * FC + 4 * lane) = g;
+    ST_WT_G(*(f32x4*)(dh3 + b * FC + 4 * lane), g);
   } else {
     // the same per feature k = 256 q + 4 lane + i, q < W / 256
     constexpr int NQ = W / 256;
@@ -196,7 +196,7 @@ __global__ void __launch_bounds__(256) k_head_bwd(const float* __restrict__ z, i
 #pragma unroll
         for (int i = 0; i < 4; ++i) g[q][i] = h[i] > 0.f ? g[q][i] : 0.f;
       }
-      *(f32x4*)(dh3 + b * W + 256 * q + 4 * lane) = g[q];
+      ST_WT_G(*(f32x4*)(dh3 + b * W + 256 * q + 4 * lane), g[q]);
     }
   }
 }
@@ -772,8 +772,8 @@ __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int krow = 16 * mt + 4 * j4 + r;     // dW2 row (kh,kw,ci)
-      out[CB_OFF_W2 + krow * C2_N + i16] = accW2[t][0][r];
-      out[CB_OFF_W2 + krow * C2_N + 16 + i16] = accW2[t][1][r];
+      ST_WT_C(out[CB_OFF_W2 + krow * C2_N + i16], accW2[t][0][r]);
+      ST_WT_C(out[CB_OFF_W2 + krow * C2_N + 16 + i16], accW2[t][1][r]);
     }
   }
   if constexpr (NW == 8) {                       // fold the odd-chunk half of dW1 (waves 4..7)
@@ -794,7 +794,7 @@ __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2)
       for (int r = 0; r < 4; ++r) {
         // D row 4 j4 + r of tile t: kh = 4 (w4 >> 1) + j4, kw = t + 4 (w4 & 1), cin = r
         const int krow = ((4 * (w4 >> 1) + j4) * C1_K + t + 4 * (w4 & 1)) * HIST + r;
-        out[CB_OFF_W1 + krow * C1_N + i16] = accW1[t][r];
+        ST_WT_C(out[CB_OFF_W1 + krow * C1_N + i16], accW1[t][r]);
       }
   }
   // db1: lanes with equal i16 (4 j4 groups) then the waves, in a fixed order
@@ -838,7 +838,7 @@ __global__ void __launch_bounds__(256) k_slab_group(const float* __restrict__ sr
   if (i >= len) return;
   const int g = blockIdx.y;
   const int s0 = g * per, s1 = min(nsplit, s0 + per);
-  dst[(int64_t)g * len + i] = sum_strided(src + (int64_t)s0 * len + i, s1 - s0, len);
+  ST_WT_C(dst[(int64_t)g * len + i], sum_strided(src + (int64_t)s0 * len + i, s1 - s0, len));
 }
 
 __device__ void loss_reduce_block(const float* __restrict__ terms, int64_t B, float* __restrict__ out) {
@@ -876,7 +876,7 @@ __global__ void __launch_bounds__(256) k_finalize(FinalizeSegs fs, const float* 
       const int r = (int)(i / sg.ncols), c = (int)(i - (int64_t)r * sg.ncols);
       const float* src = sg.src + (int64_t)r * sg.src_ld + sg.col0 + c;
       const float v = sum_strided(src, sg.nsplit, sg.split_stride) * sg.scale;
-      fs.dst[sg.dst_off + (int64_t)r * sg.dst_ld + c] = v;
+      ST_WT_C(fs.dst[sg.dst_off + (int64_t)r * sg.dst_ld + c], v);
       ss += (double)v * v;
     }
     if (fs.part && sg.slot >= 0) {

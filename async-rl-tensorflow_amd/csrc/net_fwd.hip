@@ -108,7 +108,7 @@ __global__ void __launch_bounds__(256) k_prep_fwd(const float* __restrict__ W1, 
 #pragma unroll
   for (int c4 = 0; c4 < 4; ++c4) v[c4] = Wfc[(int64_t)(32 * c + 8 * j4 + 4 * half + c4) * FC + n];
 #endif
-  ((f32x4*)(prep + PREP_W1S_BYTES))[q] = v;
+  ST_WT_R(((f32x4*)(prep + PREP_W1S_BYTES))[q], v);
 }
 
 int a3c_prep_fwd_launch(const NetLayout& L, const float* P, uint8_t* prep, hipStream_t s, const int64_t* tau_src,
@@ -250,7 +250,7 @@ __device__ inline void conv12_finish(f32x4 (&acc)[C1_TILES], float* l1s, int64_t
       d[16] = (uint16_t)tm;
       d[32] = (uint16_t)tl;
 #endif
-      if (SAVE_L1) st_act(act_l1 + (b * C1_P + pos) * C1_N + i16, v);
+      if (SAVE_L1) ST_WT_R(act_l1[(b * C1_P + pos) * C1_N + i16], v);
     }
   }
 
@@ -342,7 +342,7 @@ __device__ inline void conv12_finish(f32x4 (&acc)[C1_TILES], float* l1s, int64_t
     for (int r = 0; r < 4; ++r) {
       const int q = 16 * (grp + 4 * mi) + 4 * j4 + r;
       const float v = fmaxf(acc2[mi][r] + bias2, 0.f);
-      if (q < C2_Q) st_act(act_l2 + b * FLAT + q * C2_N + 16 * nt + i16, v);
+      if (q < C2_Q) ST_WT_R(act_l2[b * FLAT + q * C2_N + 16 * nt + i16], v);
       if (L2M && l2m) {
         // the ReLU mask as bits for the backward's dl2 epilogue: position q's channels 16 nt ..
         // 16 nt + 15 are the 16 lanes of group j4, so one ballot gives its half word (flat index
@@ -768,7 +768,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) k
 #pragma unroll
       for (int c4 = 0; c4 < 4; ++c4) v[c4] = fmaxf(v[c4] + fbias[c4], 0.f);
       fl[flane] = v;
-      *(f32x4*)(sel.l3_out + b * FC + 4 * flane) = v;
+      ST_WT_R(*(f32x4*)(sel.l3_out + b * FC + 4 * flane), v);
     }
     hrow = (const float*)fl;
   }
@@ -1189,7 +1189,7 @@ __global__ void __launch_bounds__(64 * NW) k_fc_fwd(const float* __restrict__ A,
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int row = m0 + rstride * (4 * j4 + r);
-        if (row < M) st_act(C + (int64_t)row * FC + n, fmaxf(acc[r] + bb, 0.f));
+        if (row < M) ST_WT_R(C[(int64_t)row * FC + n], fmaxf(acc[r] + bb, 0.f));
       }
     }
     WG_T1(C + (int64_t)m0 * FC + n0);   // debug: the tile's first 4 outputs
@@ -1401,8 +1401,8 @@ __device__ __forceinline__ void fc_part_body(const float* __restrict__ A, const 
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int row0 = m0 + 4 * j4 + r, row1 = row0 + 16;
-      if (row0 < M) out[(int64_t)row0 * FC] = acc0[r];
-      if (row1 < M) out[(int64_t)row1 * FC] = acc1[r];
+      if (row0 < M) ST_WT_R(out[(int64_t)row0 * FC], acc0[r]);
+      if (row1 < M) ST_WT_R(out[(int64_t)row1 * FC], acc1[r]);
     }
   } else {
     if (kr == 0) {

@@ -104,13 +104,13 @@ __global__ void __launch_bounds__(256) k_apply(float* __restrict__ w, float* __r
         mo[k] = mo[k] * op.momentum + (g[k] * lr) / sqrtf(m2[k] + op.eps);
         wv[k] = wv[k] - mo[k];
       }
-      *(f32x4*)(ms + i) = m2;
-      *(f32x4*)(mom + i) = mo;
-      *(f32x4*)(w + i) = wv;
-      if (copy) *(f32x4*)(op.target + i) = wv;
-      if (op.snap) *(f32x4*)(op.snap + i) = wv;
+      ST_WT_O(*(f32x4*)(ms + i), m2);
+      ST_WT_O(*(f32x4*)(mom + i), mo);
+      ST_WT_O(*(f32x4*)(w + i), wv);
+      if (copy) ST_WT_O(*(f32x4*)(op.target + i), wv);
+      if (op.snap) ST_WT_O(*(f32x4*)(op.snap + i), wv);
     } else {
-      *(f32x4*)(grads + i) = g;
+      ST_WT_O(*(f32x4*)(grads + i), g);
     }
   }
   if (blockIdx.x == 0 && threadIdx.x == 0 && op.counters && apply) {   // clip-only passes leave them
@@ -424,11 +424,11 @@ __global__ void __launch_bounds__(256) k_apply_opt(float* __restrict__ w, float*
       v[k] = v[k] + (g[k] * g[k] - v[k]) * omb2;
       wv[k] = wv[k] - (m[k] * alpha) / (sqrtf(v[k]) + op.eps);
     }
-    *(f32x4*)(vs + i) = v;
-    *(f32x4*)(mo + i) = m;
-    *(f32x4*)(w + i) = wv;
-    if (copy) *(f32x4*)(op.target + i) = wv;
-    if (op.snap) *(f32x4*)(op.snap + i) = wv;
+    ST_WT_O(*(f32x4*)(vs + i), v);
+    ST_WT_O(*(f32x4*)(mo + i), m);
+    ST_WT_O(*(f32x4*)(w + i), wv);
+    if (copy) ST_WT_O(*(f32x4*)(op.target + i), wv);
+    if (op.snap) ST_WT_O(*(f32x4*)(op.snap + i), wv);
   }
   // nothing in this launch reads the counters or the products: the next schedule does
   if (blockIdx.x == 0 && threadIdx.x == 0) {

@@ -371,7 +371,7 @@ __device__ inline void vpass_mfma(const uint8_t* __restrict__ tmpT, uint8_t* __r
   auto put = [&](int mt, uint32_t v) {
     const int x0 = 16 * mt + 4 * h;
     if (yy < OH && x0 < OW) {
-      st_act((uint32_t*)(out + yy * OW + x0), v);
+      *(uint32_t*)(out + yy * OW + x0) = v;   // (16-byte runs per row: not written through)
       if (lds_bf16) *(uint2*)(lds_bf16 + yy * OW + x0) = u8x4_to_bf16x4(v);   // (fused conv12)
     }
   };
@@ -509,7 +509,7 @@ __device__ __attribute__((always_inline)) inline void screen_frame(const uint8_t
       uint32_t packed = 0;
 #pragma unroll
       for (int c = 0; c < 4; ++c) packed |= (uint32_t)(acc[c] >> A3C_PRECISION_BITS) << (8 * c);
-      st_act((uint32_t*)(out + yy * OW + 4 * cq), packed);
+      *(uint32_t*)(out + yy * OW + 4 * cq) = packed;
       if (lds_bf16) *(uint2*)(lds_bf16 + yy * OW + 4 * cq) = u8x4_to_bf16x4(packed);   // (fused conv12)
     }
   }
@@ -537,7 +537,7 @@ __device__ inline void copy_frame84(const uint8_t* __restrict__ src, uint8_t* __
   for (int j = 0; j < PER; ++j) {
     const int i = tid + NT * j;
     if (i < NCH) {
-      ((uint4*)out)[i] = v[j];
+      ST_WT_R(((uint4*)out)[i], v[j]);
       if (lds_bf16) {
         uint4* d = (uint4*)(lds_bf16 + 16 * i);
         const uint2 a0 = u8x4_to_bf16x4(v[j].x), a1 = u8x4_to_bf16x4(v[j].y);
