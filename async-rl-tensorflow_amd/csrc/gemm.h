@@ -6,6 +6,8 @@
 
 enum { EPI_STORE = 0, EPI_BIAS_RELU = 1, EPI_BIAS = 2, EPI_MASK = 3, EPI_MASKBITS = 4 };
 
+// The "speed only" / "bit-identical" / "deterministic" claims below are asserted per variant, layout and
+// epilogue by tests/test_gpu_gemm.py through a3c_gemm_f32.
 // C[M][N] = epi( sum_k A(m,k) * B(k,n) )
 //   A(m,k) = A[m*lda + k] when the template's A_KC (k-contiguous) else A[k*lda + m]
 //   B(k,n) = B[k*ldb + n] when B_NC (n-contiguous) else B[n*ldb + k]
@@ -41,7 +43,8 @@ struct GemmArgs {
   const uint32_t* maskbits;
 };
 
-int a3c_gemm(bool a_kcontig, bool b_ncontig, GemmArgs g, hipStream_t s);
+// nsplit_eff (optional): the effective split gemm_setup chose for this launch (1 with wg_split)
+int a3c_gemm(bool a_kcontig, bool b_ncontig, GemmArgs g, hipStream_t s, int* nsplit_eff = nullptr);
 // three independent GEMMs in one launch: g0, g1 with (A k-strided, B n-contiguous), g2 with (A
 // k-contiguous, B k-contiguous).  The split-K folds are left to the caller (a3c_gemm_reduce, with
 // the arguments as updated here: effective split, K chunk)
@@ -50,6 +53,7 @@ int a3c_gemm_reduce(const GemmArgs& g, hipStream_t s);
 int a3c_gemm_plan_split(int M, int N, int K, int target_blocks);
 
 inline int a3c_gemm_effective_split(int K, int nsplit) {
+  if (K < 1) return 1;     // (no k-tile: a3c_gemm rejects it; never divide by per = 0)
   int ktiles = (K + 15) / 16;
   if (nsplit < 1) nsplit = 1;
   int per = (ktiles + nsplit - 1) / nsplit;

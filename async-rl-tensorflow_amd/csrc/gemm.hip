@@ -450,6 +450,7 @@ int a3c_gemm_plan_split(int M, int N, int K, int target_blocks) {
 
 // shared by a3c_gemm and a3c_gemm3: alignment checks, effective split, K-chunk
 static int gemm_setup(bool a_kc, bool b_nc, GemmArgs& g) {
+  if (g.K < 1) return a3c_set_error(A3C_ERR_INVALID, "a3c_gemm", "K < 1");   // (per would be 0 below)
   if (((a_kc || !b_nc) && (g.K & 3)) || (g.lda & 3) || (g.ldb & 3) ||
       (((uintptr_t)g.A | (uintptr_t)g.B) & 15) || (a_kc ? 0 : (g.M & 3)) || (b_nc ? (g.N & 3) : 0))
     return a3c_set_error(A3C_ERR_INVALID, "a3c_gemm", "unaligned operands (need 16-B alignment, dims %4)");
@@ -492,12 +493,13 @@ int a3c_gemm_reduce(const GemmArgs& g, hipStream_t s) {
   return 0;
 }
 
-int a3c_gemm(bool a_kc, bool b_nc, GemmArgs g, hipStream_t s) {
+int a3c_gemm(bool a_kc, bool b_nc, GemmArgs g, hipStream_t s, int* nsplit_eff) {
   if (g.M <= 0 || g.N <= 0) return 0;
   if (g.wg_split == 4) {   // in-workgroup split-K (k_gemm_f32_wks): no slab, no fold kernel
     g.nsplit = 1;
     int rc = gemm_setup(a_kc, b_nc, g);
     if (rc) return rc;
+    if (nsplit_eff) *nsplit_eff = g.nsplit;
     const int gx = (g.N + BN - 1) / BN, gy = (g.M + BM - 1) / BM;
     // g.xcd == 1: XCD-grouped 1-D grid (the kernel maps ids to tiles), else the plain 2-D grid
     const dim3 grid = g.xcd == 1 ? dim3((unsigned)(8 * ((gy + 7) / 8) * gx)) : dim3(gx, gy, 1);
@@ -512,6 +514,7 @@ int a3c_gemm(bool a_kc, bool b_nc, GemmArgs g, hipStream_t s) {
   if (g.wg_split > 1) return a3c_set_error(A3C_ERR_INVALID, "a3c_gemm", "wg_split: 4 only");
   int rc = gemm_setup(a_kc, b_nc, g);
   if (rc) return rc;
+  if (nsplit_eff) *nsplit_eff = g.nsplit;
   dim3 grid((g.N + BN - 1) / BN, (g.M + BM - 1) / BM, g.nsplit);
   // XCD-grouped order where the caller asks for it (the overlapped backward when it bounds the
   // iteration): it halves the backward GEMMs' HBM bytes, 124 -> 73 MB per iteration (profile
@@ -562,6 +565,97 @@ int a3c_gemm(bool a_kc, bool b_nc, GemmArgs g, hipStream_t s) {
   else hipLaunchKernelGGL((k_gemm_f32<false, false>), grid, dim3(256), 0, s, g);
   A3C_CHECK(hipGetLastError());
   return g.defer_reduce ? 0 : a3c_gemm_reduce(g, s);
+}
+
+// ---------------------------------------------------------------------------
+// C-ABI: the GEMM alone (include/a3c_hip.h a3c_gemm_f32 / a3c_gemm3_f32)
+// ---------------------------------------------------------------------------
+static int64_t slab_bytes(int M, int N, int split) {
+  return split > 1 ? (int64_t)split * M * N * (int64_t)sizeof(float) : 0;
+}
+
+// every rule of the header; what == the entry point's name.  Fills g (slab = ws when the split needs it)
+static int gemm_desc_args(const char* what, const a3c_gemm_desc* d, void* ws, int64_t ws_bytes, GemmArgs& g) {
+  auto bad = [&](const char* why) { return a3c_set_error(A3C_ERR_INVALID, what, why); };
+  auto mis = [](const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; };
+  if (!d) return bad("desc is NULL");
+  if (!d->A || !d->B || !d->C) return bad("A, B or C is NULL");
+  if (d->M < 1 || d->N < 1) return bad("M < 1 or N < 1");
+  if (d->K < 1) return bad("K < 1");
+  if (d->nsplit < 1) return bad("nsplit < 1");
+  if (d->epi < A3C_GEMM_STORE || d->epi > A3C_GEMM_MASKBITS) return bad("unknown epi");
+  if ((d->epi == A3C_GEMM_BIAS_RELU || d->epi == A3C_GEMM_BIAS) && !d->bias) return bad("epi needs bias");
+  if (d->epi == A3C_GEMM_MASK && !d->mask) return bad("epi needs mask");
+  if (d->epi == A3C_GEMM_MASKBITS && !d->maskbits) return bad("epi needs maskbits");
+  if (d->wg_split != 0 && d->wg_split != 4) return bad("wg_split: 0 or 4");
+  if (d->xcd < 0 || d->xcd > 2) return bad("xcd: 0, 1 or 2");
+  if (d->wg_split && d->xcd == 2) return bad("wg_split: xcd 0 or 1");
+  if (d->max_wgs < 0) return bad("max_wgs < 0");
+  const bool akc = d->a_kcontig != 0, bnc = d->b_ncontig != 0;
+  if (mis(d->A, 16) || mis(d->B, 16)) return bad("A and B need 16-byte alignment");
+  if (mis(d->C, 4) || mis(d->bias, 4) || mis(d->mask, 4) || mis(d->maskbits, 4) || mis(d->colsum, 4))
+    return bad("C, bias, mask, maskbits, colsum need 4-byte alignment");
+  if ((d->lda & 3) || (d->ldb & 3)) return bad("lda and ldb must be multiples of 4");
+  if ((akc || !bnc) && (d->K & 3)) return bad("K must be a multiple of 4 in this layout");
+  if (!akc && (d->M & 3)) return bad("M must be a multiple of 4 when a is k-strided");
+  if (bnc && (d->N & 3)) return bad("N must be a multiple of 4 when b is n-contiguous");
+  if (d->lda < (akc ? d->K : d->M) || d->ldb < (bnc ? d->N : d->K) || d->ldc < d->N)
+    return bad("lda, ldb or ldc shorter than a row");
+  if (d->epi == A3C_GEMM_MASK && d->ldm < d->N) return bad("ldm shorter than a mask row");
+  if (d->epi == A3C_GEMM_MASKBITS && d->ldm < (d->N + 31) / 32) return bad("ldm shorter than a row of mask words");
+  const int eff = d->wg_split ? 1 : a3c_gemm_effective_split(d->K, d->nsplit);
+  if (eff > 1) {
+    if (!ws) return bad("split-K needs a workspace");
+    if (mis(ws, 16)) return bad("workspace needs 16-byte alignment");
+    if (ws_bytes < slab_bytes(d->M, d->N, eff)) return bad("workspace too small (a3c_gemm_workspace_bytes)");
+  }
+  g = GemmArgs{};
+  g.A = d->A; g.lda = d->lda; g.B = d->B; g.ldb = d->ldb; g.C = d->C; g.ldc = d->ldc;
+  g.M = d->M; g.N = d->N; g.K = d->K;
+  g.epi = d->epi; g.bias = d->bias; g.mask = d->mask; g.maskbits = d->maskbits; g.ldm = d->ldm;
+  g.slab = eff > 1 ? (float*)ws : nullptr;
+  g.nsplit = d->nsplit; g.colsum = d->colsum;
+  g.xcd = d->xcd; g.max_wgs = d->max_wgs; g.big = d->big ? 1 : 0; g.wg_split = d->wg_split;
+  return 0;
+}
+
+extern "C" int a3c_gemm_workspace_bytes(int M, int N, int K, int nsplit, int* nsplit_eff, int64_t* bytes) {
+  if (M < 1 || N < 1 || K < 1 || nsplit < 1)
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_gemm_workspace_bytes", "M, N, K or nsplit < 1");
+  const int eff = a3c_gemm_effective_split(K, nsplit);
+  if (nsplit_eff) *nsplit_eff = eff;
+  if (bytes) *bytes = slab_bytes(M, N, eff);
+  return 0;
+}
+
+extern "C" int a3c_gemm_f32(const a3c_gemm_desc* d, void* workspace, int64_t workspace_bytes, int* nsplit_eff,
+                            void* stream) {
+  GemmArgs g;
+  if (int rc = gemm_desc_args("a3c_gemm_f32", d, workspace, workspace_bytes, g)) return rc;
+  return a3c_gemm(d->a_kcontig != 0, d->b_ncontig != 0, g, (hipStream_t)stream, nsplit_eff);
+}
+
+extern "C" int a3c_gemm3_f32(const a3c_gemm_desc* d, void* const* workspaces, const int64_t* workspace_bytes,
+                             int* nsplit_eff, void* stream) {
+  const char* what = "a3c_gemm3_f32";
+  if (!d) return a3c_set_error(A3C_ERR_INVALID, what, "desc is NULL");
+  GemmArgs g[3];
+  for (int i = 0; i < 3; ++i) {
+    if ((d[i].a_kcontig != 0) != (i == 2) || (d[i].b_ncontig != 0) != (i < 2))
+      return a3c_set_error(A3C_ERR_INVALID, what, "layouts: d[0], d[1] (a k-strided, b n-contiguous), d[2] (k, k)");
+    if (d[i].wg_split || d[i].big || d[i].xcd || d[i].max_wgs)
+      return a3c_set_error(A3C_ERR_INVALID, what, "wg_split, big, xcd and max_wgs must be 0");
+    if (int rc = gemm_desc_args(what, d + i, workspaces ? workspaces[i] : nullptr,
+                                workspace_bytes ? workspace_bytes[i] : 0, g[i]))
+      return rc;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = a3c_gemm3(g[0], g[1], g[2], s)) return rc;
+  for (int i = 0; i < 3; ++i) {
+    if (nsplit_eff) nsplit_eff[i] = g[i].nsplit;
+    if (int rc = a3c_gemm_reduce(g[i], s)) return rc;
+  }
+  return 0;
 }
 
 #ifdef A3C_WGLOG

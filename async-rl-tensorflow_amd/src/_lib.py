@@ -83,6 +83,16 @@ class PlayBuffers(ctypes.Structure):
                 ('lstm_h', c_void_p), ('lstm_c', c_void_p), ('episode_idx', c_void_p), ('sched', c_void_p)]
 
 
+class GemmDesc(ctypes.Structure):
+    """a3c_gemm_desc (a3c_gemm_f32 / a3c_gemm3_f32)."""
+    _fields_ = [('A', c_void_p), ('lda', c_i64), ('B', c_void_p), ('ldb', c_i64), ('C', c_void_p), ('ldc', c_i64),
+                ('bias', c_void_p), ('mask', c_void_p), ('maskbits', c_void_p), ('ldm', c_i64), ('colsum', c_void_p),
+                ('M', c_int), ('N', c_int), ('K', c_int), ('a_kcontig', c_int), ('b_ncontig', c_int), ('epi', c_int),
+                ('nsplit', c_int), ('wg_split', c_int), ('big', c_int), ('xcd', c_int), ('max_wgs', c_int)]
+
+
+GEMM_STORE, GEMM_BIAS_RELU, GEMM_BIAS, GEMM_MASK, GEMM_MASKBITS = 0, 1, 2, 3, 4   # A3C_GEMM_* epilogues
+
 # name -> (restype, argtypes)
 SIGNATURES = {
     'a3c_version': (ctypes.c_char_p, []),
@@ -133,6 +143,10 @@ SIGNATURES = {
     'a3c_conv2d_backward': (c_int, [c_void_p] * 6 + [c_int] * 10 + [c_void_p]),
     'a3c_matmul': (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_int, c_int, c_int,
                            c_void_p, c_int, c_int, c_void_p]),
+    'a3c_gemm_workspace_bytes': (c_int, [c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_i64)]),
+    'a3c_gemm_f32': (c_int, [ctypes.POINTER(GemmDesc), c_void_p, c_i64, ctypes.POINTER(c_int), c_void_p]),
+    'a3c_gemm3_f32': (c_int, [ctypes.POINTER(GemmDesc), ctypes.POINTER(c_void_p), ctypes.POINTER(c_i64),
+                              ctypes.POINTER(c_int), c_void_p]),
     'a3c_copy_params': (c_int, [c_void_p, c_void_p, c_i64, c_void_p]),
     'a3c_lstm_transpose': (c_int, [c_void_p, c_void_p, c_void_p]),
     'a3c_lstm_step': (c_int, [c_void_p] * 6 + [c_i64] + [c_void_p] * 6),
@@ -225,7 +239,8 @@ OPTIONAL_IN_OLD_BUILDS = MEASUREMENT_ONLY + ('a3c_engine_exchange_split', 'a3c_e
                                              'a3c_boot_action', 'a3c_sarsa_target', 'a3c_clip_adam_apply',
                                              'a3c_engine_set_optimizer', 'a3c_engine_adam_powers',
                                              'a3c_engine_set_adam_powers', 'a3c_engine_set_catch_rules',
-                                             'a3c_env_set_catch_rules', 'a3c_engine_set_first_screen')
+                                             'a3c_env_set_catch_rules', 'a3c_engine_set_first_screen',
+                                             'a3c_gemm_workspace_bytes', 'a3c_gemm_f32', 'a3c_gemm3_f32')
 
 KER_CONV12_FWD, KER_FC_FWD, KER_ENV_STEP, KER_CONV_BWD, KER_HEAD_SCREEN, KER_HEAD_SCREEN_CONV12, KER_FC_PART = 0, 1, 2, 3, 4, 5, 6
 # nature trunk passes (include/a3c_hip.h A3C_KER_NAT_*)

@@ -410,5 +410,42 @@ def sarsa_target(rewards, terminals, actions, boot_actions, q_target, A, discoun
     return out
 
 
+def gemm_workspace(M, N, K, nsplit=1):
+    """(effective split, workspace bytes) of a GEMM with ``nsplit`` requested (a3c_gemm_workspace_bytes; host only)."""
+    eff, nbytes = ctypes.c_int(), ctypes.c_int64()
+    check(lib().a3c_gemm_workspace_bytes(int(M), int(N), int(K), int(nsplit), ctypes.byref(eff), ctypes.byref(nbytes)),
+          'a3c_gemm_workspace_bytes')
+    return int(eff.value), int(nbytes.value)
+
+
+def gemm_desc(A, B, C, M, N, K, a_kcontig, b_ncontig, lda, ldb, ldc, epi=_lib.GEMM_STORE, bias=None, mask=None,
+              maskbits=None, ldm=0, colsum=None, nsplit=1, wg_split=0, big=0, xcd=0, max_wgs=0):
+    """a3c_gemm_desc over device tensors (only their data pointers are taken: any view, any excess behind the
+    matrix; the caller keeps them alive until the launch is enqueued).  include/a3c_hip.h has the rules."""
+    return _lib.GemmDesc(ptr(A), int(lda), ptr(B), int(ldb), ptr(C), int(ldc), ptr(bias), ptr(mask), ptr(maskbits),
+                         int(ldm), ptr(colsum), int(M), int(N), int(K), int(bool(a_kcontig)), int(bool(b_ncontig)),
+                         int(epi), int(nsplit), int(wg_split), int(big), int(xcd), int(max_wgs))
+
+
+def gemm(desc, workspace=None, workspace_bytes=None):
+    """C = epi(A B) on the fp32 matrix-core GEMM (a3c_gemm_f32); returns the effective split of the launch.
+    ``workspace``: a device tensor for the split-K slabs (its own size unless ``workspace_bytes`` says less)."""
+    eff = ctypes.c_int(0)
+    nb = 0 if workspace is None else workspace.numel() * workspace.element_size()
+    check(lib().a3c_gemm_f32(ctypes.byref(desc), ptr(workspace), int(nb if workspace_bytes is None else workspace_bytes),
+                             ctypes.byref(eff), stream_handle()), 'a3c_gemm_f32')
+    return int(eff.value)
+
+
+def gemm3(descs, workspaces):
+    """Three GEMMs as one launch, then their split-K folds (a3c_gemm3_f32); returns the three effective splits."""
+    d = (_lib.GemmDesc * 3)(*descs)
+    ws = (ctypes.c_void_p * 3)(*[ptr(w) for w in workspaces])
+    nb = (ctypes.c_int64 * 3)(*[0 if w is None else w.numel() * w.element_size() for w in workspaces])
+    eff = (ctypes.c_int * 3)()
+    check(lib().a3c_gemm3_f32(d, ws, nb, eff, stream_handle()), 'a3c_gemm3_f32')
+    return [int(e) for e in eff]
+
+
 def copy_params(dst, src):
     check(lib().a3c_copy_params(ptr(dst), ptr(src), int(src.numel()), stream_handle()), 'a3c_copy_params')

@@ -279,6 +279,65 @@ int a3c_matmul(const float* A, int64_t sam, int64_t sak, const float* B, int64_t
                int64_t ldc, int M, int N, int K, const float* bias, int relu, int accumulate, void* stream);
 
 /* ----------------------------------------------------------------------------
+ * The fp32 matrix-core GEMM of the fc layers, their gradients and the LSTM gate gradients
+ * (csrc/gemm.hip), alone: every tile form, operand layout and epilogue the engine can select,
+ * so each can be tested and timed without an engine around it.
+ *   C[m*ldc + n] = epi( sum_k A(m,k) * B(k,n) ),   m < M, n < N
+ *   A(m,k) = a_kcontig ? A[m*lda + k] : A[k*lda + m];  B(k,n) = b_ncontig ? B[k*ldb + n] : B[n*ldb + k]
+ *   epi: A3C_GEMM_STORE v; _BIAS_RELU max(v + bias[n], 0); _BIAS v + bias[n];
+ *        _MASK mask[m*ldm + n] > 0 ? v : 0;
+ *        _MASKBITS bit (n & 31) of maskbits[m*ldm + (n >> 5)] ? v : 0  (ldm in 32-bit words)
+ *   nsplit:   requested split of K into chunks of whole 16-wide k-tiles; the effective split
+ *             (a3c_gemm_workspace_bytes) may be smaller.  Effective split > 1: the partial tiles go to
+ *             `workspace` [split][M][N] and a fold kernel applies epi.
+ *   wg_split: 0, or 4 = K split over 4 wave groups inside each workgroup and folded in LDS (no
+ *             workspace, effective split 1; another summation grouping than the slab split).
+ *   big:      128x128 tiles; xcd: 0, 1, 2 tile order; max_wgs: 0 or a cap on the workgroups.  big
+ *             ignores xcd and max_wgs, wg_split ignores nsplit, big and max_wgs.  Tile size, order
+ *             and cap do not change a bit of the result.
+ *   colsum:   nullable; row s of [effective split][N] = sum over K-chunk s of B(k, n) (one row
+ *             with wg_split); the caller folds the rows.
+ * Alignment: A, B and the workspace 16 bytes, the other pointers 4; lda and ldb % 4; K % 4 unless
+ * (a k-strided, b n-contiguous); M % 4 when a is k-strided; N % 4 when b is n-contiguous.
+ * A3C_ERR_INVALID, nothing launched: a NULL desc, A, B or C; bias / mask / maskbits NULL where epi
+ * reads it; an unknown epi; M, N, K or nsplit < 1; a leading dimension shorter than its row; any
+ * alignment rule above; effective split > 1 with workspace NULL or workspace_bytes too small;
+ * wg_split not 0 or 4; xcd not 0, 1, 2; wg_split with xcd 2; max_wgs < 0.
+ *  a3c_gemm_workspace_bytes: *nsplit_eff and *bytes (either nullable) of a launch with `nsplit`
+ *             requested (wg_split launches need none).
+ *  a3c_gemm_f32: one GEMM; *nsplit_eff (nullable) = the split the launch used.
+ *  a3c_gemm3_f32: d[0..2] as ONE launch (the synchronous backward's dW_head, dW_fc, dl2) and then
+ *             their split-K folds.  Layouts are fixed: d[0], d[1] (a k-strided, b n-contiguous),
+ *             d[2] (a k-contiguous, b k-contiguous); wg_split, big, xcd, max_wgs must be 0.  Bit
+ *             for bit the three a3c_gemm_f32 calls.
+ * -------------------------------------------------------------------------- */
+#define A3C_GEMM_STORE 0
+#define A3C_GEMM_BIAS_RELU 1
+#define A3C_GEMM_BIAS 2
+#define A3C_GEMM_MASK 3
+#define A3C_GEMM_MASKBITS 4
+typedef struct a3c_gemm_desc {
+  const float* A; int64_t lda;
+  const float* B; int64_t ldb;
+  float* C; int64_t ldc;
+  const float* bias;
+  const float* mask;
+  const uint32_t* maskbits;
+  int64_t ldm;
+  float* colsum;
+  int M, N, K;
+  int a_kcontig, b_ncontig;
+  int epi;
+  int nsplit;
+  int wg_split, big, xcd, max_wgs;
+} a3c_gemm_desc;
+int a3c_gemm_workspace_bytes(int M, int N, int K, int nsplit, int* nsplit_eff, int64_t* bytes);
+int a3c_gemm_f32(const a3c_gemm_desc* d, void* workspace, int64_t workspace_bytes, int* nsplit_eff,
+                 void* stream);
+int a3c_gemm3_f32(const a3c_gemm_desc* d, void* const* workspaces, const int64_t* workspace_bytes,
+                  int* nsplit_eff, void* stream);
+
+/* ----------------------------------------------------------------------------
  * C5  LSTM head (BASELINE config 5; no reference code -- build-defined after TF1
  *     BasicLSTMCell, forget_bias 1.0, and the A3C-LSTM of assets/a3c.png's paper).
  *  a3c_lstm_transpose: w_t [4U][256+U] = w^T, the forward's operand layout (once per
