@@ -149,6 +149,10 @@ __device__ inline const uint8_t* state_plane(const StateAddr& a, int64_t b, int 
 #define WG_T1(dst) ((void)0)
 #endif
 
+#ifdef A3C_MARKERS   // debug builds only (tools/markers.py): engine.hip's marker kernel on stream s
+void a3c_mark(int id, hipStream_t s);
+#endif
+
 // Debug builds only (-DA3C_WGLOG, tools/wglog.py): every workgroup of the instrumented kernels
 // appends (start, end, kind | xcc | workgroup | HW_ID) to a device log, so which workgroups shared
 // a CU, and when, can be read back (a3c_debug_wglog).  Thread 0 logs at its own exit.
@@ -191,6 +195,7 @@ struct WgLog {
 #define WGLOG(kind) WgLog wgl_(kind)
 #define WGLOG_BIND(name) \
   void name(WglBuf* p) { (void)hipMemcpyToSymbol(HIP_SYMBOL(g_wgl), &p, sizeof(p)); }
+void a3c_wglog_bind_fwd(WglBuf*), a3c_wglog_bind_bwd(WglBuf*), a3c_wglog_bind_gemm(WglBuf*), a3c_wglog_bind_optim(WglBuf*);
 #else
 #define WGLOG(kind) ((void)0)
 #endif

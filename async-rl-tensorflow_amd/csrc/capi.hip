@@ -93,8 +93,10 @@ extern "C" int a3c_forward(const a3c_net_desc* net, const float* params, const u
   uint8_t* prep = (uint8_t*)align_ws(workspace);
   int rc = a3c_prep_fwd_launch(L, params, prep, (hipStream_t)stream);
   if (rc) return rc;
-  return a3c_forward_launch(L, params, prep, contiguous_states(states, B), B, act_l1, act_l2, act_l3, z, sel,
-                            (hipStream_t)stream, LAUNCH_ALONE);
+  FwdArgs a = {};
+  a.params = params; a.prep = prep; a.sa = contiguous_states(states, B); a.B = B;
+  a.act_l1 = act_l1; a.act_l2 = act_l2; a.act_l3 = act_l3; a.z = z; a.sel = &sel;
+  return a3c_forward_launch(L, a, (hipStream_t)stream, LAUNCH_ALONE);
 }
 
 extern "C" int a3c_select_action(int mode, const float* z, int64_t B, int zs, int A, const float* eps,
@@ -182,7 +184,9 @@ extern "C" int a3c_loss_backward(const a3c_net_desc* net, const float* params, c
       !target || !grads || !workspace || B <= 0 || B > 0x7fffffff || (((uintptr_t)states) & 15))
     return a3c_set_error(A3C_ERR_INVALID, "a3c_loss_backward", "bad argument");
   a3c_init_once();
-  return a3c_backward_launch(L, params, contiguous_states(states, B), B, act_l1, act_l2, act_l3, z, actions,
-                             target, beta, literal_adv, grads, loss_out, align_ws(workspace),
-                             (hipStream_t)stream, LAUNCH_ALONE);
+  BwdArgs a = {};
+  a.params = params; a.sa = contiguous_states(states, B); a.B = B;
+  a.act_l1 = act_l1; a.act_l2 = act_l2; a.act_l3 = act_l3; a.z = z; a.actions = actions; a.target = target;
+  a.beta = beta; a.literal = literal_adv; a.grads = grads; a.loss_out = loss_out; a.ws = align_ws(workspace);
+  return a3c_backward_launch(L, a, (hipStream_t)stream, LAUNCH_ALONE);
 }

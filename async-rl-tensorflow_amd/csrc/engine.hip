@@ -22,10 +22,6 @@
 #include "gemm.h"
 #include "nature.h"
 
-void a3c_init_once();
-int a3c_fc_fwd_launch(const float* A, const float* W, const float* bias, float* C, int64_t M, hipStream_t s,
-                      const LaunchMode& m, const float* Wrows = nullptr);
-
 // Per-rollout buffers.  Sync mode has one slot whose params are the live parameters and whose
 // tau is the live frame counter.  Overlap mode (cfg.overlap = 1) has two: rollout k fills slot
 // k & 1 with its own parameter snapshot and tau while the backward + apply of rollout k-1 (slot
@@ -143,8 +139,6 @@ struct a3c_engine {
   bool captured[NGRAPH];
   // overlap pipeline
   hipStream_t rs;          // rollout stream
-  hipStream_t gs;          // backward side stream (weight-gradient GEMMs beside the conv backward)
-  hipEvent_t ev_gfork, ev_gjoin;
   hipEvent_t ev_start, ev_roll[2];
   // split exchange (several GPUs, cfg.split_exchange): ev_head marks the fc / head gradients
   // clipped, mid-backward; a comm stream waits on it (a3c_engine_wait_grad_head)
@@ -243,9 +237,6 @@ extern "C" int a3c_engine_destroy(a3c_engine* e) {
   if (e->rs) (void)hipStreamSynchronize(e->rs);
   drop_graphs(e);
   if (e->rs) (void)hipStreamDestroy(e->rs);
-  if (e->gs) (void)hipStreamDestroy(e->gs);
-  if (e->ev_gfork) (void)hipEventDestroy(e->ev_gfork);
-  if (e->ev_gjoin) (void)hipEventDestroy(e->ev_gjoin);
   if (e->ev_start) (void)hipEventDestroy(e->ev_start);
   if (e->ev_head) (void)hipEventDestroy(e->ev_head);
   for (int k = 0; k < 2; ++k) {
@@ -459,13 +450,6 @@ extern "C" int a3c_engine_create_opts(const a3c_engine_config* cfg, const a3c_en
   if (a3c_make_tab(L.nt, L.off, L.size, L.total, &e->tt) ||
       (e->nat ? a3c_nat_fused_tab(L, &e->tt_f) : a3c_fused_tab(L, &e->tt_f)))
     return fail("tensor table");
-  {
-    bool ok = hipStreamCreateWithFlags(&e->gs, hipStreamNonBlocking) == hipSuccess &&
-              hipEventCreateWithFlags(&e->ev_gfork, hipEventDisableTiming) == hipSuccess &&
-              hipEventCreateWithFlags(&e->ev_gjoin, hipEventDisableTiming) == hipSuccess;
-    if (!ok)
-      return fail("stream/event creation failed");
-  }
   // the split exchange needs eager launches (its event is recorded mid-backward) and a peer
   e->split = cfg->split_exchange && cfg->world_size > 1 && !cfg->use_graph && !e->nat;
   e->l2bits = e->nat ? 0 : l2bits_choice(e);
@@ -641,6 +625,19 @@ static StateAddr nat_step_addr(const a3c_engine* e, int t) {
   sa.span = spans_on() ? e->spans + (size_t)SPAN_RECS * SPAN_WGS * 2 : nullptr;
   return sa;
 }
+// The engine's trunk's activation rows (l4: the nature trunk's fc output, null on NIPS): a slot's saved
+// ones from row o on, and the bootstrap state's scratch rows (NIPS: no l1 kept)
+struct Acts { float *l1, *l2, *l3, *l4; };
+static Acts slot_acts(const a3c_engine* e, const Slot& sl, int64_t o) {
+  if (e->nat) return {sl.act_l1 + o * NT_A1, sl.act_l2 + o * NT_A2, sl.act_l3 + o * NT_FLAT, sl.act_l4 + o * NT_FC};
+  return {sl.act_l1 + o * C1_P * C1_N, sl.act_l2 + o * FLAT, sl.act_l3 + o * FC, nullptr};
+}
+static Acts boot_acts(const a3c_engine* e, const Slot& sl) {
+  const int64_t E = e->E;
+  float* x = sl.nscr;
+  if (e->nat) return {x, x + E * NT_A1, x + E * (NT_A1 + NT_A2), x + E * (NT_A1 + NT_A2 + NT_FLAT)};
+  return {nullptr, sl.scr_l2, sl.scr_l3, nullptr};
+}
 // conv fusion (k_head_screen_conv12) runs with the device envs and the fused screen
 static bool conv_fused(const a3c_engine* e) { return e->fuse_conv && !e->ext && e->fused_screen; }
 // the fused rollout's fc as K-slice partials folded by the head (feed-forward head only)
@@ -787,16 +784,15 @@ static int enqueue_step(a3c_engine* e, const Slot& sl, int t, hipStream_t s) {
     nx.act_l2 = t + 1 < n ? sl.act_l2 + (o + E) * FLAT : sl.scr_l2;
     nx.l2m = t + 1 < n && l2bits_on(e) ? sl.l2m + (o + E) * C2_Q : nullptr;
   }
-  int rc;
-  if (e->nat)
-    rc = a3c_nat_forward_launch(L, sl.P, nat_step_addr(e, t), E, sl.act_l1 + o * NT_A1,
-                                sl.act_l2 + o * NT_A2, sl.act_l3 + o * NT_FLAT, sl.act_l4 + o * NT_FC, sl.z + o * zs, sel,
-                                (const uint16_t*)sl.prep, e->nat_fws, s, e->mode);
-  else
-    rc = a3c_forward_launch(L, sl.P, sl.prep, ring_addr(e, t, e->counters), E, sl.act_l1 + o * C1_P * C1_N,
-                              sl.act_l2 + o * FLAT, sl.act_l3 + o * FC, sl.z + o * zs, sel, s, e->mode,
-                              L.lstm ? &ls : nullptr, fuse && t > 0, has_next ? &nx : nullptr,
-                              fc_split(e) ? e->fcpart : nullptr, l2bits_on(e) ? sl.l2m + o * C2_Q : nullptr);
+  const Acts x = slot_acts(e, sl, o);
+  FwdArgs a = {};   // (the nature trunk runs none of the fusions: its optional fields stay clear)
+  a.params = sl.P; a.prep = sl.prep; a.B = E;
+  a.sa = e->nat ? nat_step_addr(e, t) : ring_addr(e, t, e->counters);
+  a.act_l1 = x.l1; a.act_l2 = x.l2; a.act_l3 = x.l3; a.act_l4 = x.l4;
+  a.z = sl.z + o * zs; a.sel = &sel; a.nat_ws = e->nat_fws;
+  a.ls = L.lstm ? &ls : nullptr; a.skip_conv12 = fuse && t > 0; a.next = has_next ? &nx : nullptr;
+  a.fc_part = fc_split(e) ? e->fcpart : nullptr; a.l2m = l2bits_on(e) ? sl.l2m + o * C2_Q : nullptr;
+  int rc = a3c_forward_launch(L, a, s, e->mode);
   if (rc) return rc;
   if (dev_env && !e->fused_screen) {
     rc = a3c_env_screen_launch(E, sl.frames + o, e->pool, e->ring, e->R, e->counters, t, s);
@@ -828,18 +824,16 @@ static int enqueue_rollout_end(a3c_engine* e, const Slot& sl, hipStream_t s) {
       ls.h = sl.lhb; ls.c = sl.lcb;
       if (e->lstm_fcfold) ls.fc_tick = e->fctick;
     }
-    if (e->nat) {
-      float* x = sl.nscr;
-      // (no span record: s_n is the next rollout's s_0, whose step-0 launch keys the same record)
-      return a3c_nat_forward_launch(L, sl.P, ring_addr(e, n, e->counters), E, x, x + E * NT_A1,
-                                    x + E * (NT_A1 + NT_A2), x + E * (NT_A1 + NT_A2 + NT_FLAT), sl.z + e->nE * L.zs,
-                                    none, (const uint16_t*)sl.prep, e->nat_fws, s, e->mode);
-    }
-    int rc = a3c_forward_launch(L, sl.P, sl.prep, ring_addr(e, n, e->counters), E, nullptr, sl.scr_l2,
-                                sl.scr_l3, sl.z + e->nE * L.zs, none, s, e->mode, L.lstm ? &ls : nullptr,
-                                conv_fused(e),   // s_n's convs ran in the last step's kernel
-                                nullptr, fc_split(e) ? e->fcpart : nullptr);
-    return rc;
+    const Acts x = boot_acts(e, sl);
+    FwdArgs a = {};
+    a.params = sl.P; a.prep = sl.prep; a.B = E;
+    // (nature trunk: no span record: s_n is the next rollout's s_0, whose step-0 launch keys the same record)
+    a.sa = ring_addr(e, n, e->counters);
+    a.act_l1 = x.l1; a.act_l2 = x.l2; a.act_l3 = x.l3; a.act_l4 = x.l4;
+    a.z = sl.z + e->nE * L.zs; a.sel = &none; a.nat_ws = e->nat_fws;
+    a.ls = L.lstm ? &ls : nullptr; a.fc_part = fc_split(e) ? e->fcpart : nullptr;
+    a.skip_conv12 = conv_fused(e);   // s_n's convs ran in the last step's kernel
+    return a3c_forward_launch(L, a, s, e->mode);
   }
   if (e->overlap) {
     hipLaunchKernelGGL(k_advance_tau, dim3(1), dim3(1), 0, s, e->counters, n);
@@ -877,10 +871,6 @@ static void mark(int, hipStream_t) {}
 #endif
 
 #ifdef A3C_WGLOG
-void a3c_wglog_bind_fwd(WglBuf*);
-void a3c_wglog_bind_bwd(WglBuf*);
-void a3c_wglog_bind_gemm(WglBuf*);
-void a3c_wglog_bind_optim(WglBuf*);
 // Debug builds only (tools/wglog.py): on >= 0 switches logging, reset clears the log; the whole
 // WglBuf is copied to host when host != nullptr (after a device sync); returns its size in bytes
 extern "C" int64_t a3c_debug_wglog(void* host, int on, int reset) {
@@ -1048,17 +1038,20 @@ static int enqueue_grad(a3c_engine* e, const Slot& sl, hipStream_t s) {
     // Sarsa draws a_n from the slot's own Q rows of s_n; double Q (agent.py:176-184) takes
     // its argmax from the online net's q of s_{t+1}: rows t+1 of the rollout's own q (the slot's
     // parameters, those the loss is taken at), and for t = n-1 this forward of s_n with them
+    FwdArgs f = {};   // both forwards run into the scratch rows: no l1 kept, no action drawn
+    f.act_l2 = sl.scr_l2; f.act_l3 = sl.scr_l3; f.sel = &none;
     if (e->sarsa || c.double_q) {
-      rc = a3c_forward_launch(L, sl.P, sl.prep, ring_addr(e, n, sl.tau), E, nullptr, sl.scr_l2, sl.scr_l3, zboot,
-                              none, s, e->mode);
+      f.params = sl.P; f.prep = sl.prep; f.sa = ring_addr(e, n, sl.tau); f.B = E; f.z = zboot;
+      rc = a3c_forward_launch(L, f, s, e->mode);
       if (rc) return rc;
     }
     // the target network on s_{t+1} of every transition (agent.py:186: n*E rows from s_1), or with
     // q_nstep (Algorithm S2) on the one bootstrap state s_n of every env (E rows)
     rc = a3c_prep_fwd_launch(L, e->tparams, e->prep_t, s);
     if (rc) return rc;
-    rc = a3c_forward_launch(L, e->tparams, e->prep_t, ring_addr(e, c.q_nstep ? n : 1, sl.tau), c.q_nstep ? E : e->nE,
-                            nullptr, sl.scr_l2, sl.scr_l3, e->zt, none, s, e->mode);
+    f.params = e->tparams; f.prep = e->prep_t; f.z = e->zt;
+    f.sa = ring_addr(e, c.q_nstep ? n : 1, sl.tau); f.B = c.q_nstep ? E : e->nE;
+    rc = a3c_forward_launch(L, f, s, e->mode);
     if (rc) return rc;
     if (e->sarsa) {
       // one kernel draws, from the slot's rows, the action the rollout's head would draw in s_n, at the
@@ -1089,17 +1082,12 @@ static int enqueue_grad(a3c_engine* e, const Slot& sl, hipStream_t s) {
       ra.values = sl.z + L.A; ra.value_stride = zs; ra.lambda = (double)c.gae_lambda;
     }
   }
-  static const bool fork_env = A3C_AB_KNOB("A3C_BWD_FORK", 0) != 0;  // measured slower
-  const bool fork = fork_env && !L.lstm;
   LstmBwd lb = {};
   if (L.lstm) {
     lb.n = n; lb.E = E;
     lb.h = sl.lh; lb.c = sl.lc; lb.hp = sl.lhp; lb.cp = sl.lcp; lb.gates = sl.lg;
     lb.dh = e->ldh; lb.ws = e->lws;
   }
-  StateAddr bsa = ring_addr(e, 0, sl.tau);
-  bsa.span = spans_on() ? e->spans : nullptr;   // one record per backward (tau advances by n)
-  bsa.span_div = n;
   // the per-tensor squared norms (+ lr / target-sync schedule from the device step counter) come
   // out of the backward's last kernel (k_finalize): no separate k_sumsq launch (round 3)
   OptParams op = opt_params(e, sl);
@@ -1113,16 +1101,18 @@ static int enqueue_grad(a3c_engine* e, const Slot& sl, hipStream_t s) {
     sp.sumsq_out = e->sumsq;
     sp.cut = L.off[T_FCW];
   }
-  if (e->nat)
-    rc = a3c_nat_backward_launch(L, sl.P, bsa, e->nE, sl.act_l1, sl.act_l2, sl.act_l3, sl.act_l4, sl.z, sl.actions,
-                                 sl.R_buf, c.beta, c.literal_adv, e->grads, e->loss, e->ws, s, &ra, &sf,
-                                 (const uint16_t*)sl.prep);
-  else
-  rc = a3c_backward_launch(L, sl.P, bsa, e->nE, sl.act_l1, sl.act_l2, sl.act_l3, sl.z,
-                           sl.actions, sl.R_buf, c.beta, c.literal_adv, e->grads, e->loss, e->ws, s, e->mode,
-                           &ra, fork && !e->split ? e->gs : nullptr, fork && !e->split ? e->ev_gfork : nullptr,
-                           fork && !e->split ? e->ev_gjoin : nullptr, L.lstm ? &lb : nullptr, &sf,
-                           e->split ? &sp : nullptr, l2bits_on(e) ? sl.l2m : nullptr);
+  const Acts x = slot_acts(e, sl, 0);
+  BwdArgs b = {};
+  b.params = sl.P; b.B = e->nE;
+  b.sa = ring_addr(e, 0, sl.tau);
+  b.sa.span = spans_on() ? e->spans : nullptr;   // one record per backward (tau advances by n)
+  b.sa.span_div = n;
+  b.act_l1 = x.l1; b.act_l2 = x.l2; b.act_l3 = x.l3; b.act_l4 = x.l4;
+  b.z = sl.z; b.actions = sl.actions; b.target = sl.R_buf; b.beta = c.beta; b.literal = c.literal_adv;
+  b.grads = e->grads; b.loss_out = e->loss; b.ws = e->ws;
+  b.ra = &ra; b.sf = &sf; b.lb = L.lstm ? &lb : nullptr; b.sp = e->split ? &sp : nullptr;
+  b.l2m = l2bits_on(e) ? sl.l2m : nullptr; b.nat_wt = e->nat ? (const uint16_t*)sl.prep : nullptr;
+  rc = a3c_backward_launch(L, b, s, e->mode);
   if (rc) return rc;
   if (c.world_size > 1 && !e->split) {
     // multi-GPU: clip this worker's gradient (agent.py:319) before the cross-GPU exchange
@@ -1998,26 +1988,23 @@ static int enqueue_play_step(a3c_engine* e, int mode, int t, int32_t* actions, f
   sel.ring = c.ring;
   sel.R = c.R;
   sel.frame84 = e->frame84;
-  StateAddr sa = ring_addr(e, 0, c.counters);
-  sa.base = c.ring;
-  sa.env_stride = (int64_t)c.R * PLANE;
-  sa.R = c.R;
-  const uint8_t* frozen = c.bk.frozen + (int64_t)par * E;
   const int64_t hc = (int64_t)E * LSTM_U;
-  int rc;
-  if (e->nat) {
-    rc = a3c_nat_forward_launch(L, e->params, sa, E, c.a1, c.a2, c.a3, c.a4, z, sel, (const uint16_t*)c.prep,
-                                c.nat_fws, s, e->mode, frozen);
-  } else {
-    LstmStep ls = {};
-    if (L.lstm) {
-      ls.wt = c.lwt;
-      ls.h_src = c.lh + par * hc; ls.c_src = c.lc + par * hc;
-      ls.h = c.lh + (par ^ 1) * hc; ls.c = c.lc + (par ^ 1) * hc;
-    }
-    rc = a3c_forward_launch(L, e->params, c.prep, sa, E, nullptr, c.a2, c.a3, z, sel, s, e->mode,
-                            L.lstm ? &ls : nullptr, false, nullptr, nullptr, nullptr, frozen);
+  LstmStep ls = {};
+  if (L.lstm) {
+    ls.wt = c.lwt;
+    ls.h_src = c.lh + par * hc; ls.c_src = c.lc + par * hc;
+    ls.h = c.lh + (par ^ 1) * hc; ls.c = c.lc + (par ^ 1) * hc;
   }
+  FwdArgs a = {};
+  a.params = e->params; a.prep = c.prep; a.B = E;
+  a.sa = ring_addr(e, 0, c.counters);
+  a.sa.base = c.ring;
+  a.sa.env_stride = (int64_t)c.R * PLANE;
+  a.sa.R = c.R;
+  a.act_l1 = c.a1; a.act_l2 = c.a2; a.act_l3 = c.a3; a.act_l4 = c.a4;   // (a1, a4: null on the NIPS trunk)
+  a.z = z; a.sel = &sel; a.nat_ws = c.nat_fws;
+  a.ls = L.lstm ? &ls : nullptr; a.play_frozen = c.bk.frozen + (int64_t)par * E;
+  int rc = a3c_forward_launch(L, a, s, e->mode);
   if (rc) return rc;
   if (rf)
     return a3c_play_refill_launch(e->envp, c.env, c.bk, *rf, E, t, (HIST - 1) + (int64_t)t, c.rraw, c.terms, c.counters, e->pool, c.ring, c.R,

@@ -12,6 +12,10 @@ int a3c_pool_fill_launch(uint8_t* pool, int P, uint32_t k0, uint32_t k1, hipStre
 // Catch (A3C_GAME_CATCH): frames 0..639 of an RGB pool of P >= 640 frames rendered from the frame index
 // (visible_rows: the ball is drawn in the frames of rows < visible_rows; 10: all)
 int a3c_pool_render_catch_launch(uint8_t* pool, int P, int visible_rows, hipStream_t s);
+// preprocess.hip: Environment.screen of frames idx[0..n) of rgb into out; its kernels' output rows per workgroup
+int a3c_launch_screen_atari(const uint8_t* rgb, const int32_t* idx, int64_t n, uint8_t* out, int64_t stride,
+                            hipStream_t s);
+int a3c_screen_rows();
 int a3c_env_init_launch(const EnvParams& p, const EnvBufs& b, int E, const uint8_t* pool, uint8_t* ring,
                         int R, int64_t* counters, hipStream_t s, int frame84 = 0);
 // screen of frame env.frame[(HIST-1)&1][e] of the pool into all HIST ring slots of env e

@@ -357,8 +357,6 @@ int a3c_play_refill_launch(const EnvParams& p, const EnvBufs& b, const PlayBook&
   return 0;
 }
 
-int a3c_screen_rows();
-
 template <int ROWS>
 static void launch_env_screen(int E, const int32_t* frames, const uint8_t* pool, uint8_t* ring, int R,
                               const int64_t* counters, int t, hipStream_t s) {

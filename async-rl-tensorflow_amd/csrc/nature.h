@@ -32,27 +32,22 @@ inline int64_t nat_act_floats() { return (int64_t)NT_A1 + NT_A2 + NT_FLAT + NT_F
 // forward of B states s_{tau0 + b / E} (sa) with parameters P.  Activations [B][...] NHWC:
 // l1 [B][12800], l2 [B][5184], l3 [B][3136] (the (h,w,c) flatten of network.py's linear), l4 [B][512];
 // z [B][zs] (logits, value); sel.mode >= 0: action draw + fused env act (as the NIPS head kernels).
-// ws: a3c_nat_fwd_ws_floats(B) floats (split-K slabs; with w1t null, also the prepared weight
-// terms, made there first).  w1t: the prepared block a3c_nat_prep_launch made from P (the engine's
+// a.nat_ws: a3c_nat_fwd_ws_floats(B) floats (split-K slabs; with a.prep null, also the prepared weight
+// terms, made there first).  a.prep: the prepared block a3c_nat_prep_launch made from P (the engine's
 // rollouts: conv1's terms at its start, then the conv2 / conv3 forms, A3C_NAT_*_OFF).
+// The nature body of a3c_forward_launch (net.h); m: the step tail's head + screen variant.
 int64_t a3c_nat_fwd_ws_floats(int64_t B);
-int a3c_nat_forward_launch(const NetLayout& L, const float* P, const StateAddr& sa, int64_t B, float* l1, float* l2,
-                           float* l3, float* l4, float* z, const HeadSelect& sel, const uint16_t* w1t, float* ws,
-                           hipStream_t s, const LaunchMode& m,   // (m: the step tail's head + screen variant)
-                           const uint8_t* play_frozen = nullptr);   // (play: as a3c_forward_launch)
+int a3c_nat_forward_launch(const NetLayout& L, const FwdArgs& a, hipStream_t s, const LaunchMode& m);
 
-struct ReturnsArgs;
+struct BwdArgs;
 struct SumsqFused;
 // loss + backward over B samples (network.py:81-94 with the SURVEY A11 fixes, as the NIPS path):
 // gradients of every tensor into grads (TF order), loss terms summed into loss_out[4]; with sf, the
 // per-tensor squared-norm partials (layout a3c_nat_fused_tab) and the lr schedule as well.
 int64_t a3c_nat_bwd_ws_floats(const NetLayout& L, int64_t B);
-// wt: the prepared weight terms of P (a3c_nat_prep_launch), or null: prepared into ws first
-int a3c_nat_backward_launch(const NetLayout& L, const float* P, const StateAddr& sa, int64_t B, const float* l1,
-                            const float* l2, const float* l3, const float* l4, const float* z,
-                            const int32_t* actions, const float* target, float beta, int literal, float* grads,
-                            float* loss_out, float* ws, hipStream_t s, const ReturnsArgs* ra, const SumsqFused* sf,
-                            const uint16_t* wt);
+// a.nat_wt: the prepared weight terms of P (a3c_nat_prep_launch), or null: prepared into ws first.
+// The nature body of a3c_backward_launch (net_bwd.h).
+int a3c_nat_backward_launch(const NetLayout& L, const BwdArgs& a, hipStream_t s);
 int a3c_nat_fused_tab(const NetLayout& L, TensorTab* tt);
 // the single launches behind both (a3c_engine_time_kernel): forward passes over B states
 // (fws: the fc's split-K slabs), backward passes over B samples on the plan's buffers in bws

@@ -1674,9 +1674,13 @@ int a3c_nat_prep_launch(const NetLayout& L, const float* P, uint16_t* w1t, const
 // ---------------------------------------------------------------------------------------
 // forward
 // ---------------------------------------------------------------------------------------
-int a3c_nat_forward_launch(const NetLayout& L, const float* P, const StateAddr& sa, int64_t B, float* l1, float* l2,
-                           float* l3, float* l4, float* z, const HeadSelect& sel, const uint16_t* w1t, float* ws,
-                           hipStream_t s, const LaunchMode& m, const uint8_t* play_frozen) {
+int a3c_nat_forward_launch(const NetLayout& L, const FwdArgs& a, hipStream_t s, const LaunchMode& m) {
+  const float* P = a.params;
+  const int64_t B = a.B;
+  float *l3 = a.act_l3, *l4 = a.act_l4, *z = a.z, *ws = a.nat_ws;
+  const HeadSelect& sel = *a.sel;
+  const uint16_t* w1t = (const uint16_t*)a.prep;   // (a3c_nat_prep_launch's block)
+  const uint8_t* play_frozen = a.play_frozen;
   if (L.trunk != A3C_TRUNK_NATURE || B <= 0 || B * NT1_P > 0x7fffffffLL)
     return a3c_set_error(A3C_ERR_INVALID, "a3c_nat_forward", "nature trunk, 0 < B, B * 400 < 2^31");
   if (play_frozen && !(sel.mode >= 0 && sel.env_on && sel.pool))
@@ -1691,7 +1695,7 @@ int a3c_nat_forward_launch(const NetLayout& L, const float* P, const StateAddr& 
   // (the play step keeps the fc's own fold: its tail is the 512-wide play head alone)
   const bool fold_in_head = step_tail && fcs > 1 && !nat_bf(NAT_FCF) && nat_fold_head() && !play_frozen;
   for (int pass = NAT_C1F; pass <= (fold_in_head ? NAT_C3F : NAT_FCF); ++pass) {
-    const int rc = a3c_nat_pass_launch(pass, L, P, sa, B, l1, l2, l3, l4, w1t, ws, nullptr, s);
+    const int rc = a3c_nat_pass_launch(pass, L, P, a.sa, B, a.act_l1, a.act_l2, l3, l4, w1t, ws, nullptr, s);
     if (rc) return rc;
   }
   if (fold_in_head) {   // the fc's K-slice partials, folded by the head + act + screen kernel
@@ -1743,15 +1747,17 @@ int a3c_nat_fused_tab(const NetLayout& L, TensorTab* tt) {
   return 0;
 }
 
-int a3c_nat_backward_launch(const NetLayout& L, const float* P, const StateAddr& sa, int64_t B, const float* l1,
-                            const float* l2, const float* l3, const float* l4, const float* z,
-                            const int32_t* actions, const float* target, float beta, int literal, float* grads,
-                            float* loss_out, float* ws, hipStream_t s, const ReturnsArgs* ra_in, const SumsqFused* sf,
-                            const uint16_t* wt) {
+int a3c_nat_backward_launch(const NetLayout& L, const BwdArgs& args, hipStream_t s) {
+  const float* P = args.params;
+  const int64_t B = args.B;
+  const float *l3 = args.act_l3, *l4 = args.act_l4;
+  float *grads = args.grads, *ws = args.ws;
+  const SumsqFused* sf = args.sf;
+  const uint16_t* wt = args.nat_wt;
   if (L.trunk != A3C_TRUNK_NATURE || B <= 0 || B * NT1_P > 0x7fffffffLL)
     return a3c_set_error(A3C_ERR_INVALID, "a3c_nat_backward", "nature trunk, 0 < B, B * 400 < 2^31");
   ReturnsArgs ra = {};
-  if (ra_in) ra = *ra_in;
+  if (args.ra) ra = *args.ra;
   const NatPlan p = nat_plan(L, B);
   if (!wt) {   // one-off backward: the weight terms into the workspace first
     uint16_t* t = (uint16_t*)(ws + p.wprep);
@@ -1762,8 +1768,8 @@ int a3c_nat_backward_launch(const NetLayout& L, const float* P, const StateAddr&
   float* dl4 = ws + p.dl4;
   float* terms = ws + p.terms;
   // returns (fused), losses, dz, dl4 = (dz [W_p W_v]^T) * (l4 > 0)
-  int rc = a3c_head_bwd_launch(NT_FC, L, z, actions, target, l4, P + L.off[N_HW], P + L.off[N_VW], beta, literal, B, dz,
-                               dl4, terms, ra, 1, s);
+  int rc = a3c_head_bwd_launch(NT_FC, L, args.z, args.actions, args.target, l4, P + L.off[N_HW], P + L.off[N_VW],
+                               args.beta, args.literal, B, dz, dl4, terms, ra, 1, s);
   if (rc) return rc;
   // head weights: dW[512][zs] = l4^T dz (split-K folded by the finalize), db = colsum(dz)
   GemmArgs gh = {};
@@ -1808,7 +1814,7 @@ int a3c_nat_backward_launch(const NetLayout& L, const float* P, const StateAddr&
   }
   if (rc) return rc;
   for (int pass = NAT_C3W; pass <= NAT_C1W; ++pass) {
-    rc = a3c_nat_pass_launch(pass, L, P, sa, B, l1, l2, l3, l4, wt, nullptr, ws, s);
+    rc = a3c_nat_pass_launch(pass, L, P, args.sa, B, args.act_l1, args.act_l2, l3, l4, wt, nullptr, ws, s);
     if (rc) return rc;
   }
   // the weight slabs in NAT_GROUPS fixed-order groups, then k_finalize: every segment, the loss
@@ -1853,7 +1859,7 @@ int a3c_nat_backward_launch(const NetLayout& L, const float* P, const StateAddr&
     fs.nsum = 1;
     nsumblk = fs.sum_c0[1];
   }
-  return a3c_finalize_launch(fs, nsumblk, terms, B, loss_out, s);
+  return a3c_finalize_launch(fs, nsumblk, terms, B, args.loss_out, s);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1893,8 +1899,10 @@ extern "C" int a3c_nature_forward(const a3c_net_desc* net, const float* params, 
   HeadSelect sel = {};
   sel.mode = -1;
   sel.E = 1;
-  return a3c_nat_forward_launch(L, params, nat_states(states, B), B, l1, l2, l3, l4, z, sel, nullptr,
-                                nat_align(workspace), (hipStream_t)stream, LAUNCH_ALONE);
+  FwdArgs a = {};   // (no prepared block: made in the workspace)
+  a.params = params; a.sa = nat_states(states, B); a.B = B; a.z = z; a.sel = &sel;
+  a.act_l1 = l1; a.act_l2 = l2; a.act_l3 = l3; a.act_l4 = l4; a.nat_ws = nat_align(workspace);
+  return a3c_nat_forward_launch(L, a, (hipStream_t)stream, LAUNCH_ALONE);
 }
 
 extern "C" int a3c_nature_loss_backward(const a3c_net_desc* net, const float* params, const uint8_t* states,
@@ -1907,9 +1915,11 @@ extern "C" int a3c_nature_loss_backward(const a3c_net_desc* net, const float* pa
   if (!params || !states || !l1 || !l2 || !l3 || !l4 || !z || !actions || !target || !grads || !workspace ||
       B <= 0 || B * NT1_P > 0x7fffffffLL || (((uintptr_t)grads | (uintptr_t)l3 | (uintptr_t)l4) & 15))
     return a3c_set_error(A3C_ERR_INVALID, "a3c_nature_loss_backward", "bad argument");
-  return a3c_nat_backward_launch(L, params, nat_states(states, B), B, l1, l2, l3, l4, z, actions, target, beta,
-                                 literal_adv, grads, loss_out, nat_align(workspace), (hipStream_t)stream, nullptr,
-                                 nullptr, nullptr);
+  BwdArgs a = {};   // (no fused returns or norms, no prepared weight terms)
+  a.params = params; a.sa = nat_states(states, B); a.B = B;
+  a.act_l1 = l1; a.act_l2 = l2; a.act_l3 = l3; a.act_l4 = l4; a.z = z; a.actions = actions; a.target = target;
+  a.beta = beta; a.literal = literal_adv; a.grads = grads; a.loss_out = loss_out; a.ws = nat_align(workspace);
+  return a3c_nat_backward_launch(L, a, (hipStream_t)stream);
 }
 
 // Catch: k_nat_head's A3C_GAME_CATCH instantiation, emitted behind every other kernel

@@ -208,15 +208,32 @@ struct Conv12Next {
   float* act_l2;
   uint32_t* l2m;            // nullable: act_l2's ReLU mask as bits [b][81] (the backward's dl2 epilogue)
 };
-// ls (LSTM head, C5): the cell step runs on act_l3 and the heads read ls->h
-// play_frozen (a3c_engine_play, Agent.play agent.py:351-391): the step's tail is the play form of the
-// head + act + screen kernel -- act with is_training = false, no new game on a terminal, and envs
-// with play_frozen[e] != 0 left untouched (no z row, action, env state or ring slot written)
-int a3c_forward_launch(const NetLayout& L, const float* params, const uint8_t* prep, const StateAddr& sa,
-                       int64_t B, float* act_l1, float* act_l2, float* act_l3, float* z, const HeadSelect& sel,
-                       hipStream_t s, const LaunchMode& m, const LstmStep* ls = nullptr, bool skip_conv12 = false,
-                       const Conv12Next* next = nullptr, float* fc_part = nullptr, uint32_t* l2m = nullptr,
-                       const uint8_t* play_frozen = nullptr);
+// What a forward of B states takes, on either trunk (a host-side bundle: no kernel sees it).
+// FwdArgs a = {} asks for no optional feature.
+struct FwdArgs {
+  const float* params;
+  const uint8_t* prep;      // the prepared block of `params` (nature one-off path: null, made in nat_ws first)
+  StateAddr sa;
+  int64_t B;
+  float *act_l1, *act_l2, *act_l3, *act_l4;   // l1: nullable on the NIPS trunk; l4: nature trunk only
+  float* z;
+  const HeadSelect* sel;    // the caller's, not a copy (~300 bytes per launch)
+  // optional, NIPS trunk
+  const LstmStep* ls;       // LSTM head (C5): the cell step runs on act_l3 and the heads read ls->h
+  bool skip_conv12;         // conv1 + conv2 of these states ran in the previous step's k_head_screen_conv12
+  const Conv12Next* next;   // the next states' conv1 + conv2, fused into this step's head + screen
+  float* fc_part;           // the fc as FC_NS K-slice partials, folded by the head (or the LSTM cell)
+  uint32_t* l2m;            // act_l2's ReLU mask as bits (Conv12Next)
+  // optional, both trunks: play_frozen (a3c_engine_play, Agent.play agent.py:351-391): the step's tail is the
+  // play form of the head + act + screen kernel -- act with is_training = false, no new game on a terminal, and
+  // envs with play_frozen[e] != 0 left untouched (no z row, action, env state or ring slot written)
+  const uint8_t* play_frozen;
+  float* nat_ws;            // nature trunk: a3c_nat_fwd_ws_floats(B) floats
+};
+// dispatches on L.trunk: the NIPS body (net_fwd.hip) or a3c_nat_forward_launch (nature.hip)
+int a3c_forward_launch(const NetLayout& L, const FwdArgs& a, hipStream_t s, const LaunchMode& m);
+int a3c_fc_fwd_launch(const float* A, const float* W, const float* bias, float* C, int64_t M, hipStream_t s,
+                      const LaunchMode& m, const float* Wrows = nullptr);
 // the play step's tail alone: W = FC (NIPS trunk / LSTM head rows) or NT_FC (nature trunk)
 int a3c_head_screen_play_launch(int W, const float* h, const float* Wp, const float* bp, const float* Wv,
                                 const float* bv, int A, int zs, int64_t B, float* z, const HeadSelect& sel,

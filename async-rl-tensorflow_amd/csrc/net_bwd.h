@@ -92,14 +92,29 @@ struct LstmBwd {
 };
 
 BwdPlan a3c_bwd_plan(const NetLayout& L, int64_t B, bool wks = false);
-int a3c_backward_launch(const NetLayout& L, const float* params, const StateAddr& sa, int64_t B,
-                        const float* act_l1, const float* act_l2, const float* act_l3,
-                        const float* z, const int32_t* actions, const float* target, float beta,
-                        int literal, float* grads, float* loss_out, float* ws, hipStream_t s,
-                        const LaunchMode& m, const ReturnsArgs* ra = nullptr,
-                        hipStream_t side = nullptr, hipEvent_t ev_fork = nullptr, hipEvent_t ev_join = nullptr,
-                        const LstmBwd* lb = nullptr, const SumsqFused* sf = nullptr,
-                        const SplitBwd* sp = nullptr, const uint32_t* l2m = nullptr);
+// What a loss + backward over B samples takes, on either trunk (a host-side bundle: no kernel sees
+// it).  BwdArgs a = {} asks for no optional feature.  a3c_backward_launch dispatches on L.trunk: the
+// NIPS body (net_bwd.hip) or a3c_nat_backward_launch (nature.hip).
+struct BwdArgs {
+  const float* params;
+  StateAddr sa;
+  int64_t B;
+  const float *act_l1, *act_l2, *act_l3, *act_l4;   // l4: nature trunk only
+  const float *z, *target;
+  const int32_t* actions;
+  float beta;
+  int literal;
+  float *grads, *loss_out;   // every tensor's gradient in the layout's order; [4] the loss terms, summed
+  float* ws;                 // a3c_bwd_plan(L, B).total floats (nature: a3c_nat_bwd_ws_floats(L, B))
+  // optional (lb, sp, l2m: NIPS trunk)
+  const ReturnsArgs* ra;
+  const SumsqFused* sf;
+  const LstmBwd* lb;
+  const SplitBwd* sp;
+  const uint32_t* l2m;       // act_l2's ReLU bits (the dl2 epilogue reads them instead of l2)
+  const uint16_t* nat_wt;    // nature: the prepared weight terms of params (null: prepared into ws first)
+};
+int a3c_backward_launch(const NetLayout& L, const BwdArgs& a, hipStream_t s, const LaunchMode& m);
 int a3c_returns_launch(const float* rewards, const uint8_t* terms, const float* boot, int64_t boot_stride,
                        int n, int64_t E, double gamma, float* R, hipStream_t s);
 int a3c_gae_launch(const float* rewards, const uint8_t* terms, const float* values, int64_t vstride,
@@ -131,6 +146,7 @@ int a3c_sarsa_target_launch(const float* rewards, const uint8_t* terms, const in
                             const float* qt, int nstep, int n, int64_t E, int A, int zs, double discount,
                             float* target, hipStream_t s, const BootDraw* draw = nullptr);
 int a3c_select_launch(const float* z, int64_t B, int zs, int A, const HeadSelect& sel, hipStream_t s);
+void a3c_init_once();   // (capi.hip: the two below, once per process)
 void a3c_conv12_set_smem();
 void a3c_conv_bwd_set_smem();
 int a3c_head_screen_fold_launch(const float* part, int nsplit, const float* fbias, float* l4, const float* Wp,

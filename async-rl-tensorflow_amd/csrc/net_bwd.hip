@@ -24,9 +24,7 @@
 #include "gemm.h"
 #include "net_bwd.h"
 #include "net_head.h"
-#ifdef A3C_MARKERS
-void a3c_mark(int id, hipStream_t s);
-#endif
+#include "nature.h"
 
 // ---------------------------------------------------------------------------------------
 __global__ void k_returns(const float* __restrict__ rewards, const uint8_t* __restrict__ terms,
@@ -1137,14 +1135,16 @@ static bool dwfc_late_knob(const LaunchMode& m) {
 }
 static bool bwd_bound_knob(const LaunchMode& m) { return m.bwd_bound; }
 
-int a3c_backward_launch(const NetLayout& L, const float* params, const StateAddr& sa, int64_t B,
-                        const float* act_l1, const float* act_l2, const float* act_l3,
-                        const float* z, const int32_t* actions, const float* target, float beta,
-                        int literal, float* grads, float* loss_out, float* ws, hipStream_t s,
-                        const LaunchMode& m, const ReturnsArgs* ra_in, hipStream_t side, hipEvent_t ev_fork, hipEvent_t ev_join,
-                        const LstmBwd* lb, const SumsqFused* sf, const SplitBwd* sp, const uint32_t* l2m) {
+int a3c_backward_launch(const NetLayout& L, const BwdArgs& a, hipStream_t s, const LaunchMode& m) {
+  if (L.trunk == A3C_TRUNK_NATURE) return a3c_nat_backward_launch(L, a, s);
+  const float* P = a.params;
+  const int64_t B = a.B;
+  const float *act_l1 = a.act_l1, *act_l2 = a.act_l2, *act_l3 = a.act_l3;
+  float *grads = a.grads, *ws = a.ws;
+  const LstmBwd* lb = a.lb;
+  const SumsqFused* sf = a.sf;
   ReturnsArgs ra = {};
-  if (ra_in) ra = *ra_in;
+  if (a.ra) ra = *a.ra;
   if (B <= 0) return a3c_set_error(A3C_ERR_INVALID, "a3c_loss_backward", "B must be > 0");
   // sync mode: the three GEMMs in one launch (3.32M -> 3.41M env-steps/s), and so where the
   // overlapped backward bounds the iteration (M2: 5.17-5.22M -> 5.38-5.39M); beside a rollout
@@ -1159,7 +1159,6 @@ int a3c_backward_launch(const NetLayout& L, const float* params, const StateAddr
   // (test_gpu_multirank.py::test_split_exchange_equals_one_phase)
   const bool wks = fc_wks_on(B) && !L.lstm && !multi0;
   const BwdPlan p = a3c_bwd_plan(L, B, wks);
-  const float* P = params;
   float* dz = ws + p.dz;
   float* dh3 = ws + p.dh3;
   float* dl2 = ws + p.dl2;
@@ -1170,8 +1169,9 @@ int a3c_backward_launch(const NetLayout& L, const float* params, const StateAddr
     return a3c_set_error(A3C_ERR_INVALID, "a3c_loss_backward", "the LSTM head needs its rollout sequence");
   // head input: the fc ReLU output, or the LSTM's h (C5)
   const float* head_in = lb ? lb->h : act_l3;
-  int rch = a3c_head_bwd_launch(FC, L, z, actions, target, head_in, P + L.off[T_HW], a3c ? P + L.off[T_VW] : nullptr,
-                                beta, literal, B, dz, lb ? lb->dh : dh3, terms, ra, lb ? 0 : 1, s);
+  int rch = a3c_head_bwd_launch(FC, L, a.z, a.actions, a.target, head_in, P + L.off[T_HW],
+                                a3c ? P + L.off[T_VW] : nullptr, a.beta, a.literal, B, dz, lb ? lb->dh : dh3, terms, ra,
+                                lb ? 0 : 1, s);
   if (rch) return rch;
   if (lb) {
     // truncated BPTT: dL/dh_t -> dl3 (masked by the fc ReLU) + the gate-matrix gradients
@@ -1181,15 +1181,6 @@ int a3c_backward_launch(const NetLayout& L, const float* params, const StateAddr
     if (rc0) return rc0;
   }
 
-  // The weight-gradient GEMMs (head, fc) only need dz / dl3 from k_head_bwd: with a side stream
-  // they run concurrently with the dl2 GEMM + conv backward (graph branches), joined before the
-  // slab reductions.
-  const bool fork = side && ev_fork && ev_join && !lb;
-  hipStream_t ws_s = fork ? side : s;
-  if (fork) {
-    A3C_CHECK(hipEventRecord(ev_fork, s));
-    A3C_CHECK(hipStreamWaitEvent(side, ev_fork, 0));
-  }
   // head weights: dWh[256][zs] = l3^T dz ; dbh = colsum(dz)
   GemmArgs gh = {};
   gh.A = head_in; gh.lda = FC;       // A(m=feature, k=b) = l3[b][m]  (m contiguous)
@@ -1222,8 +1213,8 @@ int a3c_backward_launch(const NetLayout& L, const float* params, const StateAddr
   gd.C = dl2; gd.ldc = FLAT;
   gd.M = (int)B; gd.N = FLAT; gd.K = FC;
   gd.epi = EPI_MASK; gd.mask = act_l2; gd.ldm = FLAT; gd.nsplit = 1;
-  if (l2m) {   // the forward's ReLU bits (engine): 415 KB instead of re-reading l2's 13.3 MB (E=256)
-    gd.epi = EPI_MASKBITS; gd.maskbits = l2m; gd.mask = nullptr; gd.ldm = FLAT / 32;
+  if (a.l2m) {   // the forward's ReLU bits (engine): 415 KB instead of re-reading l2's 13.3 MB (E=256)
+    gd.epi = EPI_MASKBITS; gd.maskbits = a.l2m; gd.mask = nullptr; gd.ldm = FLAT / 32;
   }
   gd.xcd = xcd_gemm(m) ? 2 : 0;          // the 20 row tiles of a W strip on one XCD
   {
@@ -1241,9 +1232,9 @@ int a3c_backward_launch(const NetLayout& L, const float* params, const StateAddr
     if (m.shared_gpu) gh.max_wgs = gf.max_wgs = gd.max_wgs = env_wgs;
   }
   int rc;
-  if (sp) {
-    if (!sf || fork) return a3c_set_error(A3C_ERR_INVALID, "a3c_loss_backward", "split backward: fused norms, no fork");
-    return backward_split(L, P, sa, B, act_l1, ws, s, m, p, gh, gf, gd, grads, terms, loss_out, sf, sp);
+  if (a.sp) {
+    if (!sf) return a3c_set_error(A3C_ERR_INVALID, "a3c_loss_backward", "split backward: fused norms, no fork");
+    return backward_split(L, P, a.sa, B, act_l1, ws, s, m, p, gh, gf, gd, grads, terms, a.loss_out, sf, a.sp);
   }
   static const int env_late = (int)A3C_AB_KNOB("A3C_FOLD_LATE", -1);
   // The head weight GEMM folds its own split-K slabs (k_reduce_slabs behind it) instead of the
@@ -1254,7 +1245,7 @@ int a3c_backward_launch(const NetLayout& L, const float* params, const StateAddr
   bool hfold = false;
   const bool multi = multi0 && !wks;
   const bool late = env_late >= 0 ? env_late != 0 : multi;
-  if (!fork && (multi || late)) {
+  if (multi || late) {
     // the weight-gradient split-K folds go after the conv backward (only the clip / apply read
     // them), so nothing but dl2 stands between the head and the conv
     if (multi) {
@@ -1266,7 +1257,7 @@ int a3c_backward_launch(const NetLayout& L, const float* params, const StateAddr
       if (!rc) rc = a3c_gemm(true, false, gd, s);
     }
     if (rc) return rc;
-    rc = a3c_conv_bwd_launch(L, P, sa, B, act_l1, dl2, ws, s, m);
+    rc = a3c_conv_bwd_launch(L, P, a.sa, B, act_l1, dl2, ws, s, m);
     if (rc) return rc;
     rc = a3c_gemm_reduce(gf, s);       // (gh: folded by the finalize)
     if (rc) return rc;
@@ -1278,22 +1269,21 @@ int a3c_backward_launch(const NetLayout& L, const float* params, const StateAddr
 #endif
     // dwfc_late: the fc weight GEMM (+ its fold) behind the conv backward -- only dl2 stands
     // between the head and the conv
-    const bool dwfc_late = dwfc_late_knob(m) && !fork;
+    const bool dwfc_late = dwfc_late_knob(m);
     hfold = env_hfold && p.head_split > 1;
     if (hfold) gh.defer_reduce = 0;
-    rc = abl_gemm ? 0 : a3c_gemm(false, true, gh, ws_s);
+    rc = abl_gemm ? 0 : a3c_gemm(false, true, gh, s);
     if (rc) return rc;
     if (!dwfc_late) {
-      rc = abl_gemm ? 0 : a3c_gemm(false, true, gf, ws_s);
+      rc = abl_gemm ? 0 : a3c_gemm(false, true, gf, s);
       if (rc) return rc;
     }
-    if (fork) A3C_CHECK(hipEventRecord(ev_join, side));
     rc = abl_gemm ? 0 : a3c_gemm(true, false, gd, s);
     if (rc) return rc;
 #ifdef A3C_MARKERS
     a3c_mark(4, s);
 #endif
-    rc = a3c_conv_bwd_launch(L, P, sa, B, act_l1, dl2, ws, s, m);
+    rc = a3c_conv_bwd_launch(L, P, a.sa, B, act_l1, dl2, ws, s, m);
     if (rc) return rc;
 #ifdef A3C_MARKERS
     a3c_mark(5, s);
@@ -1313,7 +1303,6 @@ int a3c_backward_launch(const NetLayout& L, const float* params, const StateAddr
     q.col0 = col0; q.ncols = ncols; q.dst_off = L.off[tensor]; q.dst_ld = dst_ld; q.scale = scale;
     q.slot = sf ? sf->tt->pb_first[tensor] : -1;
   };
-  if (fork) A3C_CHECK(hipStreamWaitEvent(s, ev_join, 0));
   // conv slabs: nwg partials -> p.groups partials (pass 1), folded by k_finalize (pass 2)
   const int per = (p.nwg + p.groups - 1) / p.groups;
   hipLaunchKernelGGL(k_slab_group, dim3((CB_SLAB + 255) / 256, p.groups), dim3(256), 0, s, ws + p.cslab, p.nwg, per,
@@ -1351,7 +1340,7 @@ int a3c_backward_launch(const NetLayout& L, const float* params, const StateAddr
     nsumblk = fs.sum_c0[fs.nsum];
   }
   hipLaunchKernelGGL(k_finalize, dim3((unsigned)(FIN_X * fs.n + 1 + nsumblk)), dim3(256), 0, s, fs, terms, B,
-                     loss_out);
+                     a.loss_out);
   A3C_CHECK(hipGetLastError());
   return 0;
 }

@@ -19,6 +19,7 @@
 #include "env_dev.h"
 #include "screen_atari.h"
 #include "net_head.h"
+#include "nature.h"
 
 #define XB_BYTES (HIST * PLANE * 2)                  // 56448: state planes as bf16
 #ifdef C2_FP32
@@ -840,11 +841,6 @@ __global__ void __launch_bounds__(256) k_select(const float* __restrict__ z, int
   if (lane == 0) sel.actions[b] = a;
 }
 
-int a3c_fc_fwd_launch(const float* A, const float* W, const float* bias, float* C, int64_t M, hipStream_t s,
-                      const LaunchMode& m, const float* Wrows = nullptr);
-
-// skip_conv12: conv1 + conv2 of these states already ran (fused into the previous step's
-// k_head_screen_conv12); next: fuse the next states' conv1 + conv2 into this step's head + screen
 // the nature trunk's rollout step tail with the fc's split-K fold in front: the workgroup folds
 // env b's row of the nsplit K-slice partials (slice order, + bias, ReLU: k_reduce_slabs' order, so
 // the row is bit-identical to the separate fold), keeps it in LDS for the head and writes it out for
@@ -951,20 +947,22 @@ int a3c_head_screen_play_launch(int W, const float* h, const float* Wp, const fl
   return 0;
 }
 
-int a3c_head_screen_conv12_launch(const NetLayout& L, const float* P, const float* act_l3, int64_t B, float* z,
-                                  const HeadSelect& sel, const Conv12Next& nx, hipStream_t s);
-int a3c_forward_launch(const NetLayout& L, const float* params, const uint8_t* prep, const StateAddr& sa,
-                       int64_t B, float* act_l1, float* act_l2, float* act_l3, float* z, const HeadSelect& sel,
-                       hipStream_t s, const LaunchMode& m, const LstmStep* ls, bool skip_conv12,
-                       const Conv12Next* next, float* fc_part, uint32_t* l2m, const uint8_t* play_frozen) {
+int a3c_forward_launch(const NetLayout& L, const FwdArgs& a, hipStream_t s, const LaunchMode& m) {
+  if (L.trunk == A3C_TRUNK_NATURE) return a3c_nat_forward_launch(L, a, s, m);
+  const float* P = a.params;
+  const uint8_t *prep = a.prep, *play_frozen = a.play_frozen;
+  const int64_t B = a.B;
+  float *act_l2 = a.act_l2, *act_l3 = a.act_l3, *z = a.z, *fc_part = a.fc_part;
+  const HeadSelect& sel = *a.sel;
+  const LstmStep* ls = a.ls;
+  const Conv12Next* next = a.next;
   if (B <= 0) return 0;
-  if (play_frozen && (next || fc_part || skip_conv12 || sel.mode < 0 || !sel.env_on || !sel.ring))
+  if (play_frozen && (next || fc_part || a.skip_conv12 || sel.mode < 0 || !sel.env_on || !sel.ring))
     return a3c_set_error(A3C_ERR_INVALID, "a3c_forward", "the play step runs unfused, with the device env and the fused screen");
   if (L.lstm != (ls != nullptr))
     return a3c_set_error(A3C_ERR_INVALID, "a3c_forward", "the LSTM head needs its recurrent state");
-  const float* P = params;
-  if (!skip_conv12) {
-    int rc0 = a3c_conv12_launch(L, P, prep, sa, B, act_l1, act_l2, s, m, l2m);
+  if (!a.skip_conv12) {
+    int rc0 = a3c_conv12_launch(L, P, prep, a.sa, B, a.act_l1, act_l2, s, m, a.l2m);
     if (rc0) return rc0;
   }
   // fused overlap rollout: the fc as K-slice partials, folded by the head of k_head_screen_conv12

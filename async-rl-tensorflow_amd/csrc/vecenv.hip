@@ -6,11 +6,6 @@
 #include <new>
 #include "env_dev.h"
 
-int a3c_pool_fill_launch(uint8_t* pool, int P, uint32_t k0, uint32_t k1, hipStream_t s, int frame_bytes);
-int a3c_pool_render_catch_launch(uint8_t* pool, int P, int visible_rows, hipStream_t s);
-int a3c_launch_screen_atari(const uint8_t* rgb, const int32_t* idx, int64_t n, uint8_t* out, int64_t stride,
-                            hipStream_t s);
-
 struct a3c_env {
   EnvParams p;
   EnvBufs b;      // single-buffered: these kernels update state in place, one thread per env
