@@ -13,6 +13,8 @@ torch = pytest.importorskip('torch')
 
 from oracle import ref_cpu as Rc  # noqa: E402
 from oracle.engine_ref import EngineRef  # noqa: E402
+import _plan as PL  # noqa: E402
+from _net_parity import GUARD  # noqa: E402
 from _engine_parity import (REF_KEYS, EpisodeCount, assert_draws_explained, assert_env_state,  # noqa: E402
                             assert_independent_grads, assert_saved_acts, report_independent)
 
@@ -61,29 +63,111 @@ def test_lstm_step_matches_oracle(B):
     np.testing.assert_allclose(out2['h'].cpu().numpy(), hr2, rtol=1e-5, atol=5e-6)
 
 
-@pytest.mark.parametrize('n,E', [(5, 37), (1, 16), (5, 256)])
-def test_lstm_bptt_matches_oracle(n, E):
-    from src import kernels as K
+def _guarded(rows, cols):
+    """[rows + 1, cols] filled with GUARD: the kernel owns rows 0..rows-1, the last row shows a write
+    one row past the end."""
+    return torch.full((rows + 1, cols), GUARD, dtype=torch.float32, device='cuda')
+
+
+def _guard_intact(t):
+    return bool((t[-1] == GUARD).all())
+
+
+@pytest.mark.parametrize('B', [15, 17])
+def test_lstm_step_env_tile_edges_guarded(B):
+    """a3c_lstm_step one env short of k_lstm_fwd's 16-env tile and one over (a second, one-env
+    tile), called through the C entry on caller buffers: every output has a row of sentinels behind
+    row B - 1, which a store of the tile's unused rows would overwrite."""
+    from src import _lib
+    assert (B + 1) % PL.LSTM_TILE == 0 or (B - 1) % PL.LSTM_TILE == 0
+    rng = np.random.default_rng(B)
+    w, b = _lstm_params(B)
+    x = np.maximum(rng.standard_normal((B, 256)), 0).astype(np.float32)
+    h = (rng.standard_normal((B, U)) * 0.5).astype(np.float32)
+    c = (rng.standard_normal((B, U)) * 0.5).astype(np.float32)
+    terms = (rng.random(B) < 0.3).astype(np.uint8)
+    dev = lambda a: torch.as_tensor(a).cuda()  # noqa: E731
+    wd, bd, xd, hd, cd, td = dev(w), dev(b), dev(x), dev(h), dev(c), dev(terms)
+    w_t = torch.empty((1024, 512), dtype=torch.float32, device='cuda')
+    out = dict(hp=_guarded(B, U), cp=_guarded(B, U), gates=_guarded(B, 4 * U), h=_guarded(B, U), c=_guarded(B, U))
+    ptr, L = _lib.ptr, _lib.lib()
+    _lib.check(L.a3c_lstm_transpose(ptr(wd), ptr(w_t), _lib.stream_handle()), 'a3c_lstm_transpose')
+    _lib.check(L.a3c_lstm_step(ptr(w_t), ptr(bd), ptr(xd), ptr(hd), ptr(cd), ptr(td), B, ptr(out['hp']), ptr(out['cp']),
+                               ptr(out['gates']), ptr(out['h']), ptr(out['c']), _lib.stream_handle()), 'a3c_lstm_step')
+    torch.cuda.synchronize()
+    for k, v in out.items():
+        assert _guard_intact(v), k
+    keep = (1 - terms.astype(np.float64))[:, None]
+    hr, cr, gr = Rc.lstm_cell(x.astype(np.float64), h * keep, c * keep, w.astype(np.float64), b.astype(np.float64))
+    got = {k: v[:B].cpu().numpy() for k, v in out.items()}
+    np.testing.assert_allclose(got['h'], hr, rtol=1e-5, atol=5e-6)
+    np.testing.assert_allclose(got['c'], cr, rtol=1e-5, atol=5e-6)
+    np.testing.assert_allclose(got['gates'], gr, rtol=1e-5, atol=5e-6)
+    assert np.array_equal(got['hp'], (h * keep).astype(np.float32))
+    assert np.array_equal(got['cp'], (c * keep).astype(np.float32))
+
+
+def _bptt_case(n, E):
+    """Inputs of a BPTT over [n, E] (the oracle's own fp64 forward, rounded to float32) and the
+    oracle's backward on them: (device-ready arrays, (dX masked by x > 0, dW, dB))."""
     rng = np.random.default_rng(100 + E)
     w, b = _lstm_params(E)
-    P = {'lstm_w': w, 'lstm_b': b}
+    prm = {'lstm_w': w, 'lstm_b': b}
     x = np.maximum(rng.standard_normal((n, E, 256)) - 0.3, 0).astype(np.float32)
     terms = (rng.random((n, E)) < 0.2).astype(np.uint8)
     h0 = (rng.standard_normal((E, U)) * 0.3).astype(np.float32)
     c0 = (rng.standard_normal((E, U)) * 0.3).astype(np.float32)
-    seq = Rc.lstm_forward_seq(P, x.astype(np.float64), h0.astype(np.float64), c0.astype(np.float64), terms)
+    seq = Rc.lstm_forward_seq(prm, x.astype(np.float64), h0.astype(np.float64), c0.astype(np.float64), terms)
     seq32 = {k: seq[k].astype(np.float32) for k in ('HP', 'CP', 'G', 'C')}
     dH = rng.standard_normal((n, E, U)).astype(np.float32)
-    dev = lambda a: torch.as_tensor(np.ascontiguousarray(a)).cuda()  # noqa: E731
-    dx, dw, db = K.lstm_bptt(dev(w), dev(x), dev(seq32['HP']), dev(seq32['CP']), dev(seq32['G']), dev(seq32['C']),
-                             dev(terms), dev(dH))
-    torch.cuda.synchronize()
     s64 = {k: v.astype(np.float64) for k, v in seq32.items()}
-    dX, dW, dB = Rc.lstm_backward_seq(P, s64, x.astype(np.float64), dH.astype(np.float64), terms)
-    dX = dX * (x > 0)
+    dX, dW, dB = Rc.lstm_backward_seq(prm, s64, x.astype(np.float64), dH.astype(np.float64), terms)
+    return (w, x, seq32['HP'], seq32['CP'], seq32['G'], seq32['C'], terms, dH), (dX * (x > 0), dW, dB)
+
+
+@pytest.mark.parametrize('n,E', [(5, 37), (1, 16), (5, 256)])
+def test_lstm_bptt_matches_oracle(n, E):
+    from src import kernels as K
+    args, (dX, dW, dB) = _bptt_case(n, E)
+    dev = lambda a: torch.as_tensor(np.ascontiguousarray(a)).cuda()  # noqa: E731
+    dx, dw, db = K.lstm_bptt(*[dev(a) for a in args])
+    torch.cuda.synchronize()
     assert rel_l2(dx.cpu().numpy(), dX) < 1e-5
     assert rel_l2(dw.cpu().numpy(), dW) < 1e-5
     assert rel_l2(db.cpu().numpy(), dB) < 1e-5
+
+
+# measured rel-L2 of dx / dw / db, then the largest per-gate one of dw and db:
+#   (2, 17)   2.1e-07 / 9.6e-08 / 1.1e-07, per gate 1.2e-07
+#   (3, 87)   2.2e-07 / 1.3e-07 / 1.5e-07, per gate 1.9e-07
+@pytest.mark.parametrize('n,E', [(2, 17), (3, 87)])
+def test_lstm_bptt_short_sequences_guarded_per_gate(n, E):
+    """a3c_lstm_bptt through the C entry on caller buffers with a row of sentinels behind dx, dw and
+    db.  n = 2 is one fused step (d[x, hp]_1 GEMM + dx_1 + cell backward of step 0) plus dx_0, with
+    E = 17 one env over the 16-env tile of k_lstm_bptt_step and a 3-way split of the dW GEMM over 3
+    k-tiles; (3, 87) a ragged tile (87 = 5 * 16 + 7) and the 4-way split over 17 k-tiles.  Beside the
+    whole-tensor bound, dW and db are held to it per gate (four blocks of 256 columns: i, j, f, o),
+    so an error confined to one gate is not diluted fourfold."""
+    from src import _lib
+    ws_plan = PL.lstm_ws(n, E)
+    assert E % PL.LSTM_TILE and (ws_plan.split_dw, PL.cdiv(n * E, PL.BK)) == {(2, 17): (3, 3), (3, 87): (4, 17)}[(n, E)]
+    args, (dX, dW, dB) = _bptt_case(n, E)
+    dev = lambda a: torch.as_tensor(np.ascontiguousarray(a)).cuda()  # noqa: E731
+    w, x, hp, cp, gates, c, terms, dh = [dev(a) for a in args]
+    dx, dw, db = _guarded(n * E, 256), _guarded(512, 1024), _guarded(1, 1024)
+    ws = torch.empty(PL.lstm_workspace_bytes(n, E), dtype=torch.uint8, device='cuda')
+    ptr = _lib.ptr
+    _lib.check(_lib.lib().a3c_lstm_bptt(ptr(w), n, E, ptr(x), ptr(hp), ptr(cp), ptr(gates), ptr(c), ptr(terms), ptr(dh),
+                                        ptr(dx), ptr(dw), ptr(db), ptr(ws), _lib.stream_handle()), 'a3c_lstm_bptt')
+    torch.cuda.synchronize()
+    assert _guard_intact(dx) and _guard_intact(dw) and _guard_intact(db)
+    dx, dw, db = dx[:-1].cpu().numpy().reshape(n, E, 256), dw[:-1].cpu().numpy(), db[0].cpu().numpy()
+    errs = [rel_l2(dx, dX), rel_l2(dw, dW), rel_l2(db, dB)]
+    gate = [rel_l2(dw[:, g * U:(g + 1) * U], dW[:, g * U:(g + 1) * U]) for g in range(4)]
+    gate += [rel_l2(db[g * U:(g + 1) * U], dB[g * U:(g + 1) * U]) for g in range(4)]
+    print(f'lstm bptt n={n} E={E}: dx {errs[0]:.1e} dw {errs[1]:.1e} db {errs[2]:.1e} per gate max {max(gate):.1e}')
+    assert max(errs) < 1e-5, errs
+    assert max(gate) < 1e-5, gate
 
 
 # ------------------------------------------------------------------ engine (C5)
