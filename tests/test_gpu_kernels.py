@@ -89,6 +89,65 @@ def test_preprocess_gather_stride_and_unaligned(K):
     assert np.array_equal(out, R.resize_bilinear_u8(R.luminance_u8(fr), 5, 9))
 
 
+def _at_offset(arr, off):
+    """arr's bytes on the device `off` bytes behind a fresh allocation's start (itself 256-aligned)."""
+    flat = np.ascontiguousarray(arr).reshape(-1)
+    buf = torch.zeros(off + flat.size, dtype=torch.uint8, device='cuda')
+    assert buf.data_ptr() % 16 == 0
+    buf[off:] = cu(flat)
+    return buf[off:].view(arr.shape)
+
+
+@pytest.mark.parametrize('off', [0, 1, 8])
+def test_preprocess_painted_frames(K, off):
+    """The 48 painted frames (tests/_painted.py: the reference's goldens, then saturated, flat and
+    hard-edged frames) through the standalone entry point.  A 16-byte-aligned source takes k_screen_atari
+    (atari::screen_band); a source 1 or 8 bytes off takes k_preprocess (a3c_preprocess_part) at the Atari
+    geometry, with its scalar staging loop."""
+    import _painted as P
+    src = _at_offset(P.painted_frames(), off)
+    assert src.data_ptr() % 16 == off
+    out = K.preprocess(src).cpu().numpy()
+    bad = [f for f in range(P.N_FRAMES) if not np.array_equal(out[f], P.painted_screens()[f])]
+    assert not bad, (off, bad)
+
+
+@pytest.mark.parametrize('off', [0, 1])
+def test_luminance_flat_greys(K, off):
+    """R = G = B frames: every group of four pixels takes lum4's multiple-of-10^4 branch (aligned), every
+    pixel the scalar lum_exact (1 byte off).  Greys 1, 236 and 254 of the painted set."""
+    import _painted as P
+    fr = P.painted_frames()[[P.GREYS[v] for v in (1, 236, 254)]]
+    out = K.luminance(_at_offset(fr, off)).cpu().numpy()
+    assert np.array_equal(out, np.stack([R.luminance_u8(f) for f in fr]))
+    assert [int(o[0, 0]) for o in out] == [1, 235, 254] and all((o == o[0, 0]).all() for o in out)
+
+
+@pytest.mark.parametrize('gather', [False, True], ids=['frames', 'frame_idx'])
+def test_preprocess_more_frames_than_one_grid(K, gather):
+    """n = 65537 frames of 4x4 -> 2x2: a3c_launch_preprocess splits n > 65535 (the grid's y limit) into
+    chunks, advancing the source (or frame_idx) and the output per chunk.  Frame i is pool frame i % 7;
+    every output against the oracle's seven screens -- frames 0, 65534, 65535 (the second chunk's
+    first) and 65536 among them -- and the guard row behind the output intact."""
+    n = 65537
+    rng = np.random.default_rng(11)
+    pool = rng.integers(0, 256, (7, 4, 4, 3), dtype=np.uint8)
+    want = np.stack([R.resize_bilinear_u8(R.luminance_u8(f), 2, 2) for f in pool])
+    assert len({w.tobytes() for w in want}) == 7
+    idx = (np.arange(n) % 7).astype(np.int32)
+    buf = torch.full((n + 1, 2, 2), 0xA5, dtype=torch.uint8, device='cuda')
+    if gather:
+        out = K.preprocess(cu(pool), frame_idx=cu(idx), out_hw=(2, 2), out=buf[:n])
+    else:
+        out = K.preprocess(cu(pool[idx]), out_hw=(2, 2), out=buf[:n])
+    got = buf.cpu().numpy()
+    assert out.data_ptr() == buf.data_ptr()
+    for i in (0, 65534, 65535, 65536):
+        assert np.array_equal(got[i], want[i % 7]), (i, got[i], want[i % 7])
+    assert np.array_equal(got[:n], want[idx])
+    assert (got[n] == 0xA5).all()
+
+
 # ---------------------------------------------------------------------------------- K2
 def test_history_push_get(K, screen_golden, golden_dir):
     hg = np.load(os.path.join(golden_dir, 'history_golden.npz'))

@@ -7,7 +7,7 @@ reference's goldens) on random and extreme images -- the exactness argument, on 
 over 16x16 output tiles whose K = 64 source window starts at a 16-aligned offset, with the
 source rows / columns past the image edge and the pad outputs as the kernel has them.
 The GPU kernels themselves are checked bit for bit through the engine's frame ring
-(tests/test_gpu_engine.py, tests/_engine_parity.py)."""
+(tests/test_gpu_engine.py, tests/_engine_parity.py; on golden and saturated frames: tests/test_gpu_painted.py)."""
 import numpy as np
 import pytest
 
