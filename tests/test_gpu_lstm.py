@@ -171,14 +171,15 @@ def test_lstm_bptt_short_sequences_guarded_per_gate(n, E):
 
 
 # ------------------------------------------------------------------ engine (C5)
-def build(A, E, n, lives, seed, frames=48, scale=4.0, **kw):
+def build(A, E, n, lives, seed, frames=48, scale=4.0, params=None, **kw):
+    """(params(names_shapes) -> {name: array}: the initial parameters, in place of the usual init.)"""
     from src.engine import Engine
     from src.initializers import init_params, flatten_host
     from src.kernels import param_names_shapes
     eng = Engine(num_envs=E, n_step=n, action_size=A, algo='a3c', start_lives=lives, num_frames=frames, seed=seed,
                  lstm=True, **kw)
     ns = param_names_shapes(A, 'a3c', lstm=True)
-    p = init_params(ns, seed=seed, stddev=0.02 * scale)
+    p = init_params(ns, seed=seed, stddev=0.02 * scale) if params is None else params(ns)
     eng.reset(flatten_host(ns, eng.offsets, eng.params.numel(), p))
     ref = EngineRef(p, E, n, A, 'a3c', lives, frames, seed, lstm=True,
                     **{k: v for k, v in kw.items() if k in REF_KEYS and k not in NOT_LSTM})
