@@ -175,6 +175,23 @@ extern "C" int a3c_sarsa_target(const float* rewards, const uint8_t* terminals, 
                                  target, (hipStream_t)stream);
 }
 
+extern "C" int a3c_lambda_q_target(const float* rewards, const uint8_t* terminals, const int32_t* actions,
+                                   const int32_t* boot_actions, const float* q_target, const float* q_sel, int n,
+                                   int64_t E, int A, int zs, double discount, double lambda, float* target,
+                                   void* stream) {
+  if (!rewards || !terminals || !q_target || !target || n < 1 || E < 1 || A < 1 || zs < A)
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_lambda_q_target", "bad argument");
+  if (!actions != !boot_actions)
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_lambda_q_target", "actions and boot_actions: both (Sarsa) or neither");
+  if (actions && q_sel)
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_lambda_q_target",
+                         "q_sel with actions: double Q picks the argmax, Sarsa the taken action");
+  if (!(lambda >= 0.0 && lambda <= 1.0))
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_lambda_q_target", "lambda must be in [0, 1]");
+  return a3c_lambda_q_target_launch(rewards, terminals, actions, boot_actions, q_target, q_sel, n, E, A, zs, discount,
+                                    lambda, target, (hipStream_t)stream);
+}
+
 extern "C" int a3c_loss_backward(const a3c_net_desc* net, const float* params, const uint8_t* states, int64_t B,
                                  const float* act_l1, const float* act_l2, const float* act_l3, const float* z,
                                  const int32_t* actions, const float* target, float beta, int literal_adv,

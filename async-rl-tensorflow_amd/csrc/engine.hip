@@ -104,6 +104,8 @@ struct a3c_engine {
   int frame84;             // cfg.frame84: pre-sized 84x84 pool frames (measurement mode M2)
   int game;                // A3C_GAME_*: the device envs' game (a3c_engine_create_ex)
   int sarsa;               // a3c_engine_opts.sarsa: Sarsa targets
+  int q_lambda_on;         // a3c_engine_set_q_lambda: lambda-return targets; 0: the one-step / n-step rules
+  double q_lambda;
   int fuse_conv;           // 1: step t+1's conv1 + conv2 fused into step t's head + screen
   unsigned long long* spans;  // [2][SPAN_RECS][2]: live launch spans of k_conv_bwd, k_head_screen_conv12
   Slot slot[2];
@@ -1053,7 +1055,16 @@ static int enqueue_grad(a3c_engine* e, const Slot& sl, hipStream_t s) {
     f.sa = ring_addr(e, c.q_nstep ? n : 1, sl.tau); f.B = c.q_nstep ? E : e->nE;
     rc = a3c_forward_launch(L, f, s, e->mode);
     if (rc) return rc;
-    if (e->sarsa) {
+    if (e->q_lambda_on) {
+      // lambda-returns (never with q_nstep): the one-step path's forwards stand, e->zt holds the
+      // target network's rows of s_1 .. s_n, and the lambda kernel takes the target kernel's place.  Sarsa: it
+      // draws a_n itself, as k_sarsa_target does, at the slot's tau + n from the slot's rows of s_n; double Q:
+      // the rollout's own rows t+1
+      const BootDraw bd = {head_select(e, 1, e->counters, 0), sl.tau, zboot, sl.boot_action};
+      rc = a3c_lambda_q_target_launch(sl.rewards, sl.terms, e->sarsa ? sl.actions : nullptr, nullptr, e->zt,
+                                      c.double_q ? sl.z + (int64_t)E * zs : nullptr, n, E, L.A, zs, c.discount,
+                                      e->q_lambda, sl.R_buf, s, e->sarsa ? &bd : nullptr);
+    } else if (e->sarsa) {
       // one kernel draws, from the slot's rows, the action the rollout's head would draw in s_n, at the
       // slot's tau + n (sl.tau holds tau alone: the schedule's base step comes from the counters, where
       // only a3c_engine_set_step writes it), and forms the targets at the taken actions -- as many
@@ -1277,6 +1288,28 @@ extern "C" int a3c_engine_set_first_screen(a3c_engine* e, int on) {
   A3C_CHECK(hipDeviceSynchronize());      // (the engine's streams: nothing in flight steps an env)
   e->envp.catch_visible = (int16_t)(catch_visible_rows(e->envp) | (on ? CATCH_FIRST_SCREEN_BIT : 0));
   drop_graphs(e);   // (they hold the other value in their kernel arguments)
+  return 0;
+}
+
+// q_lambda: which kernel forms the Q targets in enqueue_grad, and its lambda.  No reset: the
+// next gradient follows it.
+extern "C" int a3c_engine_set_q_lambda(a3c_engine* e, int on, double lambda) {
+  if (on != 0 && on != 1) return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_set_q_lambda", "on must be 0 or 1");
+  if (!(lambda >= 0.0 && lambda <= 1.0))
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_set_q_lambda", "lambda must be in [0, 1]");
+  if (!e) return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_set_q_lambda", "null");
+  if (e->L.algo != A3C_ALGO_Q)
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_set_q_lambda",
+                         "q_lambda is a Q-learning option (algo a3c has gae_lambda)");
+  if (e->cfg.q_nstep)
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_set_q_lambda",
+                         "q_lambda with q_nstep: the n-step engine is lambda = 1 with the target forward of s_n alone");
+  if (e->grad_ready && !e->grad_applied)
+    return a3c_set_error(A3C_ERR_STATE, "a3c_engine_set_q_lambda", "a gradient is pending: apply it first");
+  A3C_CHECK(hipDeviceSynchronize());      // (the engine's streams: nothing in flight forms targets)
+  e->q_lambda_on = on;
+  e->q_lambda = lambda;
+  drop_graphs(e);   // (they hold the other target kernel, or the other lambda in its arguments)
   return 0;
 }
 

@@ -145,6 +145,13 @@ struct BootDraw {
 int a3c_sarsa_target_launch(const float* rewards, const uint8_t* terms, const int32_t* actions, const int32_t* boot,
                             const float* qt, int nstep, int n, int64_t E, int A, int zs, double discount,
                             float* target, hipStream_t s, const BootDraw* draw = nullptr);
+// lambda-return Q targets: target [n][E] from qt [n*E][zs] of s_1..s_n; the bootstrap value of s_{i+1}
+// is the row's max, with qsel [n*E][zs] its value at qsel's row argmax (double Q), with actions and boot (both or
+// neither, never with qsel) its value at a' = actions[i+1][e], boot[e] behind the rollout (Sarsa).  draw != nullptr
+// (with actions): boot is not read -- the kernel draws a_n itself, as a3c_sarsa_target_launch's does
+int a3c_lambda_q_target_launch(const float* rewards, const uint8_t* terms, const int32_t* actions, const int32_t* boot,
+                               const float* qt, const float* qsel, int n, int64_t E, int A, int zs, double discount,
+                               double lambda, float* target, hipStream_t s, const BootDraw* draw = nullptr);
 int a3c_select_launch(const float* z, int64_t B, int zs, int A, const HeadSelect& sel, hipStream_t s);
 void a3c_init_once();   // (capi.hip: the two below, once per process)
 void a3c_conv12_set_smem();

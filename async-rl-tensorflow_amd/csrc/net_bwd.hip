@@ -8,6 +8,8 @@
 //  k_nstep_q_target  n-step Q-learning targets per env in float64 (at the end of the file).
 //  k_boot_action, k_sarsa_target  Sarsa: the bootstrap state's action draw and the targets at the taken
 //                actions in float64 (at the end of the file).
+//  k_lambda_q_target  lambda-return Q targets per env in float64: Q(lambda), double Q, Sarsa(lambda) (DESIGN
+//                §4m; at the end of the file).
 //  k_head_bwd    one wave per sample: softmax/log-softmax/entropy, network.py:81-94 losses
 //                (A11 fixes) or agent.py:310-314 MSE, dz, dl3 = (W_h dz) * (l3 > 0).
 //  fc layer      gemm.hip: dW = l2^T dl3 (+colsum -> db), dl2 = (dl3 W^T) * (l2 > 0),
@@ -1638,6 +1640,153 @@ int a3c_sarsa_target_launch(const float* rewards, const uint8_t* terms, const in
     if (nstep) SARSA_LAUNCH(true, false); else SARSA_LAUNCH(false, false);
   }
 #undef SARSA_LAUNCH
+  A3C_CHECK(hipGetLastError());
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------
+// lambda-return Q targets: Peng's Q(lambda), its double-Q form and Sarsa(lambda)
+// ---------------------------------------------------------------------------------------
+// One thread per env, the recursion over the rollout serial in registers.  qt [n*E][zs]: the target
+// network's rows of s_1 .. s_n, b = i*E + e.  B_i, the bootstrap value of s_{i+1}, by FORM: LQ_MAX max_a
+// qt[b][a]; LQ_DOUBLE qt[b] at the first argmax of qsel[b] (rows of the same states under the slot's own
+// parameters); LQ_SARSA qt[b][a'], a' = actions[i+1][e], behind the rollout a_n[e], a word reduced into
+// [0, A) as an unsigned value.  G = B_{n-1}; for i = n-1 .. 0:
+//   mix = (1 - lambda) B_i + lambda G;  terminal -> mix = 0;  G = r_i + discount mix;  target[i][e] = (float)G
+// lambda = 0: mix = B_i + 0 = B_i, k_td_target / k_sarsa_target's one-step value to the last bit (the sum
+// r + discount m in either operand order); lambda = 1: mix = 0 + G = G, k_nstep_q_target's recursion.
+// The B_i do not depend on G, and the kernel's time is its dependent loads (it sits on the backward stream,
+// the overlapped iteration's critical path): LQ_STEPS steps are taken at a time, their loads issued together
+// -- rewards, terminals, action words, then the rows column group by column group across the steps -- and
+// only then the serial arithmetic.  A step below 0 repeats step 0's loads (in bounds, no branch) and is not
+// stored.  VEC: the rows are 16-byte aligned and hold a multiple of four floats (zs % 4 == 0 >= A), so a row
+// is read four columns a load and the columns >= A of its last load, which lie inside the row, are masked
+// out; else column by column.  Either way a row's columns are visited in ascending order with k_td_target's
+// comparisons: the same maximum, the same first argmax.
+// DRAW (the engine's Sarsa): a_n[e] is drawn here, as k_sarsa_target<.., DRAW> does -- boot_draw at
+// *bd.tau0 + n from bd.q, written to bd.boot_action; else it is read from boot.
+enum { LQ_MAX = 0, LQ_DOUBLE = 1, LQ_SARSA = 2 };
+constexpr int LQ_STEPS = 8;
+
+template <int FORM>
+__device__ inline void lq_take(float& best, int& arg, float v, int j) {
+  if constexpr (FORM == LQ_MAX) {
+    best = fmaxf(best, v);
+  } else {
+    if (v > best) { best = v; arg = j; }
+  }
+}
+
+template <int FORM, bool VEC, bool DRAW>
+__global__ void __launch_bounds__(256) k_lambda_q_target(const float* __restrict__ rewards,
+                                                         const uint8_t* __restrict__ terms,
+                                                         const int32_t* __restrict__ actions,
+                                                         const int32_t* __restrict__ boot,
+                                                         const float* __restrict__ qt,
+                                                         const float* __restrict__ qsel, int n, int64_t E, int A,
+                                                         int zs, double discount, double lambda,
+                                                         float* __restrict__ target, BootDraw bd) {
+#pragma clang fp contract(off)
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= E) return;
+  uint32_t an = 0;
+  if constexpr (FORM == LQ_SARSA) {
+    if constexpr (DRAW) {
+      const int32_t a = boot_draw(bd.sel, *bd.tau0 + n, bd.q, zs, A, e);
+      bd.boot_action[e] = a;
+      an = (uint32_t)a;
+    } else {
+      an = (uint32_t)boot[e];
+    }
+  }
+  const double keep = 1.0 - lambda;
+  double g = 0.0;
+  for (int i1 = n; i1 > 0; i1 -= LQ_STEPS) {   // steps i1-1 .. max(i1-LQ_STEPS, 0), slot k is step i1-1-k
+    int64_t b[LQ_STEPS];
+    float bv[LQ_STEPS], rw[LQ_STEPS];
+    uint8_t tm[LQ_STEPS];
+#pragma unroll
+    for (int k = 0; k < LQ_STEPS; ++k) {
+      const int i = max(i1 - 1 - k, 0);
+      b[k] = i * E + e;
+      rw[k] = rewards[b[k]];
+      tm[k] = terms[b[k]];
+    }
+    if constexpr (FORM == LQ_SARSA) {
+      uint32_t w[LQ_STEPS];
+#pragma unroll
+      for (int k = 0; k < LQ_STEPS; ++k) {
+        const bool inside = max(i1 - 1 - k, 0) < n - 1;   // a' is the rollout's next action, not a_n
+        w[k] = (uint32_t)actions[inside ? b[k] + E : b[k]];
+        if (!inside) w[k] = an;
+      }
+#pragma unroll
+      for (int k = 0; k < LQ_STEPS; ++k) bv[k] = qt[b[k] * zs + w[k] % (uint32_t)A];
+    } else {
+      const float* __restrict__ sel = FORM == LQ_DOUBLE ? qsel : qt;
+      int arg[LQ_STEPS];
+#pragma unroll
+      for (int k = 0; k < LQ_STEPS; ++k) {
+        bv[k] = sel[b[k] * zs];
+        arg[k] = 0;
+      }
+      if constexpr (VEC) {
+        for (int j = 0; j < A; j += 4) {
+          float4 v[LQ_STEPS];
+#pragma unroll
+          for (int k = 0; k < LQ_STEPS; ++k) v[k] = *reinterpret_cast<const float4*>(sel + b[k] * zs + j);
+#pragma unroll
+          for (int k = 0; k < LQ_STEPS; ++k) {
+            lq_take<FORM>(bv[k], arg[k], v[k].x, j);
+            if (j + 1 < A) lq_take<FORM>(bv[k], arg[k], v[k].y, j + 1);
+            if (j + 2 < A) lq_take<FORM>(bv[k], arg[k], v[k].z, j + 2);
+            if (j + 3 < A) lq_take<FORM>(bv[k], arg[k], v[k].w, j + 3);
+          }
+        }
+      } else {
+        for (int j = 1; j < A; ++j) {
+          float v[LQ_STEPS];
+#pragma unroll
+          for (int k = 0; k < LQ_STEPS; ++k) v[k] = sel[b[k] * zs + j];
+#pragma unroll
+          for (int k = 0; k < LQ_STEPS; ++k) lq_take<FORM>(bv[k], arg[k], v[k], j);
+        }
+      }
+      if constexpr (FORM == LQ_DOUBLE) {
+#pragma unroll
+        for (int k = 0; k < LQ_STEPS; ++k) bv[k] = qt[b[k] * zs + arg[k]];
+      }
+    }
+    if (i1 == n) g = (double)bv[0];
+#pragma unroll
+    for (int k = 0; k < LQ_STEPS; ++k) {
+      if (i1 - 1 - k < 0) continue;
+      double mix = keep * (double)bv[k] + lambda * g;
+      if (tm[k]) mix = 0.0;
+      g = (double)rw[k] + discount * mix;
+      target[b[k]] = (float)g;
+    }
+  }
+}
+
+int a3c_lambda_q_target_launch(const float* rewards, const uint8_t* terms, const int32_t* actions, const int32_t* boot,
+                               const float* qt, const float* qsel, int n, int64_t E, int A, int zs, double discount,
+                               double lambda, float* target, hipStream_t s, const BootDraw* draw) {
+  if (E <= 0) return 0;
+  const dim3 grid((unsigned)((E + 255) / 256));
+  const bool vec = (zs & 3) == 0 && (((uintptr_t)qt | (uintptr_t)qsel) & 15) == 0;
+  const BootDraw bd = draw ? *draw : BootDraw{};
+#define LQ_LAUNCH(FORM, VEC, DRAW)                                                                            \
+  hipLaunchKernelGGL((k_lambda_q_target<FORM, VEC, DRAW>), grid, dim3(256), 0, s, rewards, terms, actions, boot, qt, \
+                     qsel, n, E, A, zs, discount, lambda, target, bd)
+  if (actions) {
+    if (draw) LQ_LAUNCH(LQ_SARSA, false, true); else LQ_LAUNCH(LQ_SARSA, false, false);
+  } else if (qsel) {
+    if (vec) LQ_LAUNCH(LQ_DOUBLE, true, false); else LQ_LAUNCH(LQ_DOUBLE, false, false);
+  } else {
+    if (vec) LQ_LAUNCH(LQ_MAX, true, false); else LQ_LAUNCH(LQ_MAX, false, false);
+  }
+#undef LQ_LAUNCH
   A3C_CHECK(hipGetLastError());
   return 0;
 }

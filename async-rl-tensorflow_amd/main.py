@@ -11,6 +11,8 @@ accepted but the TF ps/worker cluster is replaced by one process per GPU under t
   python main.py --mode engine --env_name Catch-v0 --iterations 1000   the learnable device game
   python main.py --mode engine --algo q --q_nstep true --n_step 5 --env_name Catch-v0   n-step Q-learning
   python main.py --mode engine --algo q --sarsa true --n_step 5 --env_name Catch-v0     Sarsa (--q_nstep true: n-step)
+  python main.py --mode engine --algo q --q_lambda 0.8 --n_step 5 --env_name Catch-v0    lambda-return targets: Q(lambda), with
+                 --sarsa true Sarsa(lambda), with --double_q true its double-Q form
   python main.py --mode engine --algo q --optimizer adam --env_name Catch-v0             shared Adam instead of RMSProp
   python main.py --mode engine --lstm true --env_name CatchMemory-v0   Catch that only a head with memory learns
   python main.py --mode engine --lstm true --env_name CatchMemory-v0 --first_screen true   ... with each episode's first
@@ -82,6 +84,10 @@ def parse_flags(argv=None):
                  help='engine mode, q: asynchronous Sarsa -- the target takes the target network at the action the '
                       'behaviour policy takes in the next state, not at the maximum; with --q_nstep true n-step Sarsa '
                       '(DESIGN §4i)')
+  p.add_argument('--q_lambda', type=float, default=None,
+                 help='engine mode, q: lambda-return targets over the rollout (Q(lambda); with --sarsa Sarsa(lambda), '
+                      'with --double_q its double-Q form) -- 0 is the one-step target, 1 the n-step return of '
+                      '--q_nstep true; unset: the one-step / n-step rules as they are (DESIGN §4m)')
   p.add_argument('--num_envs', type=int, default=256)
   p.add_argument('--num_frames', type=int, default=16384)
   p.add_argument('--iterations', type=int, default=1000)
@@ -153,6 +159,16 @@ def engine_options(flags):
     raise ValueError('--sarsa is a Q-learning option (its target is a Q value, DESIGN §4i): use it with --algo q')
   if flags.sarsa and flags.double_q:
     raise ValueError('--sarsa with --double_q: double Q picks the argmax, Sarsa the taken action (DESIGN §4i)')
+  q_lambda = getattr(flags, 'q_lambda', None)
+  if q_lambda is not None:
+    if not 0.0 <= q_lambda <= 1.0:
+      raise ValueError('--q_lambda must be in [0, 1] (got %r)' % q_lambda)
+    if flags.algo != 'q':
+      raise ValueError('--q_lambda is a Q-learning option (lambda-return Q targets, DESIGN §4m; algo a3c has '
+                       '--gae_lambda): use it with --algo q')
+    if flags.q_nstep:
+      raise ValueError('--q_lambda with --q_nstep: the n-step engine is lambda = 1 with the target forward of s_n '
+                       'alone (DESIGN §4m); give one of them')
   first_screen = bool(getattr(flags, 'first_screen', False))
   if first_screen and game_kind(flags.env_name) != 'catch':
     raise ValueError('--first_screen is an option of the device game Catch (--env_name Catch-v0 or CatchMemory-v0, '
@@ -172,6 +188,8 @@ def engine_options(flags):
     kw['q_nstep'] = 1
   if flags.sarsa:
     kw['sarsa'] = 1
+  if q_lambda is not None:
+    kw['q_lambda'] = float(q_lambda)
   if flags.dqn_type == 'nature':
     kw['dqn_type'] = 'nature'
   if first_screen:
@@ -460,6 +478,8 @@ def main(argv=None):
     raise ValueError('--q_nstep is an engine option: --mode agent is the per-step Q-learning loop (one-step targets)')
   if flags.mode == 'agent' and flags.sarsa:
     raise ValueError('--sarsa is an engine option: --mode agent is the per-step Q-learning loop (max targets)')
+  if flags.mode == 'agent' and flags.q_lambda is not None:
+    raise ValueError('--q_lambda is an engine option: --mode agent is the per-step Q-learning loop (one-step targets)')
   if flags.mode == 'agent' and flags.first_screen:
     raise ValueError('--first_screen is an engine option: --mode agent is the reference loop (agent.py:59-67) as it stands')
   random.seed(flags.random_seed)

@@ -121,6 +121,8 @@ SIGNATURES = {
     'a3c_boot_action': (c_int, [c_void_p, c_void_p, c_i64, c_int, c_int, c_i64, c_int, c_u64, c_void_p, c_void_p]),
     'a3c_sarsa_target': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_i64, c_int, c_int,
                                  c_double, c_void_p, c_void_p]),
+    'a3c_lambda_q_target': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_i64, c_int,
+                                    c_int, c_double, c_double, c_void_p, c_void_p]),
     'a3c_loss_backward': (c_int, [ctypes.POINTER(NetDesc), c_void_p, c_void_p, c_i64, c_void_p, c_void_p,
                                   c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_void_p,
                                   c_void_p, c_void_p, c_void_p]),
@@ -173,6 +175,7 @@ SIGNATURES = {
     'a3c_engine_set_adam_powers': (c_int, [c_void_p, c_double, c_double, c_void_p]),
     'a3c_engine_set_catch_rules': (c_int, [c_void_p, c_int, c_int]),
     'a3c_engine_set_first_screen': (c_int, [c_void_p, c_int]),
+    'a3c_engine_set_q_lambda': (c_int, [c_void_p, c_int, c_double]),
     'a3c_engine_reset': (c_int, [c_void_p, c_void_p, c_void_p]),
     'a3c_engine_rollout_grad': (c_int, [c_void_p, c_void_p]),
     'a3c_engine_apply': (c_int, [c_void_p, c_void_p]),
@@ -240,6 +243,7 @@ OPTIONAL_IN_OLD_BUILDS = MEASUREMENT_ONLY + ('a3c_engine_exchange_split', 'a3c_e
                                              'a3c_engine_set_optimizer', 'a3c_engine_adam_powers',
                                              'a3c_engine_set_adam_powers', 'a3c_engine_set_catch_rules',
                                              'a3c_env_set_catch_rules', 'a3c_engine_set_first_screen',
+                                             'a3c_lambda_q_target', 'a3c_engine_set_q_lambda',
                                              'a3c_gemm_workspace_bytes', 'a3c_gemm_f32', 'a3c_gemm3_f32')
 
 KER_CONV12_FWD, KER_FC_FWD, KER_ENV_STEP, KER_CONV_BWD, KER_HEAD_SCREEN, KER_HEAD_SCREEN_CONV12, KER_FC_PART = 0, 1, 2, 3, 4, 5, 6

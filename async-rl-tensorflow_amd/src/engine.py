@@ -56,7 +56,8 @@ def _view(ptr, shape, dtype):
 class Engine:
     def __init__(self, num_envs=256, n_step=5, action_size=6, algo='a3c', start_lives=0, num_frames=None,
                  seed=123, env_id_base=0, world_size=1, use_graph=False, overlap=False, lstm=False,
-                 external_env=False, dqn_type='nips', game='synth', catch_rules=None, first_screen=None, **overrides):
+                 external_env=False, dqn_type='nips', game='synth', catch_rules=None, first_screen=None, q_lambda=None,
+                 **overrides):
         """game: 'synth' (the synthetic Atari stand-in) or 'catch' (Catch-v0, DESIGN §4g: action_size 3,
         start_lives 0, device envs, raw RGB pool; random_start is ignored).  num_frames=None: 1024
         frames (Catch needs its 640: a smaller explicit value is rejected by the library).
@@ -73,7 +74,13 @@ class Engine:
         first_screen=None | False | True (game 'catch'; None: off, and no call is made):
         a3c_engine_set_first_screen right after the create -- at a terminal the training rollout writes
         the new game's first screen into the history where the reference loop (agent.py:59-67) writes
-        the landing's, as Agent.play does (agent.py:366-367); kept as ``first_screen``.  Play ignores it."""
+        the landing's, as Agent.play does (agent.py:366-367); kept as ``first_screen``.  Play ignores it.
+        q_lambda=None | float in [0, 1] (algo q without q_nstep; None: the one-step rule, and no
+        call is made): a3c_engine_set_q_lambda right after the create -- lambda-return targets over the
+        rollout, Q(lambda), with double_q its double-Q form, with sarsa=1 Sarsa(lambda); 0 is the one-step
+        target and 1 the n-step return; kept as ``q_lambda``.  Not in the saved state: a resumed run gives it
+        again."""
+        self.q_lambda = self._check_q_lambda(q_lambda, algo, overrides.get('q_nstep', 0))
         if first_screen is not None and game != 'catch':
             raise ValueError('first_screen is an option of game catch, not of %r' % (game,))
         self.first_screen = bool(first_screen)
@@ -149,6 +156,8 @@ class Engine:
             check(lib().a3c_engine_set_catch_rules(h, *catch_rules), 'a3c_engine_set_catch_rules')
         if first_screen is not None:
             check(lib().a3c_engine_set_first_screen(h, int(bool(first_screen))), 'a3c_engine_set_first_screen')
+        if self.q_lambda is not None:
+            check(lib().a3c_engine_set_q_lambda(h, 1, self.q_lambda), 'a3c_engine_set_q_lambda')
         b = _lib.EngineBuffers()
         check(lib().a3c_engine_get_buffers(h, ctypes.byref(b)), 'a3c_engine_get_buffers')
         self._b = b
@@ -185,6 +194,27 @@ class Engine:
         """a3c_engine_set_first_screen between iterations: no reset, the next terminal follows it."""
         check(lib().a3c_engine_set_first_screen(self._h, int(bool(on))), 'a3c_engine_set_first_screen')
         self.first_screen = bool(on)
+
+    @staticmethod
+    def _check_q_lambda(value, algo, q_nstep):
+        if value is None:
+            return None
+        value = float(value)
+        if not 0.0 <= value <= 1.0:
+            raise ValueError('q_lambda must be in [0, 1] (got %r)' % (value,))
+        if algo != 'q':
+            raise ValueError('q_lambda is a Q-learning option (algo %r; a3c has gae_lambda)' % (algo,))
+        if q_nstep:
+            raise ValueError('q_lambda with q_nstep: the n-step engine is lambda = 1 with the target forward of s_n alone')
+        return value
+
+    def set_q_lambda(self, value):
+        """a3c_engine_set_q_lambda between iterations (None: back to the one-step rule): no reset, the next
+        gradient follows it."""
+        value = self._check_q_lambda(value, self.algo, self.cfg.q_nstep)
+        check(lib().a3c_engine_set_q_lambda(self._h, int(value is not None), 0.0 if value is None else value),
+              'a3c_engine_set_q_lambda')
+        self.q_lambda = value
 
     def _slot_views(self, k):
         b = _lib.EngineBuffers()

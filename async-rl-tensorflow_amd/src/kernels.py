@@ -410,6 +410,36 @@ def sarsa_target(rewards, terminals, actions, boot_actions, q_target, A, discoun
     return out
 
 
+def lambda_q_target(rewards, terminals, q_target, A, lam, discount=0.99, q_sel=None, actions=None, boot_actions=None):
+    """lambda-return Q targets [n,E] (a3c_lambda_q_target): rewards / terminals [n,E] of the rollout,
+    q_target [n*E,zs] the target rows of s_1..s_n (A live columns); the bootstrap value of a row is its maximum, with
+    q_sel [n*E,zs] (double Q) its value at q_sel's row argmax, with actions [n,E] and boot_actions [E] (Sarsa) its
+    value at the next taken action.  lam = 0: the one-step targets; lam = 1: the n-step returns."""
+    _dev(rewards, torch.float32, 'rewards')
+    _dev(terminals, torch.uint8, 'terminals')
+    _dev(q_target, torch.float32, 'q_target')
+    n, E = int(rewards.shape[0]), int(rewards.shape[1])
+    if tuple(terminals.shape) != (n, E) or q_target.dim() != 2 or int(q_target.shape[0]) != n * E:
+        raise ValueError('expected rewards / terminals [n, E] and q_target [%d, zs]' % (n * E))
+    if q_sel is not None:
+        _dev(q_sel, torch.float32, 'q_sel')
+        if tuple(q_sel.shape) != tuple(q_target.shape):
+            raise ValueError('q_sel: expected the shape of q_target')
+    if actions is not None:
+        _dev(actions, torch.int32, 'actions')
+        if tuple(actions.shape) != (n, E):
+            raise ValueError('actions: expected shape [n, E]')
+    if boot_actions is not None:
+        _dev(boot_actions, torch.int32, 'boot_actions')
+        if tuple(boot_actions.shape) != (E,):
+            raise ValueError('boot_actions: expected shape [E]')
+    out = torch.empty((n, E), dtype=torch.float32, device=rewards.device)
+    check(lib().a3c_lambda_q_target(ptr(rewards), ptr(terminals), ptr(actions), ptr(boot_actions), ptr(q_target),
+                                    ptr(q_sel), n, E, int(A), int(q_target.shape[1]), float(discount), float(lam),
+                                    ptr(out), stream_handle()), 'a3c_lambda_q_target')
+    return out
+
+
 def gemm_workspace(M, N, K, nsplit=1):
     """(effective split, workspace bytes) of a GEMM with ``nsplit`` requested (a3c_gemm_workspace_bytes; host only)."""
     eff, nbytes = ctypes.c_int(), ctypes.c_int64()

@@ -225,7 +225,40 @@ int a3c_sarsa_target(const float* rewards, const uint8_t* terminals, const int32
                      int A, int zs, double discount, float* target, void* stream);
 
 /* ----------------------------------------------------------------------------
- * K8+K9  loss + backward (network.py:81-94 with the SURVEY §8 A11 fixes / agent.py:306-317).
+ * K7f  lambda-return Q targets over the rollout (the forward view: Peng's Q(lambda), its double-Q form
+ *     and Sarsa(lambda)) over [n][E] in float64, contraction off, from the rollout's clipped rewards,
+ *     terminals and actions [n][E] and the target network's Q rows of s_1 .. s_n, q_target [n*E][zs]
+ *     (b = i*E + e, A live columns, columns >= A never read).  The bootstrap value B_i of s_{i+1}:
+ *       Q:         max_a q_target[b][a]
+ *       double Q   (q_sel != NULL, rows [n*E][zs] of the same states under the learner's own
+ *                  parameters): q_target[b][argmax_a q_sel[b][a]]              (the first maximum)
+ *       Sarsa      (actions, boot_actions != NULL): q_target[b][a'],
+ *                  a' = i < n-1 ? actions[i+1][e] : boot_actions[e]; an action word w is used as the
+ *                  column (uint32)w % A, so any word reads inside its row.
+ *     and, for env e, with G = (double)B_{n-1} before the loop, for i = n-1 .. 0:
+ *       mix = (1 - lambda) * B_i + lambda * G
+ *       if terminals[i][e]: mix = 0
+ *       G = rewards[i][e] + discount * mix
+ *       target[i][e] = (float)G
+ *     which is (1 - lambda) sum_k lambda^(k-1) G^(k) + lambda^(N-1) G^(N) over the k-step returns
+ *     G^(k) of the rollout's remaining N = n - i steps, cut at the first terminal.  With finite
+ *     inputs this operation order makes both ends exact: lambda = 0 gives mix = B_i + 0, that is
+ *     a3c_td_target (with q_sel its double-Q form) / a3c_sarsa_target(nstep = 0) to the last bit;
+ *     lambda = 1 gives mix = 0 + G, that is a3c_nstep_q_target / a3c_sarsa_target(nstep = 1) on the
+ *     rows of s_n to the last bit.  The engine (a3c_engine_set_q_lambda) takes q_target from the
+ *     target network, q_sel from the slot's own Q rows and boot_actions from a3c_boot_action's draw.
+ *     No trace is cut at a non-greedy action (Watkins's Q(lambda) is not this rule).
+ *     A3C_ERR_INVALID: a null rewards, terminals, q_target or target; q_sel together with actions /
+ *     boot_actions; only one of actions / boot_actions; lambda outside [0, 1] or NaN; n < 1; E < 1;
+ *     A < 1; zs < A.
+ * -------------------------------------------------------------------------- */
+int a3c_lambda_q_target(const float* rewards, const uint8_t* terminals, const int32_t* actions,
+                        const int32_t* boot_actions, const float* q_target, const float* q_sel, int n,
+                        int64_t E, int A, int zs, double discount, double lambda, float* target,
+                        void* stream);
+
+/* ----------------------------------------------------------------------------
+ * K8+K9 loss + backward (network.py:81-94 with the SURVEY §8 A11 fixes / agent.py:306-317).
  *  target: a3c -> R (n-step return); q -> TD target.
  *  a3c loss per sample  -log pi(a)*stopgrad(R-V) - beta*H + (R-V)^2/2, summed over B
  *      (literal_adv != 0: no stop-gradient, network.py:83-84 literal form);
@@ -588,6 +621,22 @@ int a3c_engine_set_catch_rules(a3c_engine* eng, int visible_rows, int frozen_row
  * the checkpoint's state.  An engine that never calls it launches what it launched without it.
  * python async-rl-tensorflow_amd/main.py --mode engine --lstm true --env_name CatchMemory-v0 --first_screen true */
 int a3c_engine_set_first_screen(a3c_engine* eng, int on);
+/* q_lambda: lambda-return targets for a Q engine (a3c_lambda_q_target), the knob between
+ * its one-step targets (lambda = 0) and the n-step returns of cfg.q_nstep (lambda = 1).  on = 0, the
+ * default: every launch is what it is without this call.  on = 1: the gradient's launches are those
+ * of the one-step rule -- the target network on the n*E rows of s_1 .. s_n, and for double Q and Sarsa
+ * the slot's own forward of s_n -- with a3c_lambda_q_target in the target kernel's place: cfg.double_q
+ * passes the rollout's own rows of s_1 .. s_n as q_sel, a Sarsa engine (a3c_engine_opts.sarsa) draws
+ * a_n as it does without lambda (a3c_boot_action's rule, inside the target kernel;
+ * a3c_engine_slot_boot_actions reads it) and passes the rollout's actions.  Sync, overlap,
+ * graph, host-env and Hogwild iterations share that block.  A setter, as the three above: no reset,
+ * the next gradient follows it; it drops captured graphs.  A3C_ERR_INVALID, before anything touches the
+ * device and in this order: on not 0 or 1, lambda outside [0, 1] or NaN, eng NULL, an engine of algo
+ * a3c (it has cfg.gae_lambda), an engine with cfg.q_nstep = 1 (that engine is lambda = 1 with the
+ * target forward of s_n alone).  A3C_ERR_STATE: a computed gradient not yet applied.  A hyperparameter:
+ * not in the checkpoint's state (a resumed run gives it again), and play does not read it.
+ * python async-rl-tensorflow_amd/main.py --mode engine --algo q --q_lambda 0.8 --env_name Catch-v0 */
+int a3c_engine_set_q_lambda(a3c_engine* eng, int on, double lambda);
 /* fill the frame pool, reset the envs (new_random_game, environment.py:35-40), fill each
  * history with 4 copies of the first screen (agent.py:37-38) and initialise params
  * from host memory (nullable -> keep), rms slot = 1, mom = 0 (Adam: m = v = 0, products = 1). */
