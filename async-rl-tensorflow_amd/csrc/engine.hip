@@ -1313,6 +1313,23 @@ extern "C" int a3c_engine_set_q_lambda(a3c_engine* e, int on, double lambda) {
   return 0;
 }
 
+// precision: the nature trunk's conv compute mode, read from the layout by every nature
+// launch (weight prep, forward, the backward's conv passes).  No reset: the next rollout follows it.
+extern "C" int a3c_engine_set_precision(a3c_engine* e, int precision) {
+  if (precision != A3C_PREC_FP32 && precision != A3C_PREC_BF16)
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_set_precision", "precision: A3C_PREC_FP32 or A3C_PREC_BF16");
+  if (!e) return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_set_precision", "null");
+  if (precision == A3C_PREC_BF16 && !e->nat)
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_set_precision",
+                         "the bf16 mode is the nature trunk's (the NIPS rollout kernel has none)");
+  if (e->grad_ready && !e->grad_applied)
+    return a3c_set_error(A3C_ERR_STATE, "a3c_engine_set_precision", "a gradient is pending: apply it first");
+  A3C_CHECK(hipDeviceSynchronize());      // (the engine's streams: nothing in flight reads the prepared weights)
+  e->L.prec = precision;
+  drop_graphs(e);   // (they hold the other mode's kernels)
+  return 0;
+}
+
 extern "C" int a3c_engine_reset(a3c_engine* e, const float* host_params, void* stream) {
   if (!e) return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_reset", "null");
   hipStream_t s = (hipStream_t)stream;
@@ -2277,8 +2294,9 @@ extern "C" int a3c_engine_time_kernel(a3c_engine* e, int kernel, int iters, void
   if (e->nat) {   // one pass of the nature trunk: forward over E states, backward passes over n*E samples
     const int pass = kernel - A3C_KER_NAT_C1F;
     const bool fwd = pass <= NAT_FCF;
-    if ((pass == NAT_C3F && a3c_nat_conv23_fused()) || (pass == NAT_C1F && a3c_nat_conv123_fused()) ||
-        (pass == NAT_C2X && a3c_nat_dx_fused()))
+    const bool b1 = L.prec == A3C_PREC_BF16;   // (its forward is one launch under NAT_C2F, its dX passes two)
+    if ((pass == NAT_C3F && (b1 || a3c_nat_conv23_fused())) || (pass == NAT_C1F && (b1 || a3c_nat_conv123_fused())) ||
+        (pass == NAT_C2X && !b1 && a3c_nat_dx_fused()))
       return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_time_kernel",
                            "this pass runs inside another pass's launch (k_nat_conv23 under A3C_KER_NAT_C2F, k_nat_dx32 under A3C_KER_NAT_C3X)");
     if (!fwd && !e->grad_ready)

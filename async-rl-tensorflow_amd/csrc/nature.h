@@ -65,7 +65,8 @@ int a3c_nat_pass_launch(int pass, const NetLayout& L, const float* P, const Stat
 // the rollout start on the nature trunk: the bf16 weight terms of P into w1t (the prepared block,
 // A3C_NAT_PREP_BYTES: conv1's [3][32][256] in (cin, kh, kw) order, then conv2's [3][64][512] and
 // conv3's [3][64][576], each [term][cout][k] in TF k order), tau snapshot (overlap) and the
-// backward's go
+// backward's go.  L.prec == A3C_PREC_BF16: rn(W) alone, each form's first term ([cout][k] at the
+// same offsets; the other terms' bytes are left as they are and nothing reads them)
 #define A3C_NAT_W1T_BYTES (3 * NT1_N * NT_K1 * 2)
 #define A3C_NAT_W2T_OFF A3C_NAT_W1T_BYTES
 #define A3C_NAT_W3T_OFF (A3C_NAT_W2T_OFF + 3 * NT2_N * NT_K2 * 2)

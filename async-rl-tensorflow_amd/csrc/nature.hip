@@ -397,7 +397,9 @@ __device__ inline void nat_split2(float x0, float x1, uint32_t (&o)[NT]) {
   }
 }
 
-template <int MODE, int LAYER, int BN, int TA, int NBUF, int PF>
+// TB = 1 (with TA = 1): the bf16 compute mode (A3C_PREC_BF16) -- both operands rounded
+// once at the LDS store, one product per K step, a third of the LDS
+template <int MODE, int LAYER, int BN, int TA, int TB, int NBUF, int PF>
 __global__ void __launch_bounds__(256) k_nat_gemm_bf(NatGemm a) {
   using G = NG<LAYER>;
   constexpr int BM = 4096 / BN, BK = 32, LD = 40;
@@ -407,7 +409,8 @@ __global__ void __launch_bounds__(256) k_nat_gemm_bf(NatGemm a) {
   constexpr bool DW = MODE == NG_DW || MODE == NG_DW1;
   constexpr bool U8 = MODE == NG_DW1;
   static_assert(MODE != NG_FWD1, "conv1 forward: k_nat_conv1_bf");
-  static_assert(TA == 3 || (TA == 1 && U8), "one A term only for the exact u8 pixels");
+  static_assert(TB == 3 || (TB == 1 && TA == 1), "one B term: the bf16 mode, one A term as well");
+  static_assert(TA == 3 || (TA == 1 && (U8 || TB == 1)), "one A term: the exact u8 pixels, or the bf16 mode");
   constexpr int AQ = BM * BK / 4 / 256;                          // A quads per thread (2 or 4)
   constexpr int BQ0 = BN * BK / 4 / 256;
   constexpr int BQ = B_NC && BQ0 < 2 ? 2 : BQ0;                  // B quads per thread (pairs: >= 2)
@@ -419,7 +422,7 @@ __global__ void __launch_bounds__(256) k_nat_gemm_bf(NatGemm a) {
   static_assert(!U8 || G::C == 4, "u8 planes: the 4 history frames");
   static_assert((BM / 4) % 4 == 0 && (BN / 4) % 4 == 0, "pair mapping: 4 quads of a row per lane group");
   __shared__ __attribute__((aligned(16))) uint16_t As[NBUF][TA][BM][LD];   // NBUF 1: a third of the LDS,
-  __shared__ __attribute__((aligned(16))) uint16_t Bs[NBUF][3][BN][LD];    // two barriers per slice
+  __shared__ __attribute__((aligned(16))) uint16_t Bs[NBUF][TB][BN][LD];   // two barriers per slice
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wm = wid / WN, wn = wid % WN;
   int by, bz;
@@ -576,21 +579,21 @@ __global__ void __launch_bounds__(256) k_nat_gemm_bf(NatGemm a) {
         if (!bok[j]) continue;
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-          uint32_t w[3];
-          nat_split2<3>(rbv[j][c], rbv[j + 1][c], w);
+          uint32_t w[TB];
+          nat_split2<TB>(rbv[j][c], rbv[j + 1][c], w);
 #pragma unroll
-          for (int t = 0; t < 3; ++t) *(uint32_t*)&Bs[buf][t][bc[j] + c][br[j]] = w[t];
+          for (int t = 0; t < TB; ++t) *(uint32_t*)&Bs[buf][t][bc[j] + c][br[j]] = w[t];
           if (DW && do_colsum) cs[j / 2][c] += rbv[j][c] + rbv[j + 1][c];
         }
       }
     } else {
 #pragma unroll
       for (int j = 0; j < BQ; ++j) {
-        uint32_t lo[3], hi[3];
-        nat_split2<3>(rbv[j][0], rbv[j][1], lo);
-        nat_split2<3>(rbv[j][2], rbv[j][3], hi);
+        uint32_t lo[TB], hi[TB];
+        nat_split2<TB>(rbv[j][0], rbv[j][1], lo);
+        nat_split2<TB>(rbv[j][2], rbv[j][3], hi);
 #pragma unroll
-        for (int t = 0; t < 3; ++t) *(uint2*)&Bs[buf][t][br[j]][bc[j]] = make_uint2(lo[t], hi[t]);
+        for (int t = 0; t < TB; ++t) *(uint2*)&Bs[buf][t][br[j]][bc[j]] = make_uint2(lo[t], hi[t]);
       }
     }
   };
@@ -626,12 +629,14 @@ __global__ void __launch_bounds__(256) k_nat_gemm_bf(NatGemm a) {
   auto compute = [&](int buf) {
 #pragma unroll
     for (int s = 0; s < BK / 16; ++s) {
-      bf16x8 af[TA], bv[3];
+      bf16x8 af[TA], bv[TB];
 #pragma unroll
       for (int t = 0; t < TA; ++t) af[t] = *(const bf16x8*)&As[buf][t][wm * 32 + r][16 * s + 8 * h];
 #pragma unroll
-      for (int t = 0; t < 3; ++t) bv[t] = *(const bf16x8*)&Bs[buf][t][wn * 32 + r][16 * s + 8 * h];
-      if constexpr (TA == 1) {
+      for (int t = 0; t < TB; ++t) bv[t] = *(const bf16x8*)&Bs[buf][t][wn * 32 + r][16 * s + 8 * h];
+      if constexpr (TB == 1) {
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0], bv[0], acc, 0, 0, 0);
+      } else if constexpr (TA == 1) {
         acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0], bv[2], acc, 0, 0, 0);
         acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0], bv[1], acc, 0, 0, 0);
         acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0], bv[0], acc, 0, 0, 0);
@@ -741,20 +746,20 @@ __global__ void __launch_bounds__(256) k_nat_gemm_bf(NatGemm a) {
   }
 }
 
-template <int MODE, int LAYER, int BN, int TA>
+template <int MODE, int LAYER, int BN, int TA, int TB = 3>
 static int nat_go_bf(NatGemm a, unsigned gz, hipStream_t s, bool one_buf, bool pf2) {
   constexpr int BM = 4096 / BN;
   if (a.M <= 0 || a.N <= 0) return 0;
   a.xcd = nat_xcd();
   const dim3 grid((unsigned)((a.N + BN - 1) / BN), (unsigned)((a.M + BM - 1) / BM), gz);
   if (one_buf && pf2)
-    hipLaunchKernelGGL((k_nat_gemm_bf<MODE, LAYER, BN, TA, 1, 2>), grid, dim3(256), 0, s, a);
+    hipLaunchKernelGGL((k_nat_gemm_bf<MODE, LAYER, BN, TA, TB, 1, 2>), grid, dim3(256), 0, s, a);
   else if (one_buf)
-    hipLaunchKernelGGL((k_nat_gemm_bf<MODE, LAYER, BN, TA, 1, 1>), grid, dim3(256), 0, s, a);
+    hipLaunchKernelGGL((k_nat_gemm_bf<MODE, LAYER, BN, TA, TB, 1, 1>), grid, dim3(256), 0, s, a);
   else if (pf2)
-    hipLaunchKernelGGL((k_nat_gemm_bf<MODE, LAYER, BN, TA, 2, 2>), grid, dim3(256), 0, s, a);
+    hipLaunchKernelGGL((k_nat_gemm_bf<MODE, LAYER, BN, TA, TB, 2, 2>), grid, dim3(256), 0, s, a);
   else
-    hipLaunchKernelGGL((k_nat_gemm_bf<MODE, LAYER, BN, TA, 2, 1>), grid, dim3(256), 0, s, a);
+    hipLaunchKernelGGL((k_nat_gemm_bf<MODE, LAYER, BN, TA, TB, 2, 1>), grid, dim3(256), 0, s, a);
   A3C_CHECK(hipGetLastError());
   return 0;
 }
@@ -774,9 +779,15 @@ __device__ inline uint32_t nat_bf16_rn(float f) {
   return u >> 16;
 }
 
+// NT = 3: the three terms; NT = 1 (the bf16 mode): rn(w) alone, in the first term's place
+template <int NT>
 __device__ inline void nat_terms3(float w, uint16_t* dst, int64_t tstride) {
 #pragma clang fp contract(off)
   const uint32_t h = nat_bf16_rn(w);
+  if constexpr (NT == 1) {
+    dst[0] = (uint16_t)h;
+    return;
+  }
   const float r1 = w - __uint_as_float(h << 16);
   const uint32_t m = nat_bf16_rn(r1);
   const float r2 = r1 - __uint_as_float(m << 16);
@@ -788,6 +799,7 @@ __device__ inline void nat_terms3(float w, uint16_t* dst, int64_t tstride) {
 
 // the prepared block: conv1 [3][32][256] with k' = (cin, kh, kw); conv2 [3][64][512] and conv3
 // [3][64][576] with k in TF order (kh, kw, cin) -- one thread per (cout, k)
+template <int NT>
 __global__ void __launch_bounds__(256) k_nat_w_terms(const float* __restrict__ W1, const float* __restrict__ W2,
                                                      const float* __restrict__ W3, uint16_t* __restrict__ wt,
                                                      int all) {
@@ -795,33 +807,33 @@ __global__ void __launch_bounds__(256) k_nat_w_terms(const float* __restrict__ W
   if (i < NT1_N * NT_K1) {
     const int n = i / NT_K1, k = i - n * NT_K1;
     const int c = k >> 6, kh = (k >> 3) & 7, kw = k & 7;
-    nat_terms3(W1[((kh * 8 + kw) * HIST + c) * NT1_N + n], wt + n * NT_K1 + k, NT1_N * NT_K1);
+    nat_terms3<NT>(W1[((kh * 8 + kw) * HIST + c) * NT1_N + n], wt + n * NT_K1 + k, NT1_N * NT_K1);
     return;
   }
   if (!all) return;
   i -= NT1_N * NT_K1;
   if (i < NT2_N * NT_K2) {
     const int n = i / NT_K2, k = i - n * NT_K2;
-    nat_terms3(W2[k * NT2_N + n], wt + A3C_NAT_W2T_OFF / 2 + n * NT_K2 + k, NT2_N * NT_K2);
+    nat_terms3<NT>(W2[k * NT2_N + n], wt + A3C_NAT_W2T_OFF / 2 + n * NT_K2 + k, NT2_N * NT_K2);
     return;
   }
   i -= NT2_N * NT_K2;
   if (i < NT3_N * NT_K3) {
     const int n = i / NT_K3, k = i - n * NT_K3;
-    nat_terms3(W3[k * NT3_N + n], wt + A3C_NAT_W3T_OFF / 2 + n * NT_K3 + k, NT3_N * NT_K3);
+    nat_terms3<NT>(W3[k * NT3_N + n], wt + A3C_NAT_W3T_OFF / 2 + n * NT_K3 + k, NT3_N * NT_K3);
     return;
   }
   i -= NT3_N * NT_K3;
   // dX forms: [term][cin][tap][cout] = W[tap][cin][cout] (TF [kh][kw][cin][cout]): a copy per term
   if (i < NT1_N * NT_X2) {
     const int c = i / NT_X2, r = i - c * NT_X2, tap = r >> 6, oc = r & 63;
-    nat_terms3(W2[(tap * NT1_N + c) * NT2_N + oc], wt + A3C_NAT_W2X_OFF / 2 + i, NT1_N * NT_X2);
+    nat_terms3<NT>(W2[(tap * NT1_N + c) * NT2_N + oc], wt + A3C_NAT_W2X_OFF / 2 + i, NT1_N * NT_X2);
     return;
   }
   i -= NT1_N * NT_X2;
   if (i < NT2_N * NT_K3) {
     const int c = i / NT_K3, r = i - c * NT_K3, tap = r >> 6, oc = r & 63;
-    nat_terms3(W3[(tap * NT2_N + c) * NT3_N + oc], wt + A3C_NAT_W3X_OFF / 2 + i, NT2_N * NT_K3);
+    nat_terms3<NT>(W3[(tap * NT2_N + c) * NT3_N + oc], wt + A3C_NAT_W3X_OFF / 2 + i, NT2_N * NT_K3);
   }
 }
 
@@ -1204,6 +1216,211 @@ __global__ void __launch_bounds__(256) k_nat_conv23(const float* __restrict__ l1
 }
 
 // ---------------------------------------------------------------------------------------
+// The bf16 compute mode's forward (A3C_PREC_BF16): conv1 -> conv2 -> conv3 of one state
+// per workgroup with one bf16 term per operand, rn(x) . rn(W), one v_mfma_f32_16x16x32_bf16 per K
+// step, fp32 accumulators, bias + ReLU in fp32; l1 / l2 / l3 go out as fp32 (the backward's
+// operands), rn(l1) and rn(l2) stay in LDS as the next layer's operand.
+// LDS, 32000 B (k_nat_conv23<true>: 76800), three tenants over one region:
+//   planes  [cin 4][y 84][88 B] u8, 29568 B: staged as they are in the frame ring (a quarter of
+//           the bf16 rows); conv1's A fragment is a lane's 8 pixels kw 0..7 of one (cin, kh) patch
+//           row = two dword reads, converted in registers (exact: a pixel is the upper half of its
+//           f32).  A wave owns both 16-channel n-tiles of its m-tiles (w + 4 i of the 25), so each
+//           converted fragment feeds two MFMAs.
+//   l1      [y 20][x parity 2][x / 2 10][40 bf16], 32000 B, over the planes once conv1 has read
+//           them: the parity-split rows of k_nat_conv23 (conv2's 16 consecutive output pixels sit
+//           one row apart), rows padded 32 -> 40 so that the 16 lanes of a fragment read hit 16
+//           different 16-byte bank groups (80 B apart) -- the padding the three-term kernel had no
+//           room for
+//   l2      [81][72 bf16], 11664 B, over l1 once conv2 has read it
+// Wave w owns output channels 16 w .. 16 w + 15 of conv2 and conv3; every layer's weight fragments
+// (k_nat_w_terms<1>: [cout][k], the first term's place of the prepared block) stream from L2
+// through the C23_PD + 1 deep register ring.
+// ---------------------------------------------------------------------------------------
+#define B1_PR 88                                    // bytes per staged u8 plane row (84 + 4)
+#define B1_R1 40                                    // bf16 per l1 pixel (32 + 8)
+#define B1_R2 72                                    // bf16 per l2 pixel (64 + 8)
+#define B1_PLANES (HIST * IMG * B1_PR)              // 29568 B
+#define B1_L1 (NT1_P * B1_R1 * 2)                   // 32000 B
+#define B1_L2 (NT2_P * B1_R2 * 2)                   // 11664 B
+#define B1_LDS (B1_L1 > B1_PLANES ? B1_L1 : B1_PLANES)
+static_assert(B1_L2 <= B1_LDS && B1_LDS % 16 == 0, "l2 overlays l1");
+static_assert(NT1_P % 16 == 0 && (NT1_P / 16 + 3) / 4 == 7, "conv1: 25 m-tiles dealt over 4 waves, 7 slots");
+
+__global__ void __launch_bounds__(256) k_nat_conv123_b1(StateAddr sa, const uint16_t* __restrict__ w1r,
+                                                        const float* __restrict__ b1, const uint16_t* __restrict__ w2r,
+                                                        const float* __restrict__ b2, const uint16_t* __restrict__ w3r,
+                                                        const float* __restrict__ b3, float* __restrict__ l1,
+                                                        float* __restrict__ l2, float* __restrict__ l3, float scale) {
+  __shared__ __attribute__((aligned(16))) uint8_t smb[B1_LDS];
+  uint16_t* sm = (uint16_t*)smb;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int i16 = lane & 15, g = lane >> 4;
+  const int64_t b = blockIdx.x;
+  unsigned long long* srec = span_rec(sa, sa.tau_ptr ? *sa.tau_ptr : 0);   // (as k_nat_conv23<true>)
+  span_begin(srec);
+  {
+    // ---- the 4 history planes of state b, u8 [cin][84][88]: every dword in flight, then stored ----
+    RingRows ring;
+    ring.init(sa, sa.tau_ptr ? *sa.tau_ptr : 0);
+    const int st = ring.step_of((int)b), e = (int)b - st * ring.E;
+    constexpr int NQ = HIST * PLANE / 4, PQ = PLANE / 4, PER = (NQ + 255) / 256;
+    const uint32_t* pl4[HIST];
+#pragma unroll
+    for (int c = 0; c < HIST; ++c) pl4[c] = (const uint32_t*)ring.plane(e, st, c);
+    uint32_t pv[PER];
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+      const int q = tid + 256 * i, c = q / PQ;
+      pv[i] = q < NQ ? pl4[c < HIST ? c : 0][q - c * PQ] : 0u;
+    }
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+      const int q = tid + 256 * i;
+      if (q < NQ) {
+        const int c = q / PQ, r = q - c * PQ, y = r / (IMG / 4), x4 = (r - y * (IMG / 4)) * 4;
+        *(uint32_t*)&smb[(c * IMG + y) * B1_PR + x4] = pv[i];
+      }
+    }
+  }
+  __syncthreads();
+  {
+    // ---- conv1: wave w takes m-tiles w + 4 i (25 of 16 pixels), both n-tiles of 16 channels ----
+    constexpr int MT = 7, NTILES = NT1_P / 16;
+    int base1[MT];
+    f32x4 acc1[MT][2];
+#pragma unroll
+    for (int i = 0; i < MT; ++i) {
+      const int m = min(16 * (w + 4 * i) + i16, NT1_P - 1);
+      const int oy = m / NT1_O, ox = m - oy * NT1_O;
+      base1[i] = 4 * oy * B1_PR + 4 * ox;
+      acc1[i][0] = acc1[i][1] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
+    const uint16_t* wb1 = w1r + i16 * NT_K1 + 8 * g;
+    bf16x8 q1[C23_PD + 1][2];
+    auto ldb1 = [&](int ks, bf16x8 (&dst)[2]) {
+#pragma unroll
+      for (int j = 0; j < 2; ++j) dst[j] = *(const bf16x8*)(wb1 + j * 16 * NT_K1 + ks * 32);
+    };
+#pragma unroll
+    for (int q = 0; q < C23_PD; ++q) ldb1(q, q1[q]);
+#pragma unroll
+    for (int ks = 0; ks < NT_K1 / 32; ++ks) {
+      if (ks + C23_PD < NT_K1 / 32) ldb1(ks + C23_PD, q1[(ks + C23_PD) % (C23_PD + 1)]);
+      const int cin = ks >> 1, kh = 4 * (ks & 1) + g;        // k' = (cin, kh, kw): a lane's 8 k are kw 0..7
+      const uint8_t* rp = smb + (cin * IMG + kh) * B1_PR;
+      const bf16x8* bb = q1[ks % (C23_PD + 1)];
+#pragma unroll
+      for (int i = 0; i < MT; ++i) {
+        if (w + 4 * i >= NTILES) continue;                    // (wave-uniform) the 25 tiles
+        const uint2 lo = nat_u8x4_bf16(*(const uint32_t*)(rp + base1[i]));
+        const uint2 hi = nat_u8x4_bf16(*(const uint32_t*)(rp + base1[i] + 4));
+        const bf16x8 a = __builtin_bit_cast(bf16x8, make_uint4(lo.x, lo.y, hi.x, hi.y));
+        acc1[i][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bb[0], acc1[i][0], 0, 0, 0);
+        acc1[i][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bb[1], acc1[i][1], 0, 0, 0);
+      }
+    }
+    __syncthreads();   // the planes are no longer read: their LDS takes rn(l1)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int n1 = 16 * j + i16;
+      const float bn1 = b1[n1];
+#pragma unroll
+      for (int i = 0; i < MT; ++i) {
+        if (w + 4 * i >= NTILES) continue;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int m = 16 * (w + 4 * i) + 4 * g + r;
+          const float v = fmaxf(acc1[i][j][r] * scale + bn1, 0.f);
+          l1[(b * NT1_P + m) * NT1_N + n1] = v;
+          const int y = m / NT1_O, x = m - y * NT1_O;
+          const int slot = (y * 2 + (x & 1)) * (NT1_O / 2) + (x >> 1);
+          sm[slot * B1_R1 + n1] = (uint16_t)nat_bf16_rn(v);
+        }
+      }
+    }
+  }
+  __syncthreads();
+  // ---- conv2: 6 m-tiles of 16 pixels (81 valid) x this wave's 16 channels, 16 taps of 32 cin ----
+  const int n = 16 * w + i16;
+  bf16x8 bq[C23_PD + 1];
+  f32x4 acc2[6];
+  {
+    int base2[6];
+#pragma unroll
+    for (int mt = 0; mt < 6; ++mt) {
+      const int m = min(16 * mt + i16, NT2_P - 1);
+      const int oy = m / NT2_O, ox = m - oy * NT2_O;
+      base2[mt] = (oy * 2 * 2) * (NT1_O / 2) + ox;           // slot of (y = 2 oy, parity 0, x/2 = ox)
+      acc2[mt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
+    const uint16_t* wb2 = w2r + (int64_t)n * NT_K2 + 8 * g;
+#pragma unroll
+    for (int q = 0; q < C23_PD; ++q) bq[q] = *(const bf16x8*)(wb2 + q * 32);
+#pragma unroll
+    for (int tap = 0; tap < 16; ++tap) {
+      if (tap + C23_PD < 16) bq[(tap + C23_PD) % (C23_PD + 1)] = *(const bf16x8*)(wb2 + (tap + C23_PD) * 32);
+      const int kh = tap >> 2, kw = tap & 3;
+      const int toff = (kh * 2 + (kw & 1)) * (NT1_O / 2) + (kw >> 1);
+#pragma unroll
+      for (int mt = 0; mt < 6; ++mt) {
+        const bf16x8 a = *(const bf16x8*)(sm + (base2[mt] + toff) * B1_R1 + 8 * g);
+        acc2[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bq[tap % (C23_PD + 1)], acc2[mt], 0, 0, 0);
+      }
+    }
+  }
+  __syncthreads();   // every wave is done reading rn(l1)
+  {
+    const float bn = b2[n];
+#pragma unroll
+    for (int mt = 0; mt < 6; ++mt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int m = 16 * mt + 4 * g + r;
+        if (m < NT2_P) {
+          const float v = fmaxf(acc2[mt][r] + bn, 0.f);
+          l2[(b * NT2_P + m) * NT2_N + n] = v;
+          sm[m * B1_R2 + n] = (uint16_t)nat_bf16_rn(v);
+        }
+      }
+  }
+  // weight ring of conv3 starts under the barrier
+  const uint16_t* wb3 = w3r + (int64_t)n * NT_K3 + 8 * g;
+#pragma unroll
+  for (int q = 0; q < C23_PD; ++q) bq[q] = *(const bf16x8*)(wb3 + q * 32);
+  __syncthreads();
+  // ---- conv3: 4 m-tiles of 16 pixels (49 valid), 18 K steps (9 taps x 2 channel halves) ----
+  int base3[4];
+  f32x4 acc3[4];
+#pragma unroll
+  for (int mt = 0; mt < 4; ++mt) {
+    const int m = min(16 * mt + i16, NT3_P - 1);
+    const int oy = m / NT3_O, ox = m - oy * NT3_O;
+    base3[mt] = oy * NT2_O + ox;
+    acc3[mt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  }
+#pragma unroll
+  for (int st = 0; st < 18; ++st) {
+    if (st + C23_PD < 18) bq[(st + C23_PD) % (C23_PD + 1)] = *(const bf16x8*)(wb3 + (st + C23_PD) * 32);
+    const int tap = st >> 1, kh = tap / 3, kw = tap - kh * 3;
+    const int off = (kh * NT2_O + kw) * B1_R2 + 32 * (st & 1) + 8 * g;
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt) {
+      const bf16x8 a = *(const bf16x8*)(sm + base3[mt] * B1_R2 + off);
+      acc3[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bq[st % (C23_PD + 1)], acc3[mt], 0, 0, 0);
+    }
+  }
+  const float b3n = b3[n];
+#pragma unroll
+  for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int m = 16 * mt + 4 * g + r;
+      if (m < NT3_P) l3[(b * NT3_P + m) * NT3_N + n] = fmaxf(acc3[mt][r] + b3n, 0.f);
+    }
+  span_end(srec);
+}
+
+// ---------------------------------------------------------------------------------------
 // conv3 dX and conv2 dX fused, one workgroup per sample (network.py's conv2 / conv3 backward):
 //   dl2 = col2im(dl3 W3^T) * (l2 > 0)   M = 81 pixels, N = 64, K = 9 taps x 64 cout
 //   dl1 = col2im(dl2 W2^T) * (l1 > 0)   per stride-2 parity class: M = 100, N = 32, K = 4 real taps x 64
@@ -1539,8 +1756,14 @@ int a3c_nat_pass_launch(int pass, const NetLayout& L, const float* P, const Stat
                         const float* l2, const float* l3, const float* l4, const uint16_t* w1t, float* fws,
                         float* bws, hipStream_t s) {
   NatGemm a = {};
+  // the bf16 mode: its own forward kernel whatever the A/B knobs say, the one-term tiles
+  // for the five backward passes (k_nat_dx32 has no one-term form)
+  const bool b1 = L.prec == A3C_PREC_BF16;
+  if (b1 && !w1t && pass <= NAT_C3F)
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_nat_pass_launch", "bf16 mode: the forward needs the prepared block");
   switch (pass) {
     case NAT_C1F:
+      if (b1) return 0;                                     // inside NAT_C2F's launch
       if (w1t && nat_fuse23() && nat_fuse123()) return 0;   // inside NAT_C2F's launch
       if (w1t && nat_c1_bf()) {
         const int M = (int)(B * NT1_P);
@@ -1558,6 +1781,13 @@ int a3c_nat_pass_launch(int pass, const NetLayout& L, const float* P, const Stat
       a.M = (int)(B * NT1_P); a.N = NT1_N; a.K = NT_K1; a.scale = 1.0f / 255.0f;
       return nat_go<NG_FWD1, 1, 32>(a, 1, s);
     case NAT_C2F:
+      if (b1) {   // conv1 + conv2 + conv3, one term per operand; NAT_C1F and NAT_C3F then empty
+        hipLaunchKernelGGL(k_nat_conv123_b1, dim3((unsigned)B), dim3(256), 0, s, sa, w1t, P + L.off[N_L1B],
+                           w1t + A3C_NAT_W2T_OFF / 2, P + L.off[N_L2B], w1t + A3C_NAT_W3T_OFF / 2, P + L.off[N_L3B],
+                           (float*)l1, (float*)l2, (float*)l3, 1.0f / 255.0f);
+        A3C_CHECK(hipGetLastError());
+        return 0;
+      }
       if (w1t && nat_fuse23()) {   // conv2 + conv3 (+ conv1) in one launch; NAT_C3F (NAT_C1F) then empty
         if (nat_fuse123())
           hipLaunchKernelGGL(k_nat_conv23<true>, dim3((unsigned)B), dim3(256), 0, s, (const float*)nullptr,
@@ -1575,7 +1805,7 @@ int a3c_nat_pass_launch(int pass, const NetLayout& L, const float* P, const Stat
       a.M = (int)(B * NT2_P); a.N = NT2_N; a.K = NT_K2;
       return nat_fwd_split<2>(a, fws, s);
     case NAT_C3F:
-      if (w1t && nat_fuse23()) return 0;
+      if (b1 || (w1t && nat_fuse23())) return 0;
       a.X = l2; a.Wt = P + L.off[N_L3W]; a.bias = P + L.off[N_L3B]; a.Y = (float*)l3;
       a.M = (int)(B * NT3_P); a.N = NT3_N; a.K = NT_K3;
       return nat_fwd_split<3>(a, fws, s);
@@ -1613,10 +1843,11 @@ int a3c_nat_pass_launch(int pass, const NetLayout& L, const float* P, const Stat
     case NAT_C3W:     // dW3 (+ db3) over the (sample, pixel) rows
       a.X = l2; a.dY = bws + p.dl3; a.slab = bws + p.s3; a.colsum = bws + p.c3;
       a.M = NT_K3; a.N = NT3_N; a.K = (int)(B * NT3_P); a.kchunk = p.kc3;
+      if (b1) return nat_go_bf<NG_DW, 3, 64, 1, 1>(a, (unsigned)p.ns3, s, nat_bf1(NAT_C3W), nat_pf2(NAT_C3W));
       return nat_bf(NAT_C3W) ? nat_go_bf<NG_DW, 3, 64, 3>(a, (unsigned)p.ns3, s, nat_bf1(NAT_C3W), nat_pf2(NAT_C3W))
                            : nat_go<NG_DW, 3, 64>(a, (unsigned)p.ns3, s);
     case NAT_C3X:     // dl2 = col2im(dl3 W3^T) * (l2 > 0)
-      if (w1t && nat_fuse_dx()) {   // and dl1 in the same launch (k_nat_dx32); NAT_C2X then empty
+      if (!b1 && w1t && nat_fuse_dx()) {   // and dl1 in the same launch (k_nat_dx32); NAT_C2X then empty
         hipLaunchKernelGGL(k_nat_dx32, dim3((unsigned)B), dim3(256), 0, s, bws + p.dl3, l2, l1,
                            w1t + A3C_NAT_W3X_OFF / 2, w1t + A3C_NAT_W2X_OFF / 2, bws + p.dl2, bws + p.dl1);
         A3C_CHECK(hipGetLastError());
@@ -1624,22 +1855,26 @@ int a3c_nat_pass_launch(int pass, const NetLayout& L, const float* P, const Stat
       }
       a.X = l2; a.dY = bws + p.dl3; a.Wt = P + L.off[N_L3W]; a.Y = bws + p.dl2;
       a.M = (int)(B * NT2_P); a.N = NT2_N; a.K = 3 * 3 * NT3_N;
+      if (b1) return nat_go_bf<NG_DX, 3, 64, 1, 1>(a, 1, s, nat_bf1(NAT_C3X), nat_pf2(NAT_C3X));
       return nat_bf(NAT_C3X) ? nat_go_bf<NG_DX, 3, 64, 3>(a, 1, s, nat_bf1(NAT_C3X), nat_pf2(NAT_C3X))
                            : nat_go<NG_DX, 3, 64>(a, 1, s);
     case NAT_C2W:
       a.X = l1; a.dY = bws + p.dl2; a.slab = bws + p.s2; a.colsum = bws + p.c2;
       a.M = NT_K2; a.N = NT2_N; a.K = (int)(B * NT2_P); a.kchunk = p.kc2;
+      if (b1) return nat_go_bf<NG_DW, 2, 64, 1, 1>(a, (unsigned)p.ns2, s, nat_bf1(NAT_C2W), nat_pf2(NAT_C2W));
       return nat_bf(NAT_C2W) ? nat_go_bf<NG_DW, 2, 64, 3>(a, (unsigned)p.ns2, s, nat_bf1(NAT_C2W), nat_pf2(NAT_C2W))
                            : nat_go<NG_DW, 2, 64>(a, (unsigned)p.ns2, s);
     case NAT_C2X:     // dl1 = col2im(dl2 W2^T) * (l1 > 0), per stride-2 parity class
-      if (w1t && nat_fuse_dx()) return 0;
+      if (!b1 && w1t && nat_fuse_dx()) return 0;
       a.X = l1; a.dY = bws + p.dl2; a.Wt = P + L.off[N_L2W]; a.Y = bws + p.dl1;
       a.M = (int)(B * (NT1_O / 2) * (NT1_O / 2)); a.N = NT1_N; a.K = 2 * 2 * NT2_N;
+      if (b1) return nat_go_bf<NG_DX, 2, 32, 1, 1>(a, 4, s, nat_bf1(NAT_C2X), nat_pf2(NAT_C2X));
       return nat_bf(NAT_C2X) ? nat_go_bf<NG_DX, 2, 32, 3>(a, 4, s, nat_bf1(NAT_C2X), nat_pf2(NAT_C2X))
                            : nat_go<NG_DX, 2, 32>(a, 4, s);
     case NAT_C1W:     // dW1 (+ db1) from the u8 planes (the input needs no gradient)
       a.sa = sa; a.dY = bws + p.dl1; a.slab = bws + p.s1; a.colsum = bws + p.c1;
       a.M = NT_K1; a.N = NT1_N; a.K = (int)(B * NT1_P); a.kchunk = p.kc1;
+      if (b1) return nat_go_bf<NG_DW1, 1, 32, 1, 1>(a, (unsigned)p.ns1, s, nat_bf1(NAT_C1W), nat_pf2(NAT_C1W));
       return nat_bf(NAT_C1W) ? nat_go_bf<NG_DW1, 1, 32, 1>(a, (unsigned)p.ns1, s, nat_bf1(NAT_C1W), nat_pf2(NAT_C1W))
                            : nat_go<NG_DW1, 1, 32>(a, (unsigned)p.ns1, s);
     default:
@@ -1655,10 +1890,17 @@ __global__ void k_nat_prep(const int64_t* __restrict__ tau_src, int64_t* __restr
 }
 static int nat_w1_terms_launch(const NetLayout& L, const float* P, uint16_t* w1t, hipStream_t s) {
   // (the forward forms for k_nat_conv23, the dX forms only for k_nat_dx32)
+  if (L.prec == A3C_PREC_BF16) {   // rn(W) alone: the three forward forms (the dX tiles round W at their LDS store)
+    const int n1 = NT1_N * NT_K1 + NT2_N * NT_K2 + NT3_N * NT_K3;
+    hipLaunchKernelGGL(k_nat_w_terms<1>, dim3((n1 + 255) / 256), dim3(256), 0, s, P + L.off[N_L1W], P + L.off[N_L2W],
+                       P + L.off[N_L3W], w1t, 1);
+    A3C_CHECK(hipGetLastError());
+    return 0;
+  }
   const int all = nat_fuse23() || nat_fuse_dx() ? 1 : 0;
   const int n = NT1_N * NT_K1 + (all ? NT2_N * NT_K2 + NT3_N * NT_K3 : 0) +
                 (nat_fuse_dx() ? NT1_N * NT_X2 + NT2_N * NT_K3 : 0);
-  hipLaunchKernelGGL(k_nat_w_terms, dim3((n + 255) / 256), dim3(256), 0, s, P + L.off[N_L1W], P + L.off[N_L2W],
+  hipLaunchKernelGGL(k_nat_w_terms<3>, dim3((n + 255) / 256), dim3(256), 0, s, P + L.off[N_L1W], P + L.off[N_L2W],
                      P + L.off[N_L3W], w1t, all);
   A3C_CHECK(hipGetLastError());
   return 0;
@@ -1887,11 +2129,19 @@ extern "C" int a3c_nature_workspace_bytes(const a3c_net_desc* net, int64_t B, in
   return 0;
 }
 
-extern "C" int a3c_nature_forward(const a3c_net_desc* net, const float* params, const uint8_t* states, int64_t B,
-                                  float* l1, float* l2, float* l3, float* l4, float* z, void* workspace,
-                                  void* stream) {
+static int nat_prec_ok(int precision, const char* what) {
+  if (precision != A3C_PREC_FP32 && precision != A3C_PREC_BF16)
+    return a3c_set_error(A3C_ERR_INVALID, what, "precision: A3C_PREC_FP32 or A3C_PREC_BF16");
+  return 0;
+}
+
+extern "C" int a3c_nature_forward_prec(const a3c_net_desc* net, const float* params, const uint8_t* states, int64_t B,
+                                       float* l1, float* l2, float* l3, float* l4, float* z, void* workspace,
+                                       void* stream, int precision) {
   NetLayout L;
+  if (int rc = nat_prec_ok(precision, "a3c_nature_forward")) return rc;
   if (int rc = nat_layout(net, &L, "a3c_nature_forward")) return rc;
+  L.prec = precision;
   if (!params || !states || !l1 || !l2 || !l3 || !l4 || !z || !workspace || B < 0 || B * NT1_P > 0x7fffffffLL ||
       (((uintptr_t)params | (uintptr_t)l1 | (uintptr_t)l2 | (uintptr_t)l3 | (uintptr_t)l4) & 15))
     return a3c_set_error(A3C_ERR_INVALID, "a3c_nature_forward", "bad argument");
@@ -1904,14 +2154,21 @@ extern "C" int a3c_nature_forward(const a3c_net_desc* net, const float* params, 
   a.act_l1 = l1; a.act_l2 = l2; a.act_l3 = l3; a.act_l4 = l4; a.nat_ws = nat_align(workspace);
   return a3c_nat_forward_launch(L, a, (hipStream_t)stream, LAUNCH_ALONE);
 }
+extern "C" int a3c_nature_forward(const a3c_net_desc* net, const float* params, const uint8_t* states, int64_t B,
+                                  float* l1, float* l2, float* l3, float* l4, float* z, void* workspace,
+                                  void* stream) {
+  return a3c_nature_forward_prec(net, params, states, B, l1, l2, l3, l4, z, workspace, stream, A3C_PREC_FP32);
+}
 
-extern "C" int a3c_nature_loss_backward(const a3c_net_desc* net, const float* params, const uint8_t* states,
-                                        int64_t B, const float* l1, const float* l2, const float* l3, const float* l4,
-                                        const float* z, const int32_t* actions, const float* target, float beta,
-                                        int literal_adv, float* grads, float* loss_out, void* workspace,
-                                        void* stream) {
+extern "C" int a3c_nature_loss_backward_prec(const a3c_net_desc* net, const float* params, const uint8_t* states,
+                                             int64_t B, const float* l1, const float* l2, const float* l3,
+                                             const float* l4, const float* z, const int32_t* actions,
+                                             const float* target, float beta, int literal_adv, float* grads,
+                                             float* loss_out, void* workspace, void* stream, int precision) {
   NetLayout L;
+  if (int rc = nat_prec_ok(precision, "a3c_nature_loss_backward")) return rc;
   if (int rc = nat_layout(net, &L, "a3c_nature_loss_backward")) return rc;
+  L.prec = precision;
   if (!params || !states || !l1 || !l2 || !l3 || !l4 || !z || !actions || !target || !grads || !workspace ||
       B <= 0 || B * NT1_P > 0x7fffffffLL || (((uintptr_t)grads | (uintptr_t)l3 | (uintptr_t)l4) & 15))
     return a3c_set_error(A3C_ERR_INVALID, "a3c_nature_loss_backward", "bad argument");
@@ -1920,6 +2177,14 @@ extern "C" int a3c_nature_loss_backward(const a3c_net_desc* net, const float* pa
   a.act_l1 = l1; a.act_l2 = l2; a.act_l3 = l3; a.act_l4 = l4; a.z = z; a.actions = actions; a.target = target;
   a.beta = beta; a.literal = literal_adv; a.grads = grads; a.loss_out = loss_out; a.ws = nat_align(workspace);
   return a3c_nat_backward_launch(L, a, (hipStream_t)stream);
+}
+extern "C" int a3c_nature_loss_backward(const a3c_net_desc* net, const float* params, const uint8_t* states,
+                                        int64_t B, const float* l1, const float* l2, const float* l3, const float* l4,
+                                        const float* z, const int32_t* actions, const float* target, float beta,
+                                        int literal_adv, float* grads, float* loss_out, void* workspace,
+                                        void* stream) {
+  return a3c_nature_loss_backward_prec(net, params, states, B, l1, l2, l3, l4, z, actions, target, beta, literal_adv,
+                                       grads, loss_out, workspace, stream, A3C_PREC_FP32);
 }
 
 // Catch: k_nat_head's A3C_GAME_CATCH instantiation, emitted behind every other kernel

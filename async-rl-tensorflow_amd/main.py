@@ -13,6 +13,8 @@ accepted but the TF ps/worker cluster is replaced by one process per GPU under t
   python main.py --mode engine --algo q --sarsa true --n_step 5 --env_name Catch-v0     Sarsa (--q_nstep true: n-step)
   python main.py --mode engine --algo q --q_lambda 0.8 --n_step 5 --env_name Catch-v0    lambda-return targets: Q(lambda), with
                  --sarsa true Sarsa(lambda), with --double_q true its double-Q form
+  python main.py --mode engine --dqn_type nature --precision bf16   the nature trunk's convolutions on single bf16 operands,
+                 fp32 accumulation, parameters and activations
   python main.py --mode engine --algo q --optimizer adam --env_name Catch-v0             shared Adam instead of RMSProp
   python main.py --mode engine --lstm true --env_name CatchMemory-v0   Catch that only a head with memory learns
   python main.py --mode engine --lstm true --env_name CatchMemory-v0 --first_screen true   ... with each episode's first
@@ -119,6 +121,10 @@ def parse_flags(argv=None):
   p.add_argument('--dqn_type', choices=['nips', 'nature'], default='nips',
                  help="conv trunk of network.py:30-50 (Network(DQN_type=...)): nips (fused kernels) or nature "
                       "(implicit-GEMM kernels, nature.hip; --algo a3c)")
+  p.add_argument('--precision', default='fp32',
+                 help="engine mode, --dqn_type nature: fp32 (every convolution operand as three bf16 terms, fp32-class "
+                      "results) or bf16 (mixed precision: one bf16 term per operand, fp32 accumulation, parameters and "
+                      "saved activations; DESIGN §4n)")
   # evaluation: --mode engine --is_train false (Agent.play, agent.py:351-391)
   p.add_argument('--n_episode', type=int, default=100, help='play: episodes (agent.py:351)')
   p.add_argument('--play_steps', type=int, default=10000, help="play: cap on an episode's env steps (agent.py:351 n_step)")
@@ -169,6 +175,12 @@ def engine_options(flags):
     if flags.q_nstep:
       raise ValueError('--q_lambda with --q_nstep: the n-step engine is lambda = 1 with the target forward of s_n '
                        'alone (DESIGN §4m); give one of them')
+  precision = getattr(flags, 'precision', 'fp32')
+  if precision not in ('fp32', 'bf16'):
+    raise ValueError("--precision must be fp32 or bf16 (got %r)" % (precision,))
+  if precision == 'bf16' and flags.dqn_type != 'nature':
+    raise ValueError('--precision bf16 is the compute mode of the nature trunk (DESIGN §4n; the nips rollout kernel '
+                     'has none): use it with --dqn_type nature')
   first_screen = bool(getattr(flags, 'first_screen', False))
   if first_screen and game_kind(flags.env_name) != 'catch':
     raise ValueError('--first_screen is an option of the device game Catch (--env_name Catch-v0 or CatchMemory-v0, '
@@ -194,6 +206,8 @@ def engine_options(flags):
     kw['dqn_type'] = 'nature'
   if first_screen:
     kw['first_screen'] = True
+  if precision != 'fp32':
+    kw['precision'] = precision
   return kw
 
 
@@ -480,6 +494,9 @@ def main(argv=None):
     raise ValueError('--sarsa is an engine option: --mode agent is the per-step Q-learning loop (max targets)')
   if flags.mode == 'agent' and flags.q_lambda is not None:
     raise ValueError('--q_lambda is an engine option: --mode agent is the per-step Q-learning loop (one-step targets)')
+  if flags.mode == 'agent' and flags.precision != 'fp32':
+    raise ValueError('--precision is an engine option (the nature trunk of --mode engine, DESIGN §4n): --mode agent '
+                     'is the per-op loop in fp32')
   if flags.mode == 'agent' and flags.first_screen:
     raise ValueError('--first_screen is an engine option: --mode agent is the reference loop (agent.py:59-67) as it stands')
   random.seed(flags.random_seed)

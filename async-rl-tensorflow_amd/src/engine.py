@@ -57,7 +57,7 @@ class Engine:
     def __init__(self, num_envs=256, n_step=5, action_size=6, algo='a3c', start_lives=0, num_frames=None,
                  seed=123, env_id_base=0, world_size=1, use_graph=False, overlap=False, lstm=False,
                  external_env=False, dqn_type='nips', game='synth', catch_rules=None, first_screen=None, q_lambda=None,
-                 **overrides):
+                 precision='fp32', **overrides):
         """game: 'synth' (the synthetic Atari stand-in) or 'catch' (Catch-v0, DESIGN §4g: action_size 3,
         start_lives 0, device envs, raw RGB pool; random_start is ignored).  num_frames=None: 1024
         frames (Catch needs its 640: a smaller explicit value is rejected by the library).
@@ -79,7 +79,12 @@ class Engine:
         call is made): a3c_engine_set_q_lambda right after the create -- lambda-return targets over the
         rollout, Q(lambda), with double_q its double-Q form, with sarsa=1 Sarsa(lambda); 0 is the one-step
         target and 1 the n-step return; kept as ``q_lambda``.  Not in the saved state: a resumed run gives it
-        again."""
+        again.
+        precision='fp32' | 'bf16' ('fp32': no call is made): a3c_engine_set_precision right after
+        the create -- 'bf16' (dqn_type 'nature' only) runs every convolution pass on one bf16 term per operand
+        with fp32 accumulation; parameters, optimizer slots and saved activations stay fp32; kept as
+        ``precision``.  Not in the saved state: a resumed run gives it again."""
+        self.precision = self._check_precision(precision, str(dqn_type).lower())
         self.q_lambda = self._check_q_lambda(q_lambda, algo, overrides.get('q_nstep', 0))
         if first_screen is not None and game != 'catch':
             raise ValueError('first_screen is an option of game catch, not of %r' % (game,))
@@ -158,6 +163,8 @@ class Engine:
             check(lib().a3c_engine_set_first_screen(h, int(bool(first_screen))), 'a3c_engine_set_first_screen')
         if self.q_lambda is not None:
             check(lib().a3c_engine_set_q_lambda(h, 1, self.q_lambda), 'a3c_engine_set_q_lambda')
+        if self.precision != 'fp32':
+            check(lib().a3c_engine_set_precision(h, _lib.PRECISIONS[self.precision]), 'a3c_engine_set_precision')
         b = _lib.EngineBuffers()
         check(lib().a3c_engine_get_buffers(h, ctypes.byref(b)), 'a3c_engine_get_buffers')
         self._b = b
@@ -215,6 +222,19 @@ class Engine:
         check(lib().a3c_engine_set_q_lambda(self._h, int(value is not None), 0.0 if value is None else value),
               'a3c_engine_set_q_lambda')
         self.q_lambda = value
+
+    @staticmethod
+    def _check_precision(value, dqn_type):
+        _lib.precision_code(value)
+        if value == 'bf16' and dqn_type != 'nature':
+            raise ValueError("precision 'bf16' is the nature trunk's compute mode (dqn_type %r has none)" % (dqn_type,))
+        return value
+
+    def set_precision(self, value):
+        """a3c_engine_set_precision between iterations: no reset, the next rollout and gradient follow it."""
+        value = self._check_precision(value, self.dqn_type)
+        check(lib().a3c_engine_set_precision(self._h, _lib.PRECISIONS[value]), 'a3c_engine_set_precision')
+        self.precision = value
 
     def _slot_views(self, k):
         b = _lib.EngineBuffers()

@@ -172,26 +172,35 @@ class NatureNet:
               'a3c_nature_workspace_bytes')
         return torch.empty(int(n.value), dtype=torch.uint8, device=device)
 
-    def forward(self, params, states, workspace=None, z=None):
+    def forward(self, params, states, workspace=None, z=None, precision=None):
         """states [B,4,84,84] u8 (oldest frame first).  Returns dict z/l1/l2/l3/l4.
-        z: caller-owned head rows [>= B, zs] to write into (rows past B are left alone)."""
+        z: caller-owned head rows [>= B, zs] to write into (rows past B are left alone).
+        precision: None (a3c_nature_forward) or 'fp32' | 'bf16' (a3c_nature_forward_prec)."""
         _dev(params, torch.float32, 'params')
         _dev(states, torch.uint8, 'states')
         B = int(states.shape[0])
         dev = states.device
+        prec = None if precision is None else _lib.precision_code(precision)
         out = dict(l1=torch.empty((B, 12800), dtype=torch.float32, device=dev),
                    l2=torch.empty((B, 5184), dtype=torch.float32, device=dev),
                    l3=torch.empty((B, 3136), dtype=torch.float32, device=dev),
                    l4=torch.empty((B, 512), dtype=torch.float32, device=dev),
                    z=_z_rows(z, B, self.zs, dev))
         ws = workspace if workspace is not None else self.workspace(B, dev)
+        if prec is not None:
+            check(lib().a3c_nature_forward_prec(ctypes.byref(self.desc), ptr(params), ptr(states), B, ptr(out['l1']),
+                                                ptr(out['l2']), ptr(out['l3']), ptr(out['l4']), ptr(out['z']), ptr(ws),
+                                                stream_handle(), prec), 'a3c_nature_forward_prec')
+            return out
         check(lib().a3c_nature_forward(ctypes.byref(self.desc), ptr(params), ptr(states), B, ptr(out['l1']),
                                        ptr(out['l2']), ptr(out['l3']), ptr(out['l4']), ptr(out['z']), ptr(ws),
                                        stream_handle()), 'a3c_nature_forward')
         return out
 
     def loss_backward(self, params, states, fwd, actions, target, beta=0.01, literal_adv=False, grads=None,
-                      workspace=None):
+                      workspace=None, precision=None):
+        """precision: None (a3c_nature_loss_backward) or 'fp32' | 'bf16' (a3c_nature_loss_backward_prec)."""
+        prec = None if precision is None else _lib.precision_code(precision)
         _dev(actions, torch.int32, 'actions')
         _dev(target, torch.float32, 'target')
         B = int(states.shape[0])
@@ -200,6 +209,13 @@ class NatureNet:
             grads = torch.zeros(self.total, dtype=torch.float32, device=dev)
         loss = torch.zeros(4, dtype=torch.float32, device=dev)
         ws = workspace if workspace is not None else self.workspace(B, dev)
+        if prec is not None:
+            check(lib().a3c_nature_loss_backward_prec(ctypes.byref(self.desc), ptr(params), ptr(states), B,
+                                                      ptr(fwd['l1']), ptr(fwd['l2']), ptr(fwd['l3']), ptr(fwd['l4']),
+                                                      ptr(fwd['z']), ptr(actions), ptr(target), float(beta),
+                                                      1 if literal_adv else 0, ptr(grads), ptr(loss), ptr(ws),
+                                                      stream_handle(), prec), 'a3c_nature_loss_backward_prec')
+            return grads, loss
         check(lib().a3c_nature_loss_backward(ctypes.byref(self.desc), ptr(params), ptr(states), B, ptr(fwd['l1']),
                                              ptr(fwd['l2']), ptr(fwd['l3']), ptr(fwd['l4']), ptr(fwd['z']),
                                              ptr(actions), ptr(target), float(beta), 1 if literal_adv else 0,

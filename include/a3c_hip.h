@@ -93,6 +93,35 @@ int a3c_nature_loss_backward(const a3c_net_desc* net, const float* params, const
                              const float* l1, const float* l2, const float* l3, const float* l4, const float* z,
                              const int32_t* actions, const float* target, float beta, int literal_adv,
                              float* grads, float* loss_out, void* workspace, void* stream);
+/* The nature trunk's convolution compute mode.  "rn" is round-to-nearest-even to bf16.
+ *   A3C_PREC_FP32  every convolution operand as three bf16 terms: fp32-class results (the default, and
+ *                  what the two entries above run)
+ *   A3C_PREC_BF16  mixed precision: fp32 parameters and saved activations, each convolution pass on one
+ *                  bf16 term per operand with fp32 accumulation --
+ *                    forward   l1 = relu(pixel . rn(W1) / 255 + b1) (a u8 pixel is exact in bf16),
+ *                              l2 = relu(rn(l1) . rn(W2) + b2), l3 = relu(rn(l2) . rn(W3) + b3), bias and ReLU
+ *                              in fp32, l1 / l2 / l3 stored fp32: one launch, one workgroup per state
+ *                    backward  dW = rn(activation) . rn(dY) (conv1: pixel . rn(dY)), dX = rn(dY) . rn(W),
+ *                              each pass rounding the fp32 values it reads; ReLU masks, bias column
+ *                              sums (of the fp32 dY), slab counts and fold order as in FP32
+ *                  The fc, the heads, the loss and the optimizer are the FP32 mode's. */
+#define A3C_PREC_FP32 0
+#define A3C_PREC_BF16 1
+/* a3c_nature_forward in the given mode: the same arguments, outputs and workspace; A3C_PREC_FP32
+ * launches exactly what a3c_nature_forward launches.  A3C_ERR_INVALID, in this order: a precision
+ * that is neither constant, then a3c_nature_forward's own checks (the description, the arguments). */
+int a3c_nature_forward_prec(const a3c_net_desc* net, const float* params, const uint8_t* states, int64_t B,
+                            float* l1, float* l2, float* l3, float* l4, float* z, void* workspace, void* stream,
+                            int precision);
+/* a3c_nature_loss_backward in the given mode, on whatever activations it is given (for the mode's
+ * own gradients: those of a3c_nature_forward_prec in the same mode).  A3C_PREC_FP32 launches exactly
+ * what a3c_nature_loss_backward launches.  A3C_ERR_INVALID, in this order: a precision that is neither
+ * constant, then a3c_nature_loss_backward's own checks. */
+int a3c_nature_loss_backward_prec(const a3c_net_desc* net, const float* params, const uint8_t* states, int64_t B,
+                                  const float* l1, const float* l2, const float* l3, const float* l4,
+                                  const float* z, const int32_t* actions, const float* target, float beta,
+                                  int literal_adv, float* grads, float* loss_out, void* workspace, void* stream,
+                                  int precision);
 
 /* ----------------------------------------------------------------------------
  * K1  Environment.screen (environment.py:49-53): fp64 luminance truncated to u8, then
@@ -637,6 +666,19 @@ int a3c_engine_set_first_screen(a3c_engine* eng, int on);
  * not in the checkpoint's state (a resumed run gives it again), and play does not read it.
  * python async-rl-tensorflow_amd/main.py --mode engine --algo q --q_lambda 0.8 --env_name Catch-v0 */
 int a3c_engine_set_q_lambda(a3c_engine* eng, int on, double lambda);
+/* precision: the convolution compute mode of a nature-trunk engine, A3C_PREC_FP32 (the
+ * default: every launch is what it is without this call) or A3C_PREC_BF16 (the definition stands at
+ * the constants).  In BF16 the weight preparation at each rollout's start writes rn(W) alone, the
+ * rollout steps, the bootstrap state and play run the one-term forward kernel, and the gradient's five
+ * convolution passes run the one-term tiles; parameters, optimizer slots and saved activations stay
+ * fp32.  A setter, as the four above: no reset, the next rollout and the next gradient follow it
+ * (overlap: a rollout already made is back-propagated in the new mode); it drops captured graphs.
+ * A3C_ERR_INVALID, before anything touches the device and in this order: a precision that is neither
+ * constant, eng NULL, A3C_PREC_BF16 on a NIPS-trunk engine (its fused rollout kernel has no such mode).
+ * A3C_ERR_STATE: a computed gradient not yet applied.  A hyperparameter: not in the checkpoint's state
+ * (a resumed run gives it again); a3c_engine_play follows it (it runs the same forward launch).
+ * python async-rl-tensorflow_amd/main.py --mode engine --dqn_type nature --precision bf16 */
+int a3c_engine_set_precision(a3c_engine* eng, int precision);
 /* fill the frame pool, reset the envs (new_random_game, environment.py:35-40), fill each
  * history with 4 copies of the first screen (agent.py:37-38) and initialise params
  * from host memory (nullable -> keep), rms slot = 1, mom = 0 (Adam: m = v = 0, products = 1). */
