@@ -5,7 +5,7 @@ B = n * E alone; the functions here restate those choices line for line from the
 tests/test_plan_cpu.py ties them to the library through the workspace sizes it reports (every
 plan's `total` is what a3c_workspace_bytes / a3c_nature_workspace_bytes /
 a3c_lstm_workspace_bytes size).  The GPU case tables (tests/test_gpu_batch_edges.py,
-tests/test_gpu_lstm.py) assert from these functions that a batch reaches the fork it names, so
+tests/test_gpu_lstm.py, tests/test_gpu_nat_bf16.py) assert from these functions that a batch reaches the fork it names, so
 moving a plan constant fails a test instead of silently un-testing a fork.
 
 Sources (async-rl-tensorflow_amd/csrc):
@@ -15,7 +15,7 @@ Sources (async-rl-tensorflow_amd/csrc):
   net_bwd.h  CB_SLAB
   net_bwd.hip  a3c_bwd_plan; k_conv_bwd's sample range; k_slab_group's slab range
   nature.h   the nature trunk's geometry, A3C_NAT_PREP_BYTES
-  nature.hip   dw_split, nat_plan, fc_split, nat_fwd_slab_floats, a3c_nat_fwd_ws_floats
+  nature.hip   dw_split, nat_plan, fc_split, nat_fwd_slab_floats, a3c_nat_fwd_ws_floats; k_nat_gemm_bf's K slices
   lstm.hip   lstm_ws
 The plans' A/B environment knobs (A3C_CB_NWG, A3C_NAT_DW_WGS*, A3C_NAT_FC_SPLIT) are taken at
 their defaults."""
@@ -60,10 +60,11 @@ NAT_W3T_OFF = NAT_W2T_OFF + 3 * NT2_N * NT_K2 * 2
 NAT_W2X_OFF = NAT_W3T_OFF + 3 * NT3_N * NT_K3 * 2
 NAT_W3X_OFF = NAT_W2X_OFF + 3 * NT1_N * NT_X2 * 2
 NAT_PREP_BYTES = NAT_W3X_OFF + 3 * NT2_N * NT_K3 * 2
-NAT_GROUPS = 8                           # nature.hip:1383
-NAT_DW_WGS = (768, 2048, 768)            # nature.hip:1408-1410
-NAT_DW_MTILES = (2, 8, 9)                # nature.hip:1411-1413
-NAT_FWD_SPLIT_MAX = 4                    # nature.hip:1446
+NAT_GROUPS = 8                           # nature.hip:1600
+NAT_DW_WGS = (768, 2048, 768)            # nature.hip:1625-1627
+NAT_DW_MTILES = (2, 8, 9)                # nature.hip:1628-1630
+NAT_FWD_SPLIT_MAX = 4                    # nature.hip:1663
+NAT_BK = 32                              # nature.hip:405 k_nat_gemm_bf: BK, the rows of one K slice
 
 
 def cdiv(a, b):
@@ -151,7 +152,7 @@ def workspace_bytes(A, algo, B):
 
 
 def dw_split(R, mtiles, target):
-    """nature.hip:1389-1397 dw_split -> (ns, kc)."""
+    """nature.hip:1606-1614 dw_split -> (ns, kc)."""
     want = max(target // mtiles, 1)
     per = cdiv(R, want)
     per = max(cdiv(per, 32) * 32, 32)
@@ -162,7 +163,7 @@ NatPlan = namedtuple('NatPlan', 'B head_split ns kc off regions total')
 
 
 def nat_plan(A, B):
-    """nature.hip:1398-1436 nat_plan; ns / kc are the (conv1, conv2, conv3) triples."""
+    """nature.hip:1615-1653 nat_plan; ns / kc are the (conv1, conv2, conv3) triples."""
     z = zs('a3c', A)
     head_split = gemm_effective_split(B, gemm_plan_split(NT_FC, z, B, 128))
     sp = [dw_split(B * P, m, t) for P, m, t in zip((NT1_P, NT2_P, NT3_P), NAT_DW_MTILES, NAT_DW_WGS)]
@@ -181,13 +182,29 @@ def nat_plan(A, B):
     return NatPlan(B, head_split, ns, kc, off, take.regions, take.o)
 
 
+NatDwSlices = namedtuple('NatDwSlices', 'kc slices last_rows last_slice_rows')
+
+
+def nat_dw_slices(A, B):
+    """k_nat_gemm_bf's K loop over a dW chunk (nature.hip:432-433 kbeg / kend, :653-707 the three loop forms), per
+    (conv1, conv2, conv3) pass: the slices of NAT_BK rows a full chunk holds (kc // NAT_BK: dw_split makes kc whole
+    slices), the rows of the last chunk (kend stops at K = B * P) and the rows of that chunk's last slice (fewer
+    than NAT_BK: the loads' `r >= kend` leaves the rest of the slice zero)."""
+    p = nat_plan(A, B)
+    out = []
+    for rows, ns, kc in zip((B * NT1_P, B * NT2_P, B * NT3_P), p.ns, p.kc):
+        last = rows - (ns - 1) * kc
+        out.append(NatDwSlices(kc, kc // NAT_BK, last, last % NAT_BK or NAT_BK))
+    return tuple(out)
+
+
 def nat_fc_split(B):
-    """nature.hip:1438-1441 fc_split: the forward fc GEMM (M = B, N = 512, K = 3136)."""
+    """nature.hip:1655-1658 fc_split: the forward fc GEMM (M = B, N = 512, K = 3136)."""
     return gemm_effective_split(NT_FLAT, gemm_plan_split(B, NT_FC, NT_FLAT, 512))
 
 
 def nat_fwd_ws_floats(B):
-    """nature.hip:1465-1471 nat_fwd_slab_floats + the prepared weights."""
+    """nature.hip:1682-1688 nat_fwd_slab_floats + the prepared weights."""
     sp = nat_fc_split(B)
     fc = sp * B * NT_FC if sp > 1 else 0
     cv = NAT_FWD_SPLIT_MAX * B * max(NT2_P * NT2_N, NT3_P * NT3_N)
@@ -195,7 +212,7 @@ def nat_fwd_ws_floats(B):
 
 
 def nature_workspace_bytes(A, B):
-    """nature.hip:1881-1888 a3c_nature_workspace_bytes."""
+    """nature.hip:2123-2130 a3c_nature_workspace_bytes."""
     return max(nat_fwd_ws_floats(B), nat_plan(A, B).total) * 4 + 256
 
 

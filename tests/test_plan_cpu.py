@@ -120,6 +120,35 @@ def test_nature_plan_invariants(A):
         regions_disjoint(p.regions, p.total)
 
 
+def test_nature_dw_slices():
+    """nat_dw_slices against the kernel's slice constant, the plan it rests on (tied above through the slab counts
+    ns, which size s1..s3 and c1..c3) and the batches tests/test_gpu_nat_bf16.py names."""
+    src = open(os.path.join(ROOT, 'async-rl-tensorflow_amd', 'csrc', 'nature.hip')).read()
+    body = src[src.index('__global__ void __launch_bounds__(256) k_nat_gemm_bf(NatGemm a) {'):]
+    assert f'BK = {P.NAT_BK},' in body[:body.index('\n', body.index('constexpr int BM'))]
+    assert 'per = (per + 31) / 32 * 32;               // whole K slices' in src and P.NAT_BK == 32
+    for B in range(1, B_MAX + 1):
+        p = P.nat_plan(6, B)
+        for s, ns, kc, rows in zip(P.nat_dw_slices(6, B), p.ns, p.kc, (B * P.NT1_P, B * P.NT2_P, B * P.NT3_P)):
+            # whole slices in a full chunk; the last chunk ends the reduction; its last slice is the only short one
+            assert s.kc == kc == s.slices * P.NAT_BK and s.slices >= 1, B
+            assert 1 <= s.last_rows <= kc and (ns - 1) * kc + s.last_rows == rows, B
+            assert 1 <= s.last_slice_rows <= P.NAT_BK and (s.last_rows - s.last_slice_rows) % P.NAT_BK == 0, B
+    # one slice per dW workgroup up to B = 30: what the reference-checked bf16 cases reached before
+    assert all(s.slices == 1 for B in range(1, 31) for s in P.nat_dw_slices(6, B))
+    assert [s.slices for s in P.nat_dw_slices(6, 30)] == [1, 1, 1] and P.nat_dw_slices(6, 31)[0].slices == 2
+    table = {31: ((2, 1, 1), (48, 15, 15), (16, 15, 15)),
+             103: ((4, 2, 2), (112, 23, 55), (16, 23, 23)),
+             123: ((5, 2, 3), (80, 43, 75), (16, 11, 11))}
+    for B, want in table.items():
+        s = P.nat_dw_slices(6, B)
+        assert (tuple(x.slices for x in s), tuple(x.last_rows for x in s), tuple(x.last_slice_rows for x in s)) == want
+    # the first batch with four and with five conv1 slices, and with two conv2 slices
+    assert min(B for B in range(1, 200) if P.nat_dw_slices(6, B)[0].slices == 4) == 93
+    assert min(B for B in range(1, 200) if P.nat_dw_slices(6, B)[0].slices == 5) == 123
+    assert min(B for B in range(1, 200) if P.nat_dw_slices(6, B)[1].slices == 2) == 102
+
+
 def test_lstm_plan_invariants():
     for n in range(1, 9):
         for E in range(1, 601):
