@@ -2294,9 +2294,7 @@ extern "C" int a3c_engine_time_kernel(a3c_engine* e, int kernel, int iters, void
   if (e->nat) {   // one pass of the nature trunk: forward over E states, backward passes over n*E samples
     const int pass = kernel - A3C_KER_NAT_C1F;
     const bool fwd = pass <= NAT_FCF;
-    const bool b1 = L.prec == A3C_PREC_BF16;   // (its forward is one launch under NAT_C2F, its dX passes two)
-    if ((pass == NAT_C3F && (b1 || a3c_nat_conv23_fused())) || (pass == NAT_C1F && (b1 || a3c_nat_conv123_fused())) ||
-        (pass == NAT_C2X && !b1 && a3c_nat_dx_fused()))
+    if (pass == NAT_C3F || pass == NAT_C1F)
       return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_time_kernel",
                            "this pass runs inside another pass's launch (k_nat_conv23 under A3C_KER_NAT_C2F, k_nat_dx32 under A3C_KER_NAT_C3X)");
     if (!fwd && !e->grad_ready)

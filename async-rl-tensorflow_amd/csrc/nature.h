@@ -32,9 +32,9 @@ inline int64_t nat_act_floats() { return (int64_t)NT_A1 + NT_A2 + NT_FLAT + NT_F
 // forward of B states s_{tau0 + b / E} (sa) with parameters P.  Activations [B][...] NHWC:
 // l1 [B][12800], l2 [B][5184], l3 [B][3136] (the (h,w,c) flatten of network.py's linear), l4 [B][512];
 // z [B][zs] (logits, value); sel.mode >= 0: action draw + fused env act (as the NIPS head kernels).
-// a.nat_ws: a3c_nat_fwd_ws_floats(B) floats (split-K slabs; with a.prep null, also the prepared weight
-// terms, made there first).  a.prep: the prepared block a3c_nat_prep_launch made from P (the engine's
-// rollouts: conv1's terms at its start, then the conv2 / conv3 forms, A3C_NAT_*_OFF).
+// a.nat_ws: a3c_nat_fwd_ws_floats(B) floats (the fc's split-K slabs; with a.prep null, also the
+// prepared weight terms, made there first).  a.prep: the prepared block a3c_nat_prep_launch made from P
+// (the engine's rollouts: conv1's terms at its start, then conv2's and conv3's, A3C_NAT_*_OFF).
 // The nature body of a3c_forward_launch (net.h); m: the step tail's head + screen variant.
 int64_t a3c_nat_fwd_ws_floats(int64_t B);
 int a3c_nat_forward_launch(const NetLayout& L, const FwdArgs& a, hipStream_t s, const LaunchMode& m);
@@ -51,14 +51,11 @@ int a3c_nat_backward_launch(const NetLayout& L, const BwdArgs& a, hipStream_t s)
 int a3c_nat_fused_tab(const NetLayout& L, TensorTab* tt);
 // the single launches behind both (a3c_engine_time_kernel): forward passes over B states
 // (fws: the fc's split-K slabs), backward passes over B samples on the plan's buffers in bws
-// (valid after a backward of the same B has filled them); w1t: the prepared block (null: the
-// per-layer forms of the passes that need none)
+// (valid after a backward of the same B has filled them); w1t: the prepared block (the conv forward
+// reads it: null there is A3C_ERR_INVALID; the backward passes do not).
+// The three conv forwards run as one launch under NAT_C2F (k_nat_conv23, bf16 mode:
+// k_nat_conv123_b1); NAT_C1F and NAT_C3F launch nothing.
 enum { NAT_C1F = 0, NAT_C2F, NAT_C3F, NAT_FCF, NAT_C3W, NAT_C3X, NAT_C2W, NAT_C2X, NAT_C1W };
-enum { NAT_FCW = NAT_C1W + 1, NAT_FCX };
-// conv2 + conv3 forward run as one launch (k_nat_conv23, under NAT_C2F; NAT_C3F launches nothing)
-bool a3c_nat_conv23_fused();
-bool a3c_nat_conv123_fused();   // conv1 as well (NAT_C1F launches nothing)
-bool a3c_nat_dx_fused();        // conv3 dX + conv2 dX as one launch under NAT_C3X (NAT_C2X launches nothing)   // (variant-selection bits of the fc backward GEMMs, nature.hip)
 int a3c_nat_pass_launch(int pass, const NetLayout& L, const float* P, const StateAddr& sa, int64_t B, const float* l1,
                         const float* l2, const float* l3, const float* l4, const uint16_t* w1t, float* fws,
                         float* bws, hipStream_t s);
@@ -70,10 +67,6 @@ int a3c_nat_pass_launch(int pass, const NetLayout& L, const float* P, const Stat
 #define A3C_NAT_W1T_BYTES (3 * NT1_N * NT_K1 * 2)
 #define A3C_NAT_W2T_OFF A3C_NAT_W1T_BYTES
 #define A3C_NAT_W3T_OFF (A3C_NAT_W2T_OFF + 3 * NT2_N * NT_K2 * 2)
-#define A3C_NAT_W2X_OFF (A3C_NAT_W3T_OFF + 3 * NT3_N * NT_K3 * 2)
-#define NT_X2 (4 * 4 * NT2_N)     // conv2's dX form: a cin row of 16 taps x 64 cout (1024)
-#define A3C_NAT_W3X_OFF (A3C_NAT_W2X_OFF + 3 * NT1_N * NT_X2 * 2)
-// (+ the dX forms: conv2's [3][32 cin][16 taps x 64 cout], conv3's [3][64 cin][9 taps x 64 cout])
-#define A3C_NAT_PREP_BYTES (A3C_NAT_W3X_OFF + 3 * NT2_N * NT_K3 * 2)
+#define A3C_NAT_PREP_BYTES (A3C_NAT_W3T_OFF + 3 * NT3_N * NT_K3 * 2)
 int a3c_nat_prep_launch(const NetLayout& L, const float* P, uint16_t* w1t, const int64_t* tau_src, int64_t* tau_dst,
                         uint32_t* sig, hipStream_t s);

@@ -1,16 +1,21 @@
 // The "nature" trunk of the reference's A3C Network (network.py:30-42: conv 8x8/4 32, conv 4x4/2
-// 64, conv 3x3/1 64, fc 3136 -> 512, all ReLU; heads network.py:60-79) on gfx950 matrix cores.
+// 64, conv 3x3/1 64, fc 3136 -> 512, all ReLU; heads network.py:60-79) on gfx950's bf16 matrix
+// cores.  The reference computes in fp32: the fp32 mode splits every fp32 operand into three
+// round-to-nearest bf16 terms and sums six products (fp32-class results); the bf16 compute mode
+// (A3C_PREC_BF16) rounds each operand once.  What runs (DESIGN §4d has the measurements
+// of the forms that lost: the fp32 MFMA tiles, per-layer forward passes, a fused dX, the fc on
+// these tiles -- all removed):
 //
-//  k_nat_gemm<MODE, BN>  one implicit-GEMM tile kernel for every convolution pass, operands gathered
-//                        straight from the NHWC activations (no im2col buffer in HBM), staged in LDS
-//                        as 16-deep K slices with a register prefetch of the next slice, and reduced
-//                        on v_mfma_f32_32x32x2f32 (exact fp32 products, fp32 accumulation: the
-//                        reference computes in fp32).  4 waves, each a 32x32 block of a
-//                        64x64 (BN = 64) or 128x32 (BN = 32: the 32-channel layers) tile.
-//    NG_FWD1  conv1: rows = (sample, output pixel), K = (kh, kw, cin) in TF order, A read from the
-//             u8 frame ring (the 4 history planes of the state, history.py:13-24), x / 255 applied to
-//             the accumulator (agent.py:226 / network.py:46); + bias, ReLU
-//    NG_FWD   conv2, conv3 from the fp32 NHWC output of the layer below; + bias, ReLU
+//  k_nat_w_terms<NT>   the prepared block: the conv weights as bf16 terms [term][cout][k], once per
+//                      rollout (a3c_nat_prep_launch) or into the workspace of a per-op call
+//  k_nat_conv23        fp32 mode: conv1 + conv2 + conv3 forward of one state per workgroup, the
+//                      activations kept in LDS as terms between the layers (launched as NAT_C2F)
+//  k_nat_conv123_b1    the same in the bf16 mode, one term per operand
+//  k_nat_gemm_bf<MODE, LAYER, BN, TA, TB, NBUF, PF>
+//                      the implicit-GEMM tile kernel of the conv backward passes, operands gathered
+//                      straight from the NHWC activations (no im2col buffer in HBM), split into
+//                      TA / TB terms at the LDS store, reduced on v_mfma_f32_32x32x16_bf16.  4 waves,
+//                      each a 32x32 block of a 64x64 (BN = 64) or 128x32 (BN = 32) tile.
 //    NG_DX    dX = col2im(dY W^T) * (X > 0), one stride parity class (py, px) per grid z: the output
 //             pixels y = S i + py, x = S j + px are reached only by taps kh = py + S th, kw = px + S tw,
 //             so K = (th, tw, cout) holds only real taps (conv2: 2x2x64 instead of 4x4x64)
@@ -20,36 +25,39 @@
 //    NG_DW1   the same for conv1 (patches from the u8 ring; the 1/255 is the finalize's scale)
 //  fc 3136 -> 512 and its backward: gemm.hip (split-K slabs with the bias + ReLU epilogue; the
 //  weight gradient in-workgroup split-K).  Head (k_nat_head): head_row<512> + the action draw and the
-//  fused env act of net_head.h; head backward: k_head_bwd<512> (net_bwd.hip).
+//  fused env act of net_head.h; the rollout step's head + screen kernels: net_fwd.hip; head
+//  backward: k_head_bwd<512> (net_bwd.hip).
 #include "nature.h"
 #include "net_bwd.h"
 #include "net_head.h"
 
-enum { NG_FWD1 = 0, NG_FWD, NG_DX, NG_DW1, NG_DW };
+// (the values are part of the kernels' symbol names, which profiles/ and tools/ record: 0 and 1
+// were the forward modes, whose passes k_nat_conv23 / k_nat_conv123_b1 run)
+enum { NG_DX = 2, NG_DW1, NG_DW };
 
 // conv layer geometry (NHWC input H x W x C, TF weights [KH][KW][C][OC], VALID, stride S)
 template <int LAYER> struct NG;
 template <> struct NG<1> { static constexpr int H = IMG, W = IMG, C = HIST, KH = 8, KW = 8, S = 4, OH = NT1_O, OW = NT1_O, OC = NT1_N; };
 template <> struct NG<2> { static constexpr int H = NT1_O, W = NT1_O, C = NT1_N, KH = 4, KW = 4, S = 2, OH = NT2_O, OW = NT2_O, OC = NT2_N; };
 template <> struct NG<3> { static constexpr int H = NT2_O, W = NT2_O, C = NT2_N, KH = 3, KW = 3, S = 1, OH = NT3_O, OW = NT3_O, OC = NT3_N; };
-// the fc 3136 -> 512 (network.py:41-42) as a 1x1 convolution of a 1x1 "image": the same tile
-// kernels then run its forward, weight gradient (NG_DW) and input gradient with the l3 ReLU mask (NG_DX)
-template <> struct NG<4> { static constexpr int H = 1, W = 1, C = NT_FLAT, KH = 1, KW = 1, S = 1, OH = 1, OW = 1, OC = NT_FC; };
 
+// (bias and scale were the removed forward modes' and are read by nothing: they stay because the
+// kernels' argument layout does -- without them the compiler merges the argument loads of the dX
+// and conv1 dW tiles differently and allocates other registers, and these kernels are to stay the
+// instructions that were measured)
 struct NatGemm {
-  StateAddr sa;        // NG_FWD1 / NG_DW1: the u8 state planes of sample b (b = t E + e)
-  const float* X;      // fp32 NHWC input activation [B][H][W][C] (NG_FWD, NG_DW; NG_DX: its ReLU mask)
-  const float* Wt;     // TF weights [KH][KW][C][OC]
-  const float* bias;   // NG_FWD*: [OC]
-  const float* dY;     // NG_DX, NG_DW*: [B][OH][OW][OC]
-  float* Y;            // NG_FWD*: [B][OH][OW][OC]; NG_DX: dX [B][H][W][C]
+  StateAddr sa;        // NG_DW1: the u8 state planes of sample b (b = t E + e)
+  const float* X;      // fp32 NHWC input activation [B][H][W][C] (NG_DW; NG_DX: its ReLU mask)
+  const float* Wt;     // NG_DX: TF weights [KH][KW][C][OC]
+  const float* bias;   // unused
+  const float* dY;     // [B][OH][OW][OC]
+  float* Y;            // NG_DX: dX [B][H][W][C]
   float* slab;         // NG_DW*: [nsplit][M][N]
   float* colsum;       // NG_DW*: [nsplit][N]
   int M, N, K;         // NG_DX: M per parity class; NG_DW*: M = KH KW C, N = OC, K = B OH OW (reduction)
-  int kchunk;          // NG_DW*: reduction rows per split (a multiple of the K slice); NG_FWD: > 0 splits K
-                       // over grid z into slab partials (the fold applies bias + ReLU)
-  float scale;         // NG_FWD1: 1/255
-  int xcd;             // NG_DW*, NG_DX: XCD-grouped tile order (nat_tile_of)
+  int kchunk;          // NG_DW*: reduction rows per split (a multiple of the K slice)
+  float scale;         // unused
+  int xcd;             // XCD-grouped tile order (nat_tile_of)
 };
 
 // The dispatcher deals workgroups round-robin over the 8 XCDs (linear id % 8), each with its own
@@ -60,7 +68,7 @@ struct NatGemm {
 template <int MODE>
 __device__ inline void nat_tile_of(int xcd, int& by, int& bz) {
   by = (int)blockIdx.y; bz = (int)blockIdx.z;
-  if (!xcd || gridDim.x != 1 || MODE == NG_FWD1 || MODE == NG_FWD) return;
+  if (!xcd || gridDim.x != 1) return;
   constexpr bool DWM = MODE == NG_DW || MODE == NG_DW1;
   const int G = DWM ? (int)gridDim.z : (int)gridDim.y;     // groups sharing data
   const int S = DWM ? (int)gridDim.y : (int)gridDim.z;     // workgroups per group
@@ -98,285 +106,18 @@ struct RingRows {
   }
 };
 
-// One tile of an implicit GEMM on v_mfma_f32_32x32x2f32: 32-deep K slices, double-buffered in LDS
-// (one barrier per slice), the next slice's operands loaded into registers under the current
-// slice's 16 MFMAs per wave.  Geometry at compile time (every index division by a constant).
-template <int MODE, int LAYER, int BN>
-__global__ void __launch_bounds__(256) k_nat_gemm(NatGemm a) {
-  using G = NG<LAYER>;
-  constexpr int BM = 4096 / BN, BK = 32, LP = 4;
-  constexpr int WN = BN / 32;                                   // waves along n
-  constexpr bool A_KC = MODE == NG_FWD1 || MODE == NG_FWD || MODE == NG_DX;   // A quads along k
-  constexpr bool B_NC = MODE != NG_DX;                           // B quads along n
-  constexpr bool DW = MODE == NG_DW || MODE == NG_DW1;
-  constexpr bool U8 = MODE == NG_FWD1 || MODE == NG_DW1;
-  constexpr int AQ = BM * BK / 4 / 256;                          // A quads per thread (2 or 4)
-  constexpr int BQ = BN * BK / 4 / 256;                          // B quads per thread (2 or 1)
-  constexpr int P = G::OH * G::OW;
-  constexpr int TW = G::KW / G::S;                               // NG_DX taps per class along x
-  constexpr int NI = G::H / G::S, NJ = G::W / G::S;              // NG_DX class grid
-  static_assert(MODE != NG_DX || (G::H % G::S == 0 && G::KH % G::S == 0), "parity classes");
-  static_assert(!U8 || G::C == 4, "u8 planes: the 4 history frames");
-  static_assert(P > BK, "one sample wrap per slice");
-  __shared__ __attribute__((aligned(16))) float As[2][BK][BM + LP];
-  __shared__ __attribute__((aligned(16))) float Bs[2][BK][BN + LP];
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int wm = wid / WN, wn = wid % WN;
-  int by, bz;
-  nat_tile_of<MODE>(a.xcd, by, bz);
-  const int m0 = by * BM, n0 = blockIdx.x * BN;
-  const bool split = DW || (MODE == NG_FWD && a.kchunk > 0);
-  const int kbeg = split ? bz * a.kchunk : 0;
-  const int kend = split ? min(a.K, kbeg + a.kchunk) : a.K;
-  const int py = MODE == NG_DX ? bz / G::S : 0, px = MODE == NG_DX ? bz % G::S : 0;
-  RingRows ring;
-  if constexpr (U8) ring.init(a.sa, a.sa.tau_ptr ? *a.sa.tau_ptr : 0);
-
-  // ---- per-thread operand coordinates ----
-  int ar[AQ], ac[AQ];          // A_KC: row m (tile-local), k offset; else: reduction row, m offset
-  bool aval[AQ];
-  int64_t abase[AQ];           // NG_FWD: X offset of the patch origin; NG_DX: sample b
-  int ai[AQ], aj[AQ];          // NG_DX: class grid position; NG_FWD1: pixel origin (y0, x0)
-  const uint8_t* apl[AQ][4];   // NG_FWD1: the sample's 4 planes (ring slots wrap: no common stride)
-  int mk[AQ][3];               // DW: (kh, kw, c0) of the thread's m quad
-#pragma unroll
-  for (int i = 0; i < AQ; ++i) {
-    const int q = tid + 256 * i;
-    if constexpr (A_KC) { ar[i] = q >> 3; ac[i] = (q & 7) * 4; }
-    else { ar[i] = q / (BM / 4); ac[i] = (q % (BM / 4)) * 4; }
-    abase[i] = 0; ai[i] = aj[i] = 0;
-    if constexpr (A_KC) {
-      const int m = m0 + ar[i];
-      aval[i] = m < a.M;
-      const int mm = aval[i] ? m : 0;
-      if constexpr (MODE == NG_DX) {
-        const int b = mm / (NI * NJ), r = mm - b * (NI * NJ);
-        abase[i] = b; ai[i] = r / NJ; aj[i] = r - (r / NJ) * NJ;
-      } else {
-        const int b = mm / P, pos = mm - b * P, oy = pos / G::OW, ox = pos - oy * G::OW;
-        if constexpr (MODE == NG_FWD1) {
-          const int t = b / ring.E, e = b - t * ring.E;
-#pragma unroll
-          for (int cc = 0; cc < 4; ++cc) apl[i][cc] = ring.plane(e, t, cc);
-          ai[i] = oy * G::S; aj[i] = ox * G::S;
-        } else {
-          abase[i] = (((int64_t)b * G::H + oy * G::S) * G::W + ox * G::S) * G::C;
-        }
-      }
-    } else {
-      const int m = m0 + ac[i];
-      aval[i] = m < a.M;
-      const int mm = aval[i] ? m : 0;
-      if constexpr (U8) {                  // conv1: m = (cin, kh, kw), a quad = kw 4j..4j+3 of plane cin
-        mk[i][0] = (mm >> 3) & 7; mk[i][1] = mm & 7; mk[i][2] = mm >> 6;
-      } else {                             // TF order m = (kh KW + kw) C + c, a quad = 4 channels
-        mk[i][0] = mm / (G::KW * G::C);
-        mk[i][1] = (mm / G::C) % G::KW;
-        mk[i][2] = mm % G::C;
-      }
-    }
-  }
-  int br[BQ], bc[BQ];          // B_NC: k row, n offset; else: n row, k offset
-#pragma unroll
-  for (int j = 0; j < BQ; ++j) {
-    const int q = tid + 256 * j;
-    if constexpr (B_NC) { br[j] = q / (BN / 4); bc[j] = (q % (BN / 4)) * 4; }
-    else { br[j] = q >> 3; bc[j] = (q & 7) * 4; }
-  }
-
-  // A quad i of the slice at k0
-  auto load_a = [&](int i, int k0) -> f32x4 {
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if constexpr (A_KC) {
-      const int k = k0 + ac[i];
-      if (!aval[i] || k >= kend) return v;
-      if constexpr (MODE == NG_FWD1) {     // conv1's K order (cin, kh, kw): kw 4j..4j+3 of one plane, one dword
-        const int cc = k >> 6, kh = (k >> 3) & 7, kw = k & 7;
-        const uint32_t d = *(const uint32_t*)(apl[i][cc] + (ai[i] + kh) * IMG + aj[i] + kw);
-        v[0] = (float)(d & 255u); v[1] = (float)((d >> 8) & 255u); v[2] = (float)((d >> 16) & 255u); v[3] = (float)(d >> 24);
-      } else if constexpr (MODE == NG_FWD) {
-        const int kh = k / (G::KW * G::C), rem = k - kh * (G::KW * G::C), kw = rem / G::C, c0 = rem - kw * G::C;
-        v = *(const f32x4*)(a.X + abase[i] + (kh * G::W + kw) * G::C + c0);
-      } else {                                                     // NG_DX: k = (th TW + tw) OC + oc
-        const int th = k / (TW * G::OC), rem = k - th * (TW * G::OC), tw = rem / G::OC, oc0 = rem - tw * G::OC;
-        const int oy = ai[i] - th, ox = aj[i] - tw;
-        if (oy >= 0 && oy < G::OH && ox >= 0 && ox < G::OW)
-          v = *(const f32x4*)(a.dY + ((abase[i] * G::OH + oy) * G::OW + ox) * G::OC + oc0);
-      }
-    } else {                                                       // DW: reduction row r, m quad
-      const int r = k0 + ar[i];
-      if (!aval[i] || r >= kend) return v;
-      const int b = r / P, pos = r - b * P, oy = pos / G::OW, ox = pos - oy * G::OW;
-      const int y = oy * G::S + mk[i][0], x = ox * G::S + mk[i][1];
-      if constexpr (MODE == NG_DW1) {
-        const int t = ring.step_of(b);
-        const uint32_t d = *(const uint32_t*)(ring.plane(b - t * ring.E, t, mk[i][2]) + y * IMG + x);
-        v[0] = (float)(d & 255u); v[1] = (float)((d >> 8) & 255u); v[2] = (float)((d >> 16) & 255u); v[3] = (float)(d >> 24);
-      } else {
-        v = *(const f32x4*)(a.X + (((int64_t)b * G::H + y) * G::W + x) * G::C + mk[i][2]);
-      }
-    }
-    return v;
-  };
-  auto load_b = [&](int j, int k0) -> f32x4 {
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if constexpr (B_NC) {
-      const int k = k0 + br[j], n = n0 + bc[j];
-      if (k >= kend || n >= a.N) return v;
-      const int row = MODE == NG_FWD1 ? ((((k >> 3) & 7) * 8 + (k & 7)) * 4 + (k >> 6)) : k;   // conv1: TF row of k
-      v = DW ? *(const f32x4*)(a.dY + (int64_t)k * G::OC + n) : *(const f32x4*)(a.Wt + (int64_t)row * G::OC + n);
-    } else {                                                       // NG_DX: B(k, c) = W[kh][kw][c][oc..]
-      const int n = n0 + br[j], k = k0 + bc[j];
-      if (n >= a.N || k >= kend) return v;
-      const int th = k / (TW * G::OC), rem = k - th * (TW * G::OC), tw = rem / G::OC, oc0 = rem - tw * G::OC;
-      const int kh = py + G::S * th, kw = px + G::S * tw;
-      v = *(const f32x4*)(a.Wt + (((int64_t)kh * G::KW + kw) * G::C + n) * G::OC + oc0);
-    }
-    return v;
-  };
-  auto store = [&](int buf, const f32x4 (&ra)[AQ], const f32x4 (&rbv)[BQ]) {
-#pragma unroll
-    for (int i = 0; i < AQ; ++i) {
-      if constexpr (A_KC) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) As[buf][ac[i] + c][ar[i]] = ra[i][c];
-      } else {
-        *(f32x4*)&As[buf][ar[i]][ac[i]] = ra[i];
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < BQ; ++j) {
-      if constexpr (B_NC) {
-        *(f32x4*)&Bs[buf][br[j]][bc[j]] = rbv[j];
-      } else {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) Bs[buf][bc[j] + c][br[j]] = rbv[j][c];
-      }
-    }
-  };
-
-  f32x16 acc = {};
-  float csum = 0.f;
-  const bool do_colsum = DW && a.colsum && by == 0 && tid < BN;
-  const int kh = lane >> 5, c = lane & 31;
-  auto load_all = [&](int k0, f32x4 (&ra)[AQ], f32x4 (&rbv)[BQ]) {
-#if defined(NAT_ABL) && NAT_ABL == 2      // measurement only: no operand loads
-    for (int i = 0; i < AQ; ++i) ra[i] = (f32x4){(float)k0, 1.f, 2.f, 3.f};
-    for (int j = 0; j < BQ; ++j) rbv[j] = (f32x4){(float)k0, 1.f, 2.f, 3.f};
-    return;
-#endif
-#pragma unroll
-    for (int i = 0; i < AQ; ++i) ra[i] = load_a(i, k0);
-#pragma unroll
-    for (int j = 0; j < BQ; ++j) rbv[j] = load_b(j, k0);
-  };
-  auto compute = [&](int buf) {
-    if (do_colsum) {
-#pragma unroll
-      for (int k = 0; k < BK; ++k) csum += Bs[buf][k][tid];
-    }
-#if defined(NAT_ABL) && NAT_ABL == 1      // measurement only: LDS operand reads, no MFMA
-    for (int kk = 0; kk < BK / 2; ++kk) acc[kk] += As[buf][2 * kk + kh][wm * 32 + c] * Bs[buf][2 * kk + kh][wn * 32 + c];
-    return;
-#endif
-#pragma unroll
-    for (int kk = 0; kk < BK / 2; ++kk)
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(As[buf][2 * kk + kh][wm * 32 + c], Bs[buf][2 * kk + kh][wn * 32 + c],
-                                                 acc, 0, 0, 0);
-  };
-  if constexpr (DW) {
-    // the weight-gradient passes (long reductions, ~110-120 VGPRs anyway): two register sets keep
-    // two slices in flight beyond the one in LDS, slice s loading while slices s-2 and s-1 compute
-    // (measured: conv1/2/3 dW 188/91/66 -> 175/87/63 us; the forward passes lose occupancy with it)
-    f32x4 ra0[AQ], rb0[BQ], ra1[AQ], rb1[BQ];
-    load_all(kbeg, ra0, rb0);
-    store(0, ra0, rb0);
-    if (kbeg + BK < kend) load_all(kbeg + BK, ra1, rb1);
-    if (kbeg + 2 * BK < kend) load_all(kbeg + 2 * BK, ra0, rb0);
-    __syncthreads();
-    for (int k0 = kbeg; k0 < kend; k0 += 2 * BK) {
-      // LDS buffer 0: slice k0; set 1: slice k0 + BK; set 0: slice k0 + 2 BK
-      compute(0);
-      if (k0 + BK < kend) {
-        store(1, ra1, rb1);
-        if (k0 + 3 * BK < kend) load_all(k0 + 3 * BK, ra1, rb1);
-      }
-      __syncthreads();
-      if (k0 + BK >= kend) break;
-      compute(1);
-      if (k0 + 2 * BK < kend) {
-        store(0, ra0, rb0);
-        if (k0 + 4 * BK < kend) load_all(k0 + 4 * BK, ra0, rb0);
-      }
-      __syncthreads();
-    }
-  } else {
-    // one register set: the next slice loads under this slice's MFMAs
-    f32x4 ra[AQ], rbv[BQ];
-    load_all(kbeg, ra, rbv);
-    store(0, ra, rbv);
-    __syncthreads();
-    int buf = 0;
-    for (int k0 = kbeg; k0 < kend; k0 += BK) {
-      const bool more = k0 + BK < kend;
-      if (more) load_all(k0 + BK, ra, rbv);
-      compute(buf);
-      if (more) store(buf ^ 1, ra, rbv);        // (the other buffer: last read before the previous barrier)
-      __syncthreads();
-      buf ^= 1;
-    }
-  }
-
-  const int col = n0 + wn * 32 + (lane & 31);
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int row = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-    if (row >= a.M || col >= a.N) continue;
-    float v = acc[r];
-    if constexpr (MODE == NG_FWD1 || MODE == NG_FWD) {
-      if (MODE == NG_FWD && split) {            // a K-split partial: the fold adds bias + ReLU
-        a.slab[((int64_t)bz * a.M + row) * a.N + col] = v;
-        continue;
-      }
-      v = fmaxf((MODE == NG_FWD1 ? v * a.scale : v) + a.bias[col], 0.f);
-      a.Y[(int64_t)row * a.N + col] = v;
-    } else if constexpr (MODE == NG_DX) {
-      const int b = row / (NI * NJ), rr = row - b * (NI * NJ), i = rr / NJ, j = rr - (rr / NJ) * NJ;
-      const int64_t o = (((int64_t)b * G::H + py + G::S * i) * G::W + px + G::S * j) * G::C + col;
-      a.Y[o] = a.X[o] > 0.f ? v : 0.f;
-    } else {
-      // conv1's m = (cin, kh, kw) -> the TF row (kh 8 + kw) 4 + cin of dW1 [8][8][4][32]
-      const int trow = MODE == NG_DW1 ? ((((row >> 3) & 7) * 8 + (row & 7)) * 4 + (row >> 6)) : row;
-      a.slab[((int64_t)bz * a.M + trow) * a.N + col] = v;
-    }
-  }
-  if (do_colsum && n0 + tid < a.N) a.colsum[(int64_t)bz * a.N + n0 + tid] = csum;
-}
-
-static int nat_xcd() {
-  static const int v = (int)A3C_AB_KNOB("A3C_NAT_XCD", 1);   // A/B: 0 = the hardware tile order
-  return v;
-}
-template <int MODE, int LAYER, int BN>
-static int nat_go(NatGemm a, unsigned gz, hipStream_t s) {
-  constexpr int BM = 4096 / BN;
-  if (a.M <= 0 || a.N <= 0) return 0;
-  a.xcd = nat_xcd();
-  const dim3 grid((unsigned)((a.N + BN - 1) / BN), (unsigned)((a.M + BM - 1) / BM), gz);
-  hipLaunchKernelGGL((k_nat_gemm<MODE, LAYER, BN>), grid, dim3(256), 0, s, a);
-  A3C_CHECK(hipGetLastError());
-  return 0;
-}
-
 // ---------------------------------------------------------------------------------------
-// The same passes on the bf16 matrix cores (v_mfma_f32_32x32x16_bf16, 32 cycles per 32x32x16 vs 512
-// for the 32x32x2f32 chain of the same depth).  Each fp32 operand is split at the LDS store into
+// The conv backward passes on the bf16 matrix cores (v_mfma_f32_32x32x16_bf16, 32 cycles per 32x32x16
+// against 512 for a v_mfma_f32_32x32x2f32 chain of the same depth: the fp32 MFMA form of this tile
+// lost on the dX and conv1 dW passes alone and in the whole bench, DESIGN §4d,
+// profiles/round6/r6bf3_nature_pass_ab.txt).  Geometry at compile time (every index division by a
+// constant).  Each fp32 operand is split at the LDS store into
 // three round-to-nearest bf16 terms x = hi + mid + lo (v_cvt_pk_bf16_f32; exact to ~2^-24 relative)
 // and the tile sums the six products hi.hi, hi.mid, mid.hi, mid.mid, hi.lo, lo.hi (the dropped
 // ones are below 2^-24 of the product): fp32-class results, as the NIPS conv2 (net_fwd.hip).
 // conv1's dW (TA = 1): a u8 pixel is exact in one bf16 term, three products.
 // LDS holds the terms k-contiguous ([row][k], 40 bf16 a row) for the MFMA's 8-deep lane fragments;
-// operands that arrive along rows (the dW passes' A and B, the forward's weights) are loaded as
+// operands that arrive along rows (the dW passes' A and B) are loaded as
 // quad pairs at k and k + 1 and stored as packed (k, k + 1) dwords.
 // ---------------------------------------------------------------------------------------
 typedef float f32x2v __attribute__((ext_vector_type(2)));
@@ -404,11 +145,11 @@ __global__ void __launch_bounds__(256) k_nat_gemm_bf(NatGemm a) {
   using G = NG<LAYER>;
   constexpr int BM = 4096 / BN, BK = 32, LD = 40;
   constexpr int WN = BN / 32;
-  constexpr bool A_KC = MODE == NG_FWD || MODE == NG_DX;         // A quads along k (else pairs of row quads)
+  constexpr bool A_KC = MODE == NG_DX;                           // A quads along k (else pairs of row quads)
   constexpr bool B_NC = MODE != NG_DX;                           // B quads along n: pairs of row quads
   constexpr bool DW = MODE == NG_DW || MODE == NG_DW1;
   constexpr bool U8 = MODE == NG_DW1;
-  static_assert(MODE != NG_FWD1, "conv1 forward: k_nat_conv1_bf");
+  static_assert(MODE == NG_DX || MODE == NG_DW || MODE == NG_DW1, "the backward passes");
   static_assert(TB == 3 || (TB == 1 && TA == 1), "one B term: the bf16 mode, one A term as well");
   static_assert(TA == 3 || (TA == 1 && (U8 || TB == 1)), "one A term: the exact u8 pixels, or the bf16 mode");
   constexpr int AQ = BM * BK / 4 / 256;                          // A quads per thread (2 or 4)
@@ -428,9 +169,8 @@ __global__ void __launch_bounds__(256) k_nat_gemm_bf(NatGemm a) {
   int by, bz;
   nat_tile_of<MODE>(a.xcd, by, bz);
   const int m0 = by * BM, n0 = blockIdx.x * BN;
-  const bool split = DW || (MODE == NG_FWD && a.kchunk > 0);
-  const int kbeg = split ? bz * a.kchunk : 0;
-  const int kend = split ? min(a.K, kbeg + a.kchunk) : a.K;
+  const int kbeg = DW ? bz * a.kchunk : 0;
+  const int kend = DW ? min(a.K, kbeg + a.kchunk) : a.K;
   const int py = MODE == NG_DX ? bz / G::S : 0, px = MODE == NG_DX ? bz % G::S : 0;
   RingRows ring;
   if constexpr (U8) ring.init(a.sa, a.sa.tau_ptr ? *a.sa.tau_ptr : 0);
@@ -462,13 +202,8 @@ __global__ void __launch_bounds__(256) k_nat_gemm_bf(NatGemm a) {
       const int m = m0 + ar[i];
       aval[i] = m < a.M;
       const int mm = aval[i] ? m : 0;
-      if constexpr (MODE == NG_DX) {
-        const int b = mm / (NI * NJ), r = mm - b * (NI * NJ);
-        abase[i] = b; ai[i] = r / NJ; aj[i] = r - (r / NJ) * NJ;
-      } else {
-        const int b = mm / P, pos = mm - b * P, oy = pos / G::OW, ox = pos - oy * G::OW;
-        abase[i] = (((int64_t)b * G::H + oy * G::S) * G::W + ox * G::S) * G::C;
-      }
+      const int b = mm / (NI * NJ), r = mm - b * (NI * NJ);
+      abase[i] = b; ai[i] = r / NJ; aj[i] = r - (r / NJ) * NJ;
     } else {
       const int m = m0 + ac[i];
       aval[i] = m < a.M;
@@ -502,15 +237,10 @@ __global__ void __launch_bounds__(256) k_nat_gemm_bf(NatGemm a) {
     if constexpr (A_KC) {
       const int k = k0 + ac[i];
       if (!aval[i] || k >= kend) return v;
-      if constexpr (MODE == NG_FWD) {
-        const int kh = k / (G::KW * G::C), rem = k - kh * (G::KW * G::C), kw = rem / G::C, c0 = rem - kw * G::C;
-        v = *(const f32x4*)(a.X + abase[i] + (kh * G::W + kw) * G::C + c0);
-      } else {
-        const int th = k / (TW * G::OC), rem = k - th * (TW * G::OC), tw = rem / G::OC, oc0 = rem - tw * G::OC;
-        const int oy = ai[i] - th, ox = aj[i] - tw;
-        if (oy >= 0 && oy < G::OH && ox >= 0 && ox < G::OW)
-          v = *(const f32x4*)(a.dY + ((abase[i] * G::OH + oy) * G::OW + ox) * G::OC + oc0);
-      }
+      const int th = k / (TW * G::OC), rem = k - th * (TW * G::OC), tw = rem / G::OC, oc0 = rem - tw * G::OC;
+      const int oy = ai[i] - th, ox = aj[i] - tw;
+      if (oy >= 0 && oy < G::OH && ox >= 0 && ox < G::OW)
+        v = *(const f32x4*)(a.dY + ((abase[i] * G::OH + oy) * G::OW + ox) * G::OC + oc0);
     } else {
       const int r = k0 + ar[i];
       if (!aval[i] || r >= kend) return v;
@@ -529,10 +259,10 @@ __global__ void __launch_bounds__(256) k_nat_gemm_bf(NatGemm a) {
   auto load_b = [&](int j, int k0) -> f32x4 {
     f32x4 v = {0.f, 0.f, 0.f, 0.f};
     if (!bok[j]) return v;
-    if constexpr (B_NC) {
+    if constexpr (B_NC) {                                          // (DW) dY rows
       const int k = k0 + br[j], n = n0 + bc[j];
       if (k >= kend || n >= a.N) return v;
-      v = DW ? *(const f32x4*)(a.dY + (int64_t)k * G::OC + n) : *(const f32x4*)(a.Wt + (int64_t)k * G::OC + n);
+      v = *(const f32x4*)(a.dY + (int64_t)k * G::OC + n);
     } else {
       const int n = n0 + br[j], k = k0 + bc[j];
       if (n >= a.N || k >= kend) return v;
@@ -712,13 +442,7 @@ __global__ void __launch_bounds__(256) k_nat_gemm_bf(NatGemm a) {
     const int row = m0 + wm * 32 + (q & 3) + 8 * (q >> 2) + 4 * h;
     if (row >= a.M || col >= a.N) continue;
     float v = acc[q];
-    if constexpr (MODE == NG_FWD) {
-      if (split) {
-        a.slab[((int64_t)bz * a.M + row) * a.N + col] = v;
-        continue;
-      }
-      a.Y[(int64_t)row * a.N + col] = fmaxf(v + a.bias[col], 0.f);
-    } else if constexpr (MODE == NG_DX) {
+    if constexpr (MODE == NG_DX) {
       const int b = row / (NI * NJ), rr = row - b * (NI * NJ), i = rr / NJ, j = rr - (rr / NJ) * NJ;
       const int64_t o = (((int64_t)b * G::H + py + G::S * i) * G::W + px + G::S * j) * G::C + col;
       a.Y[o] = a.X[o] > 0.f ? v : 0.f;
@@ -746,33 +470,22 @@ __global__ void __launch_bounds__(256) k_nat_gemm_bf(NatGemm a) {
   }
 }
 
-template <int MODE, int LAYER, int BN, int TA, int TB = 3>
-static int nat_go_bf(NatGemm a, unsigned gz, hipStream_t s, bool one_buf, bool pf2) {
+template <int MODE, int LAYER, int BN, int TA, int TB, int NBUF, int PF>
+static int nat_go_bf(NatGemm a, unsigned gz, hipStream_t s) {
   constexpr int BM = 4096 / BN;
   if (a.M <= 0 || a.N <= 0) return 0;
-  a.xcd = nat_xcd();
+  a.xcd = 1;   // (the hardware tile order lost, 1.27M against 1.33M: DESIGN §4d, profiles/round6/r6pf4_nature_knob_bench_ab.txt)
   const dim3 grid((unsigned)((a.N + BN - 1) / BN), (unsigned)((a.M + BM - 1) / BM), gz);
-  if (one_buf && pf2)
-    hipLaunchKernelGGL((k_nat_gemm_bf<MODE, LAYER, BN, TA, TB, 1, 2>), grid, dim3(256), 0, s, a);
-  else if (one_buf)
-    hipLaunchKernelGGL((k_nat_gemm_bf<MODE, LAYER, BN, TA, TB, 1, 1>), grid, dim3(256), 0, s, a);
-  else if (pf2)
-    hipLaunchKernelGGL((k_nat_gemm_bf<MODE, LAYER, BN, TA, TB, 2, 2>), grid, dim3(256), 0, s, a);
-  else
-    hipLaunchKernelGGL((k_nat_gemm_bf<MODE, LAYER, BN, TA, TB, 2, 1>), grid, dim3(256), 0, s, a);
+  hipLaunchKernelGGL((k_nat_gemm_bf<MODE, LAYER, BN, TA, TB, NBUF, PF>), grid, dim3(256), 0, s, a);
   A3C_CHECK(hipGetLastError());
   return 0;
 }
 
 // ---------------------------------------------------------------------------------------
-// conv1 forward on the bf16 matrix cores.  A u8 pixel is exact in bf16, and the fp32 weight is
-// three round-to-nearest bf16 terms (w = hi + mid + lo to ~2^-24 relative, as the NIPS conv1,
-// net_fwd.hip): acc += x hi + x mid + x lo, every product exact in the fp32 accumulator -- three
-// v_mfma_f32_32x32x16_bf16 (32 cycles each) per 16-deep K step instead of eight 64-cycle fp32 ones.
+// The prepared block: the conv weights as round-to-nearest bf16 terms (w = hi + mid + lo to ~2^-24
+// relative, as the NIPS conv1, net_fwd.hip), k-contiguous per output channel, for the per-state
+// forward kernels below.
 // ---------------------------------------------------------------------------------------
-#define W1T_ELEMS (3 * NT1_N * NT_K1)     // bf16: [term][cout][k'], k' = (cin, kh, kw)
-#define C1B_LD 40                          // bf16 per LDS row: 32 + 8 (16-byte aligned, rows 80 B apart)
-
 __device__ inline uint32_t nat_bf16_rn(float f) {
   uint32_t u = __float_as_uint(f);
   u += 0x7FFFu + ((u >> 16) & 1u);
@@ -801,8 +514,7 @@ __device__ inline void nat_terms3(float w, uint16_t* dst, int64_t tstride) {
 // [3][64][576] with k in TF order (kh, kw, cin) -- one thread per (cout, k)
 template <int NT>
 __global__ void __launch_bounds__(256) k_nat_w_terms(const float* __restrict__ W1, const float* __restrict__ W2,
-                                                     const float* __restrict__ W3, uint16_t* __restrict__ wt,
-                                                     int all) {
+                                                     const float* __restrict__ W3, uint16_t* __restrict__ wt) {
   int i = blockIdx.x * 256 + threadIdx.x;
   if (i < NT1_N * NT_K1) {
     const int n = i / NT_K1, k = i - n * NT_K1;
@@ -810,7 +522,6 @@ __global__ void __launch_bounds__(256) k_nat_w_terms(const float* __restrict__ W
     nat_terms3<NT>(W1[((kh * 8 + kw) * HIST + c) * NT1_N + n], wt + n * NT_K1 + k, NT1_N * NT_K1);
     return;
   }
-  if (!all) return;
   i -= NT1_N * NT_K1;
   if (i < NT2_N * NT_K2) {
     const int n = i / NT_K2, k = i - n * NT_K2;
@@ -821,19 +532,6 @@ __global__ void __launch_bounds__(256) k_nat_w_terms(const float* __restrict__ W
   if (i < NT3_N * NT_K3) {
     const int n = i / NT_K3, k = i - n * NT_K3;
     nat_terms3<NT>(W3[k * NT3_N + n], wt + A3C_NAT_W3T_OFF / 2 + n * NT_K3 + k, NT3_N * NT_K3);
-    return;
-  }
-  i -= NT3_N * NT_K3;
-  // dX forms: [term][cin][tap][cout] = W[tap][cin][cout] (TF [kh][kw][cin][cout]): a copy per term
-  if (i < NT1_N * NT_X2) {
-    const int c = i / NT_X2, r = i - c * NT_X2, tap = r >> 6, oc = r & 63;
-    nat_terms3<NT>(W2[(tap * NT1_N + c) * NT2_N + oc], wt + A3C_NAT_W2X_OFF / 2 + i, NT1_N * NT_X2);
-    return;
-  }
-  i -= NT1_N * NT_X2;
-  if (i < NT2_N * NT_K3) {
-    const int c = i / NT_K3, r = i - c * NT_K3, tap = r >> 6, oc = r & 63;
-    nat_terms3<NT>(W3[(tap * NT2_N + c) * NT3_N + oc], wt + A3C_NAT_W3X_OFF / 2 + i, NT2_N * NT_K3);
   }
 }
 
@@ -844,120 +542,18 @@ __device__ inline uint2 nat_u8x4_bf16(uint32_t d) {   // 4 pixels -> 4 bf16 (exa
                     __builtin_amdgcn_perm(__float_as_uint(f3), __float_as_uint(f2), 0x07060302u));
 }
 
-// tile: 128 rows (sample, pixel) x 32 channels, 4 waves of 32 rows; K = 256 in 8 slices of 32 (k' =
-// (cin, kh, kw): a row's 32 k' of a slice are 4 kernel rows of 8 pixels of one plane), LDS double-buffered
-template <int NBUF>
-__global__ void __launch_bounds__(256) k_nat_conv1_bf(StateAddr sa, const uint16_t* __restrict__ w1t,
-                                                      const float* __restrict__ bias, float* __restrict__ Y, int M,
-                                                      float scale) {
-  constexpr int BM = 128, BK = 32, P = NT1_P, OW = NT1_O;
-  __shared__ __attribute__((aligned(16))) uint16_t As[NBUF][BM][C1B_LD];
-  __shared__ __attribute__((aligned(16))) uint16_t Bs[NBUF][3][NT1_N][C1B_LD];
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int m0 = blockIdx.x * BM;
-  RingRows ring;
-  ring.init(sa, sa.tau_ptr ? *sa.tau_ptr : 0);
-  // A: 2 octets per thread, an octet = kw 0..7 of one (cin, kh) patch row = one 8-byte load
-  int ar[2], ac[2], ai[2], aj[2];
-  bool aval[2];
-  const uint8_t* apl[2][4];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int q = tid + 256 * i;
-    ar[i] = q >> 2; ac[i] = (q & 3) * 8;
-    const int m = m0 + ar[i];
-    aval[i] = m < M;
-    const int mm = aval[i] ? m : 0;
-    const int b = mm / P, pos = mm - b * P, oy = pos / OW, ox = pos - oy * OW;
-    const int t = ring.step_of(b), e = b - t * ring.E;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) apl[i][c] = ring.plane(e, t, c);
-    ai[i] = oy * 4; aj[i] = ox * 4;
-  }
-  auto load_a = [&](int i, int k0) -> uint2 {
-    const int k = k0 + ac[i];
-    if (!aval[i]) return make_uint2(0u, 0u);
-    const int c = k >> 6, kh = (k >> 3) & 7;
-    const uint32_t* q = (const uint32_t*)(apl[i][c] + (ai[i] + kh) * IMG + aj[i]);
-    return make_uint2(q[0], q[1]);
-  };
-  // B: 3 terms x 32 couts x 32 k' per slice = 384 chunks of 8 bf16
-  auto load_b = [&](int q, int k0) -> uint4 {
-    const int term = q >> 7, n = (q >> 2) & 31, kc = (q & 3) * 8;
-    return *(const uint4*)(w1t + (term * NT1_N + n) * NT_K1 + k0 + kc);
-  };
-  uint2 ra[2];
-  uint4 rb0, rb1;
-  const bool b2 = tid < 128;
-  auto load_all = [&](int k0) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) ra[i] = load_a(i, k0);
-    rb0 = load_b(tid, k0);
-    if (b2) rb1 = load_b(256 + tid, k0);
-  };
-  auto store = [&](int buf) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const uint2 lo = nat_u8x4_bf16(ra[i].x), hi = nat_u8x4_bf16(ra[i].y);
-      *(uint4*)&As[buf][ar[i]][ac[i]] = make_uint4(lo.x, lo.y, hi.x, hi.y);
-    }
-    {
-      const int q = tid, term = q >> 7, n = (q >> 2) & 31, kc = (q & 3) * 8;
-      *(uint4*)&Bs[buf][term][n][kc] = rb0;
-    }
-    if (b2) {
-      const int q = 256 + tid, term = q >> 7, n = (q >> 2) & 31, kc = (q & 3) * 8;
-      *(uint4*)&Bs[buf][term][n][kc] = rb1;
-    }
-  };
-  f32x16 acc = {};
-  const int r = lane & 31, h = lane >> 5;
-  auto compute = [&](int buf) {
-#pragma unroll
-    for (int s = 0; s < BK / 16; ++s) {
-      const bf16x8 a = *(const bf16x8*)&As[buf][wid * 32 + r][16 * s + 8 * h];
-#pragma unroll
-      for (int term = 0; term < 3; ++term) {
-        const bf16x8 bv = *(const bf16x8*)&Bs[buf][term][r][16 * s + 8 * h];
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, bv, acc, 0, 0, 0);
-      }
-    }
-  };
-  load_all(0);
-  store(0);
-  __syncthreads();
-  int buf = 0;
-  for (int k0 = 0; k0 < NT_K1; k0 += BK) {
-    const bool more = k0 + BK < NT_K1;
-    if (more) load_all(k0 + BK);
-    compute(buf);
-    if constexpr (NBUF == 1) {   // one buffer: the slice is stored after every wave has read it
-      __syncthreads();
-      if (more) store(0);
-    } else {
-      if (more) store(buf ^ 1);
-    }
-    __syncthreads();
-    buf ^= NBUF - 1;
-  }
-  const int col = lane & 31;
-  const float bc = bias[col];
-#pragma unroll
-  for (int q = 0; q < 16; ++q) {
-    const int row = m0 + wid * 32 + (q & 3) + 8 * (q >> 2) + 4 * h;
-    if (row < M) Y[(int64_t)row * NT1_N + col] = fmaxf(acc[q] * scale + bc, 0.f);
-  }
-}
-
 // ---------------------------------------------------------------------------------------
-// conv2 + conv3 forward fused, one workgroup per sample (the rollout's B = E states): the sample's
-// l1 (20x20x32) is split into three bf16 terms into LDS once; conv2 (M = 81 pixels, N = 64,
-// K = 16 taps x 32) and then conv3 (M = 49, N = 64, K = 9 taps x 64) run on
-// v_mfma_f32_16x16x32_bf16 with the six products of the term split (as k_nat_gemm_bf); l2 goes
-// out (the backward's operand) and, as terms, into the LDS the l1 terms held, for conv3.  Wave w
-// owns output channels 16w..16w+15 of both layers, its weight fragments (the prepared terms,
-// [term][cout][k]) streamed from L2 with a 3-tap register ring.  Replaces two K-chain-bound passes
-// of 324 / 392 tiles and a fold with one 256-workgroup launch and no l2 re-read from HBM.
+// conv1 + conv2 + conv3 forward fused, one workgroup per sample (the rollout's B = E states).
+// conv1: the sample's 4 u8 planes staged as bf16 rows, M = 400 pixels, N = 32, K = 256 in (cin, kh,
+// kw) order on v_mfma_f32_16x16x32_bf16 (the u8 pixel exact in one term: three products); its
+// output (x/255 + bias, ReLU) goes out for the backward and, as three bf16 terms, into LDS.  conv2
+// (M = 81 pixels, N = 64, K = 16 taps x 32) and then conv3 (M = 49, N = 64, K = 9 taps x 64) run
+// with the six products of the term split (as k_nat_gemm_bf); l2 goes out (the backward's operand)
+// and, as terms, into the LDS the l1 terms held, for conv3.  Wave w owns output channels
+// 16w..16w+15 of conv2 / conv3, its weight fragments (the prepared terms, [term][cout][k]) streamed
+// from L2 with a 3-tap register ring.  The per-layer tile passes it replaced were K-chain-bound at
+// this batch (324 / 392 tiles and a fold; conv1 its own launch: 1.47M against 1.51M with it inside;
+// DESIGN §4d, profiles/round6/r6fu_nature_fusion_ab.txt, r6sp1_nature_split_ab.txt).
 // ---------------------------------------------------------------------------------------
 // l1 terms: [term][y 20][x parity 2][x / 2 10][32 bf16]: a 16-lane fragment read walks consecutive
 // output pixels, which sit at x = 2 ox + kw -- parity-split rows put them one row apart.
@@ -980,9 +576,6 @@ __device__ inline f32x4 c23_mfma6(const bf16x8 (&a)[3], const bf16x8 (&b)[3], f3
   return acc;
 }
 
-// C1: conv1 as well (k_nat_conv123): the sample's 4 u8 planes staged as bf16 rows, conv1 (M = 400
-// pixels, N = 32, K = 256 in (cin, kh, kw) order, the u8 pixel exact: three products) on the same
-// MFMA, its output (x/255 + bias, ReLU) written out for the backward and, as terms, into LDS.
 #define C123_PR 88                                   // bf16 per staged plane row (84 + 4)
 static_assert(HIST * IMG * C123_PR <= 3 * C23_T1, "planes fit the term LDS");
 #ifndef C23_PD     // weight-fragment prefetch distance in K steps (the ring holds C23_PD + 1 steps)
@@ -991,20 +584,19 @@ static_assert(HIST * IMG * C123_PR <= 3 * C23_T1, "planes fit the term LDS");
 #ifndef C23_BATCH  // 1: the plane staging issues all its loads before the first conversion
 #define C23_BATCH 1
 #endif
-template <bool C1>
-__global__ void __launch_bounds__(256) k_nat_conv23(const float* __restrict__ l1c, const uint16_t* __restrict__ w2t,
-                                                    const float* __restrict__ b2, const uint16_t* __restrict__ w3t,
-                                                    const float* __restrict__ b3, float* __restrict__ l2,
-                                                    float* __restrict__ l3, StateAddr sa, const uint16_t* __restrict__ w1t,
-                                                    const float* __restrict__ b1, float* __restrict__ l1, float scale) {
+__global__ void __launch_bounds__(256) k_nat_conv23(const uint16_t* __restrict__ w2t, const float* __restrict__ b2,
+                                                    const uint16_t* __restrict__ w3t, const float* __restrict__ b3,
+                                                    float* __restrict__ l2, float* __restrict__ l3, StateAddr sa,
+                                                    const uint16_t* __restrict__ w1t, const float* __restrict__ b1,
+                                                    float* __restrict__ l1, float scale) {
   __shared__ __attribute__((aligned(16))) uint16_t sm[3 * C23_T1];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int i16 = lane & 15, g = lane >> 4;
   const int64_t b = blockIdx.x;
   // the engine's live launch span (a3c_engine_span_stats 1, bench.py's roofline)
-  unsigned long long* srec = C1 ? span_rec(sa, sa.tau_ptr ? *sa.tau_ptr : 0) : nullptr;
+  unsigned long long* srec = span_rec(sa, sa.tau_ptr ? *sa.tau_ptr : 0);
   span_begin(srec);
-  if constexpr (C1) {
+  {
     // ---- the 4 history planes of state b as bf16 [cin][84][88] ----
     RingRows ring;
     ring.init(sa, sa.tau_ptr ? *sa.tau_ptr : 0);
@@ -1095,22 +687,6 @@ __global__ void __launch_bounds__(256) k_nat_conv23(const float* __restrict__ l1
         sm[1 * C23_T1 + slot * C23_R1 + n1] = (uint16_t)(__float_as_uint(mf) >> 16);
         sm[2 * C23_T1 + slot * C23_R1 + n1] = (uint16_t)nat_bf16_rn(r1 - mf);
       }
-    }
-  } else {
-    // ---- stage l1 of sample b as three bf16 terms (3200 float4 chunks, 12.5 per thread) ----
-    const f32x4* src = (const f32x4*)(l1c + b * NT_A1);
-    constexpr int NCH = NT_A1 / 4;
-#pragma unroll 4
-    for (int c = tid; c < NCH; c += 256) {
-      const f32x4 v = src[c];
-      const int px = c >> 3, c4 = (c & 7) * 4;          // pixel (y 20 x 20), channel quad
-      const int y = px / NT1_O, x = px - y * NT1_O;
-      const int slot = (y * 2 + (x & 1)) * (NT1_O / 2) + (x >> 1);
-      uint32_t lo[3], hi[3];
-      nat_split2<3>(v[0], v[1], lo);
-      nat_split2<3>(v[2], v[3], hi);
-#pragma unroll
-      for (int t = 0; t < 3; ++t) *(uint2*)&sm[t * C23_T1 + slot * C23_R1 + c4] = make_uint2(lo[t], hi[t]);
     }
   }
   __syncthreads();
@@ -1220,7 +796,7 @@ __global__ void __launch_bounds__(256) k_nat_conv23(const float* __restrict__ l1
 // per workgroup with one bf16 term per operand, rn(x) . rn(W), one v_mfma_f32_16x16x32_bf16 per K
 // step, fp32 accumulators, bias + ReLU in fp32; l1 / l2 / l3 go out as fp32 (the backward's
 // operands), rn(l1) and rn(l2) stay in LDS as the next layer's operand.
-// LDS, 32000 B (k_nat_conv23<true>: 76800), three tenants over one region:
+// LDS, 32000 B (k_nat_conv23: 76800), three tenants over one region:
 //   planes  [cin 4][y 84][88 B] u8, 29568 B: staged as they are in the frame ring (a quarter of
 //           the bf16 rows); conv1's A fragment is a lane's 8 pixels kw 0..7 of one (cin, kh) patch
 //           row = two dword reads, converted in registers (exact: a pixel is the upper half of its
@@ -1256,7 +832,7 @@ __global__ void __launch_bounds__(256) k_nat_conv123_b1(StateAddr sa, const uint
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int i16 = lane & 15, g = lane >> 4;
   const int64_t b = blockIdx.x;
-  unsigned long long* srec = span_rec(sa, sa.tau_ptr ? *sa.tau_ptr : 0);   // (as k_nat_conv23<true>)
+  unsigned long long* srec = span_rec(sa, sa.tau_ptr ? *sa.tau_ptr : 0);   // (as k_nat_conv23)
   span_begin(srec);
   {
     // ---- the 4 history planes of state b, u8 [cin][84][88]: every dword in flight, then stored ----
@@ -1420,160 +996,6 @@ __global__ void __launch_bounds__(256) k_nat_conv123_b1(StateAddr sa, const uint
   span_end(srec);
 }
 
-// ---------------------------------------------------------------------------------------
-// conv3 dX and conv2 dX fused, one workgroup per sample (network.py's conv2 / conv3 backward):
-//   dl2 = col2im(dl3 W3^T) * (l2 > 0)   M = 81 pixels, N = 64, K = 9 taps x 64 cout
-//   dl1 = col2im(dl2 W2^T) * (l1 > 0)   per stride-2 parity class: M = 100, N = 32, K = 4 real taps x 64
-// dl3 (already masked by l3 > 0) is staged as three bf16 terms on a zero-bordered 11 x 11 grid,
-// so every tap reads a plain fragment (out-of-range sources are the zeros); dl2 goes out (conv2
-// dW's operand) and, as terms on a 1-bordered 11 x 11 grid, into the same LDS for conv2 dX.
-// The weights' dX forms ([term][cin][tap][cout], prepared per rollout) stream from L2.
-// ---------------------------------------------------------------------------------------
-#define DX_R 72                                   // bf16 per grid cell (64 + 8)
-#define DX_G (11 * 11)
-#define DX_T (DX_G * DX_R)                        // bf16 per term
-__global__ void __launch_bounds__(256) k_nat_dx32(const float* __restrict__ dl3, const float* __restrict__ l2,
-                                                  const float* __restrict__ l1, const uint16_t* __restrict__ w3x,
-                                                  const uint16_t* __restrict__ w2x, float* __restrict__ dl2,
-                                                  float* __restrict__ dl1) {
-  __shared__ __attribute__((aligned(16))) uint16_t sm[3 * DX_T];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int i16 = lane & 15, g = lane >> 4;
-  const int64_t b = blockIdx.x;
-  auto zero_all = [&]() {
-    for (int q = tid; q < 3 * DX_T / 8; q += 256) ((uint4*)sm)[q] = make_uint4(0u, 0u, 0u, 0u);
-  };
-  zero_all();
-  __syncthreads();
-  {   // dl3 [49][64] -> cells (y + 2, x + 2)
-    const f32x4* src = (const f32x4*)(dl3 + b * NT_FLAT);
-    for (int q = tid; q < NT_FLAT / 4; q += 256) {
-      const f32x4 v = src[q];
-      const int px = q >> 4, c4 = (q & 15) * 4, y = px / NT3_O, x = px - y * NT3_O;
-      const int cell = (y + 2) * 11 + x + 2;
-      uint32_t lo[3], hi[3];
-      nat_split2<3>(v[0], v[1], lo);
-      nat_split2<3>(v[2], v[3], hi);
-#pragma unroll
-      for (int t = 0; t < 3; ++t) *(uint2*)&sm[t * DX_T + cell * DX_R + c4] = make_uint2(lo[t], hi[t]);
-    }
-  }
-  __syncthreads();
-  // ---- conv3 dX: 6 m-tiles of the 81 l2 pixels x this wave's 16 cin, 18 K steps ----
-  const int n3 = 16 * w + i16;
-  int cell3[6];
-#pragma unroll
-  for (int mt = 0; mt < 6; ++mt) {
-    const int m = min(16 * mt + i16, NT2_P - 1);
-    const int y = m / NT2_O, x = m - y * NT2_O;
-    cell3[mt] = (y + 2) * 11 + x + 2;
-  }
-  f32x4 acc3[6];
-#pragma unroll
-  for (int mt = 0; mt < 6; ++mt) acc3[mt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  const uint16_t* wb3 = w3x + (int64_t)n3 * NT_K3 + 8 * g;
-  bf16x8 bq[3][3];
-  auto ldb3 = [&](int st, bf16x8 (&dst)[3]) {
-#pragma unroll
-    for (int t = 0; t < 3; ++t) dst[t] = *(const bf16x8*)(wb3 + (int64_t)t * NT2_N * NT_K3 + st * 32);
-  };
-  ldb3(0, bq[0]);
-  ldb3(1, bq[1]);
-#pragma unroll
-  for (int st = 0; st < 18; ++st) {
-    if (st + 2 < 18) ldb3(st + 2, bq[(st + 2) % 3]);
-    const int tap = st >> 1, kh = tap / 3, kw = tap - kh * 3;
-    const int off = -(kh * 11 + kw) * DX_R + 32 * (st & 1) + 8 * g;   // source dl3 pixel (y - kh, x - kw)
-#pragma unroll
-    for (int mt = 0; mt < 6; ++mt) {
-      bf16x8 a[3];
-      const uint16_t* ap = sm + cell3[mt] * DX_R + off;
-#pragma unroll
-      for (int t = 0; t < 3; ++t) a[t] = *(const bf16x8*)(ap + t * DX_T);
-      acc3[mt] = c23_mfma6(a, bq[st % 3], acc3[mt]);
-    }
-  }
-  __syncthreads();   // dl3 terms no longer read
-  zero_all();
-  __syncthreads();
-  // dl2 = acc * (l2 > 0): out, and as terms into cells (y + 1, x + 1)
-#pragma unroll
-  for (int mt = 0; mt < 6; ++mt)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int m = 16 * mt + 4 * g + r;
-      if (m < NT2_P) {
-        const int64_t o = (b * NT2_P + m) * NT2_N + n3;
-        const float v = l2[o] > 0.f ? acc3[mt][r] : 0.f;
-        dl2[o] = v;
-        const int y = m / NT2_O, x = m - y * NT2_O, cell = (y + 1) * 11 + x + 1;
-        const float hf = __uint_as_float(nat_bf16_rn(v) << 16);
-        const float r1 = v - hf;
-        const float mf = __uint_as_float(nat_bf16_rn(r1) << 16);
-        sm[0 * DX_T + cell * DX_R + n3] = (uint16_t)(__float_as_uint(hf) >> 16);
-        sm[1 * DX_T + cell * DX_R + n3] = (uint16_t)(__float_as_uint(mf) >> 16);
-        sm[2 * DX_T + cell * DX_R + n3] = (uint16_t)nat_bf16_rn(r1 - mf);
-      }
-    }
-  __syncthreads();
-  // ---- conv2 dX: 4 parity classes x 7 m-tiles (100 pixels of the 10 x 10 class grid) x 2
-  // n-tiles of 16 cin; wave w: n-tile w & 1, m-tiles (w >> 1) + 2 j of every class ----
-  const int n2 = 16 * (w & 1) + i16;
-  const int mh = w >> 1;
-  const uint16_t* wb2 = w2x + (int64_t)n2 * NT_X2 + 8 * g;
-#pragma unroll
-  for (int cl = 0; cl < 4; ++cl) {
-    const int py = cl >> 1, px = cl & 1;
-    int cell2[4];
-    f32x4 acc2[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int m = min(16 * (mh + 2 * j) + i16, 99);
-      const int ci = m / 10, cj = m - ci * 10;
-      cell2[j] = (ci + 1) * 11 + cj + 1;
-      acc2[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    }
-    // K step ks: real tap (th, tw) = ((ks >> 1) >> 1, (ks >> 1) & 1), kernel tap (py + 2 th, px + 2 tw)
-    auto ldb2 = [&](int ks, bf16x8 (&dst)[3]) {
-      const int tp = ks >> 1, th = tp >> 1, tw = tp & 1;
-      const int tap = (py + 2 * th) * 4 + px + 2 * tw;
-#pragma unroll
-      for (int t = 0; t < 3; ++t)
-        dst[t] = *(const bf16x8*)(wb2 + (int64_t)t * NT1_N * NT_X2 + tap * 64 + 32 * (ks & 1));
-    };
-    ldb2(0, bq[0]);
-    ldb2(1, bq[1]);
-#pragma unroll
-    for (int ks = 0; ks < 8; ++ks) {
-      if (ks + 2 < 8) ldb2(ks + 2, bq[(ks + 2) % 3]);
-      const int tp = ks >> 1, th = tp >> 1, tw = tp & 1;
-      const int off = -(th * 11 + tw) * DX_R + 32 * (ks & 1) + 8 * g;   // dl2 pixel (i - th, j - tw)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        if (mh + 2 * j >= 7) continue;                  // (wave-uniform) the class's 7 tiles
-        bf16x8 a[3];
-        const uint16_t* ap = sm + cell2[j] * DX_R + off;
-#pragma unroll
-        for (int t = 0; t < 3; ++t) a[t] = *(const bf16x8*)(ap + t * DX_T);
-        acc2[j] = c23_mfma6(a, bq[ks % 3], acc2[j]);
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      if (mh + 2 * j >= 7) continue;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int m = 16 * (mh + 2 * j) + 4 * g + r;
-        if (m < 100) {
-          const int ci = m / 10, cj = m - ci * 10;
-          const int64_t o = (b * NT1_P + (2 * ci + py) * NT1_O + 2 * cj + px) * NT1_N + n2;
-          dl1[o] = l1[o] > 0.f ? acc2[j][r] : 0.f;
-        }
-      }
-    }
-  }
-}
-
 // the policy / value head of B states (one wave each) on the 512-wide fc output, + the action
 // draw and fused env act when sel.mode >= 0 (agent.py:59-62, network.py:72)
 // (GAME: the device env's game of the fused act, A3C_GAME_*)
@@ -1602,6 +1024,14 @@ struct NatPlan {
   int head_split, ns1, ns2, ns3, kc1, kc2, kc3;
   int64_t dz, dl4, dl3, dl2, dl1, terms, hgrad, hcol, hslab, fccol, s1, s2, s3, c1, c2, c3, g1, g2, g3, wprep, total;
 };
+// workgroups per dW pass (the reduction's slab count): conv1 / conv2 / conv3 768 / 2048 / 768,
+// by whole-bench sweeps (r6dwg2-5, B = 1280): 1.717M against 1.653M for 1536 on all three (the
+// choice by times alone, r6dwg: 62 / 89 / 97 -> 51 / 74 / 81 us against 512); conv1's count is
+// the sensitive one (832: 1.65M, 1536: 1.65M, 640: 1.68M).  DESIGN §4d,
+// profiles/round6/r6dwg_nature_dw_wgs_sweep_ab.txt
+#define NAT_DW_WGS1 768
+#define NAT_DW_WGS2 2048
+#define NAT_DW_WGS3 768
 // the reduction split of a weight-gradient pass: ~target workgroups over its m tiles
 static void dw_split(int64_t R, int mtiles, int target, int& ns, int& kc) {
   int want = target / mtiles;
@@ -1617,17 +1047,9 @@ static NatPlan nat_plan(const NetLayout& L, int64_t B) {
   int64_t o = 0;
   auto take = [&](int64_t floats) { int64_t r = o; o += (floats + 63) & ~(int64_t)63; return r; };
   p.head_split = a3c_gemm_effective_split((int)B, a3c_gemm_plan_split(NT_FC, L.zs, (int)B, 128));
-  // workgroups per dW pass (the reduction's slab count): conv1 / conv2 / conv3 768 / 2048 / 768,
-  // by whole-bench sweeps (r6dwg2-5, B = 1280): 1.717M against 1.653M for 1536 on all three (the
-  // choice by times alone, r6dwg: 62 / 89 / 97 -> 51 / 74 / 81 us against 512); conv1's count is
-  // the sensitive one (832: 1.65M, 1536: 1.65M, 640: 1.68M)
-  static const int wgs = (int)A3C_AB_KNOB("A3C_NAT_DW_WGS", 0);   // > 0: one count for all three
-  static const int wgs1 = (int)A3C_AB_KNOB("A3C_NAT_DW_WGS1", wgs > 0 ? wgs : 768);
-  static const int wgs2 = (int)A3C_AB_KNOB("A3C_NAT_DW_WGS2", wgs > 0 ? wgs : 2048);
-  static const int wgs3 = (int)A3C_AB_KNOB("A3C_NAT_DW_WGS3", wgs > 0 ? wgs : 768);
-  dw_split(B * NT1_P, 2, wgs1, p.ns1, p.kc1);     // M = 256 in 128-row tiles
-  dw_split(B * NT2_P, 8, wgs2, p.ns2, p.kc2);     // M = 512 in 64-row tiles
-  dw_split(B * NT3_P, 9, wgs3, p.ns3, p.kc3);     // M = 576
+  dw_split(B * NT1_P, 2, NAT_DW_WGS1, p.ns1, p.kc1);     // M = 256 in 128-row tiles
+  dw_split(B * NT2_P, 8, NAT_DW_WGS2, p.ns2, p.kc2);     // M = 512 in 64-row tiles
+  dw_split(B * NT3_P, 9, NAT_DW_WGS3, p.ns3, p.kc3);     // M = 576
   p.dz = take(B * L.zs);
   p.dl4 = take(B * NT_FC);
   p.dl3 = take(B * NT_FLAT);
@@ -1652,179 +1074,53 @@ static NatPlan nat_plan(const NetLayout& L, int64_t B) {
   return p;
 }
 
+// the fc forward's split-K: the plan's (an override of 2 or 8 lost, 1.05M / 1.25M against 1.26M:
+// DESIGN §4d, profiles/round6/r6sp1_nature_split_ab.txt)
 static int fc_split(int64_t B) {
-  static const int v = (int)A3C_AB_KNOB("A3C_NAT_FC_SPLIT", 0);   // A/B: > 0 overrides the plan
-  return a3c_gemm_effective_split(NT_FLAT, v > 0 ? v : a3c_gemm_plan_split((int)B, NT_FC, NT_FLAT, 512));
+  return a3c_gemm_effective_split(NT_FLAT, a3c_gemm_plan_split((int)B, NT_FC, NT_FLAT, 512));
 }
-// conv2 / conv3 forward: few output tiles at the rollout's B = E (324 / 196 of 64 x 64 at 256
-// envs), each a long K chain -- conv3 splits K in two so twice the workgroups run half the chain
-// (measured, r6sp1: conv2 28.5 us unsplit vs 30.2 split in 2, conv3 25.3 vs 23.2; 4-way loses on both)
-#define NAT_FWD_SPLIT(LAYER) ((LAYER) == 2 ? 1 : 2)
-#define NAT_FWD_SPLIT_MAX 4
-static int nat_fwd_split_n(int layer) {
-  static const int v = (int)A3C_AB_KNOB("A3C_NAT_FWD_SPLIT", 0);   // A/B: 1..4 for both layers
-  const int n = v > 0 ? v : NAT_FWD_SPLIT(layer);
-  return n > NAT_FWD_SPLIT_MAX ? NAT_FWD_SPLIT_MAX : n;
-}
-// passes on the bf16 matrix cores / with one LDS buffer (bits NAT_*; measured per pass)
-// (every pass on bf16 terms, with one LDS buffer (30 KB instead of 61: room for the other stream's
-// workgroups); two slices in registers for conv1 dW.  Chosen by whole-bench A/B,
-// tools/r6/nat_ab_bench.sh r6pf3 / r6pf4: 1.20M with two buffers on the dW passes although they time
-// faster alone, 1.28M with one, 1.33M with conv3 fwd's one as well).  Bits NAT_FCF / NAT_FCW /
-// NAT_FCX put the fc's forward and backward GEMMs on the same kernels: measured-and-rejected
-// (r6fc1: 1.27M / 1.30M / 1.32M against 1.33M on gemm.hip), so they stay A/B-only)
-#define NAT_BF_DEFAULT ((1 << NAT_C2F) | (1 << NAT_C3F) | (1 << NAT_C3W) | (1 << NAT_C3X) | (1 << NAT_C2W) | \
-                        (1 << NAT_C2X) | (1 << NAT_C1W))
-#define NAT_BF1_DEFAULT ((1 << NAT_C2F) | (1 << NAT_C3F) | (1 << NAT_C3W) | (1 << NAT_C3X) | (1 << NAT_C2W) | \
-                         (1 << NAT_C2X))
-#define NAT_PF2_DEFAULT (1 << NAT_C1W)
-
+// the forward's workspace: the fc's split-K slabs, then room for the prepared block of a per-op call
 static int64_t nat_fwd_slab_floats(int64_t B) {
   const int sp = fc_split(B);
   const int64_t fc = sp > 1 ? (int64_t)sp * B * NT_FC : 0;
-  const int64_t cv = (int64_t)NAT_FWD_SPLIT_MAX * B * (NT2_P * NT2_N > NT3_P * NT3_N ? NT2_P * NT2_N : NT3_P * NT3_N);
-  return ((fc > cv ? fc : cv) + 63) / 64 * 64;
+  return (fc + 63) / 64 * 64;
 }
 int64_t a3c_nat_fwd_ws_floats(int64_t B) { return nat_fwd_slab_floats(B) + A3C_NAT_PREP_BYTES / 4; }
-// which passes run on the bf16 matrix cores (bit NAT_*) and which of those with one LDS buffer
-static bool nat_bf(int pass) {
-  static const long long v = A3C_AB_KNOB("A3C_NAT_BF", NAT_BF_DEFAULT);
-  return (v >> pass) & 1;
-}
-static bool nat_bf1(int pass) {
-  static const long long v = A3C_AB_KNOB("A3C_NAT_BF1", NAT_BF1_DEFAULT);
-  return (v >> pass) & 1;
-}
-static bool nat_pf2(int pass) {     // two slices in flight in registers
-  static const long long v = A3C_AB_KNOB("A3C_NAT_PF2", NAT_PF2_DEFAULT);
-  return (v >> pass) & 1;
-}
-// A/B: 1 = the fc's split-K fold inside the head + screen kernel (one launch per step fewer);
-// measured-and-rejected: 1.29M vs 1.33M (r6fh1) -- 256 workgroups each folding 16 slabs of one
-// row are slower than the wide fold kernel
-static int nat_fold_head() {
-  static const int v = (int)A3C_AB_KNOB("A3C_NAT_FOLD_HEAD", 0);
-  return v;
-}
-static int nat_fuse23() {
-  static const int v = (int)A3C_AB_KNOB("A3C_NAT_FUSE23", 1);   // A/B: 0 = separate conv2 / conv3 passes
-  return v;
-}
-static int nat_fuse123() {
-  static const int v = (int)A3C_AB_KNOB("A3C_NAT_FUSE123", 1);   // A/B: 0 = conv1 its own launch
-  return v;
-}
-// A/B: 1 = conv3 dX + conv2 dX as one per-sample launch (k_nat_dx32): 153 us alone against 85 + 107
-// for the two passes, but the whole bench loses (r6fu: 1.51M vs 1.60M; r6dxp: 1.58M vs 1.64M) --
-// two of its 52 KB workgroups on a CU keep the rollout's conv workgroup off it, and reserving LDS
-// so that only one fits (1.37M) starves the pass itself; so it stays off
-static int nat_fuse_dx() {
-  static const int v = (int)A3C_AB_KNOB("A3C_NAT_FUSE_DX", 0);
-  return v;
-}
-bool a3c_nat_dx_fused() { return nat_fuse_dx() != 0; }
-bool a3c_nat_conv23_fused() { return nat_fuse23() != 0; }
-bool a3c_nat_conv123_fused() { return nat_fuse23() && nat_fuse123(); }
-static int nat_c1_bf() {
-  static const int v = (int)A3C_AB_KNOB("A3C_NAT_C1_BF", 1);   // A/B: 0 = the fp32 MFMA conv1 forward
-  return v;
-}
-
-// a split conv forward: partials into fws, then the fold with bias + ReLU into Y (gemm.hip)
-template <int LAYER>
-static int nat_fwd_split(NatGemm a, float* fws, hipStream_t s) {
-  constexpr int pass = LAYER == 2 ? NAT_C2F : NAT_C3F;
-  const int S = nat_fwd_split_n(LAYER);
-  if (S == 1) {    // one K chain per tile: bias + ReLU in the tile's epilogue
-    a.kchunk = 0;
-    return nat_bf(pass) ? nat_go_bf<NG_FWD, LAYER, 64, 3>(a, 1, s, nat_bf1(pass), nat_pf2(pass)) : nat_go<NG_FWD, LAYER, 64>(a, 1, s);
-  }
-  a.kchunk = ((a.K + S - 1) / S + 31) / 32 * 32;
-  const int ns = (a.K + a.kchunk - 1) / a.kchunk;
-  a.slab = fws;
-  int rc = nat_bf(pass) ? nat_go_bf<NG_FWD, LAYER, 64, 3>(a, (unsigned)ns, s, nat_bf1(pass), nat_pf2(pass))
-                        : nat_go<NG_FWD, LAYER, 64>(a, (unsigned)ns, s);
-  if (rc) return rc;
-  GemmArgs g = {};
-  g.slab = fws; g.nsplit = ns; g.M = a.M; g.N = a.N; g.C = a.Y; g.ldc = a.N; g.epi = EPI_BIAS_RELU; g.bias = a.bias;
-  return a3c_gemm_reduce(g, s);
-}
 int64_t a3c_nat_bwd_ws_floats(const NetLayout& L, int64_t B) { return nat_plan(L, B).total; }
 
-// one pass of the forward (B states) or of the backward (B samples, buffers of the plan in bws)
+// one pass of the forward (B states) or of the backward (B samples, buffers of the plan in bws).
+// The backward tiles, per pass <MODE, LAYER, BN, TA, TB, NBUF, PF>: three bf16 terms per operand in
+// the fp32 mode (conv1 dW's u8 pixels: one), one in the bf16 mode; one LDS buffer
+// (NBUF 1: two time faster alone on the dW passes but cost the concurrent rollout its co-residency,
+// 1.20M against 1.28M, profiles/round6/r6pf3_nature_variant_bench_ab.txt); conv1 dW alone keeps two
+// buffers and two slices in registers (PF 2: 1.33M against 1.28M without,
+// r6pf4_nature_knob_bench_ab.txt).  The fc's GEMMs on these tiles lost to gemm.hip (r6fc1_nature_fc_bf_ab.txt: 1.27M / 1.30M
+// / 1.32M against 1.33M); conv3 dX + conv2 dX as one per-sample kernel lost too (153 us alone against
+// 85 + 107, but 1.51M against 1.60M: its 52 KB workgroups keep the rollout's conv workgroups off
+// their CUs, r6fu_nature_fusion_ab.txt, r6dxp_nature_dx_fc_ab.txt).  All in DESIGN §4d.
 int a3c_nat_pass_launch(int pass, const NetLayout& L, const float* P, const StateAddr& sa, int64_t B, const float* l1,
                         const float* l2, const float* l3, const float* l4, const uint16_t* w1t, float* fws,
                         float* bws, hipStream_t s) {
-  NatGemm a = {};
-  // the bf16 mode: its own forward kernel whatever the A/B knobs say, the one-term tiles
-  // for the five backward passes (k_nat_dx32 has no one-term form)
   const bool b1 = L.prec == A3C_PREC_BF16;
-  if (b1 && !w1t && pass <= NAT_C3F)
-    return a3c_set_error(A3C_ERR_INVALID, "a3c_nat_pass_launch", "bf16 mode: the forward needs the prepared block");
+  if (!w1t && pass >= NAT_C1F && pass <= NAT_C3F)
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_nat_pass_launch", "the conv forward needs the prepared block");
   switch (pass) {
     case NAT_C1F:
-      if (b1) return 0;                                     // inside NAT_C2F's launch
-      if (w1t && nat_fuse23() && nat_fuse123()) return 0;   // inside NAT_C2F's launch
-      if (w1t && nat_c1_bf()) {
-        const int M = (int)(B * NT1_P);
-        if (nat_bf1(NAT_C1F))
-          hipLaunchKernelGGL(k_nat_conv1_bf<1>, dim3((unsigned)((M + 127) / 128)), dim3(256), 0, s, sa, w1t,
-                             P + L.off[N_L1B], (float*)l1, M, 1.0f / 255.0f);
-        else
-          hipLaunchKernelGGL(k_nat_conv1_bf<2>, dim3((unsigned)((M + 127) / 128)), dim3(256), 0, s, sa, w1t,
-                             P + L.off[N_L1B], (float*)l1, M, 1.0f / 255.0f);
-        A3C_CHECK(hipGetLastError());
-        return 0;
-      }
-      a.sa = sa;
-      a.Wt = P + L.off[N_L1W]; a.bias = P + L.off[N_L1B]; a.Y = (float*)l1;
-      a.M = (int)(B * NT1_P); a.N = NT1_N; a.K = NT_K1; a.scale = 1.0f / 255.0f;
-      return nat_go<NG_FWD1, 1, 32>(a, 1, s);
-    case NAT_C2F:
-      if (b1) {   // conv1 + conv2 + conv3, one term per operand; NAT_C1F and NAT_C3F then empty
+    case NAT_C3F:   // inside NAT_C2F's launch
+      return 0;
+    case NAT_C2F:   // conv1 + conv2 + conv3, one workgroup per state
+      if (b1)
         hipLaunchKernelGGL(k_nat_conv123_b1, dim3((unsigned)B), dim3(256), 0, s, sa, w1t, P + L.off[N_L1B],
                            w1t + A3C_NAT_W2T_OFF / 2, P + L.off[N_L2B], w1t + A3C_NAT_W3T_OFF / 2, P + L.off[N_L3B],
                            (float*)l1, (float*)l2, (float*)l3, 1.0f / 255.0f);
-        A3C_CHECK(hipGetLastError());
-        return 0;
-      }
-      if (w1t && nat_fuse23()) {   // conv2 + conv3 (+ conv1) in one launch; NAT_C3F (NAT_C1F) then empty
-        if (nat_fuse123())
-          hipLaunchKernelGGL(k_nat_conv23<true>, dim3((unsigned)B), dim3(256), 0, s, (const float*)nullptr,
-                             w1t + A3C_NAT_W2T_OFF / 2, P + L.off[N_L2B], w1t + A3C_NAT_W3T_OFF / 2,
-                             P + L.off[N_L3B], (float*)l2, (float*)l3, sa, w1t, P + L.off[N_L1B], (float*)l1,
-                             1.0f / 255.0f);
-        else
-          hipLaunchKernelGGL(k_nat_conv23<false>, dim3((unsigned)B), dim3(256), 0, s, l1, w1t + A3C_NAT_W2T_OFF / 2,
-                             P + L.off[N_L2B], w1t + A3C_NAT_W3T_OFF / 2, P + L.off[N_L3B], (float*)l2, (float*)l3,
-                             sa, (const uint16_t*)nullptr, (const float*)nullptr, (float*)nullptr, 0.f);
-        A3C_CHECK(hipGetLastError());
-        return 0;
-      }
-      a.X = l1; a.Wt = P + L.off[N_L2W]; a.bias = P + L.off[N_L2B]; a.Y = (float*)l2;
-      a.M = (int)(B * NT2_P); a.N = NT2_N; a.K = NT_K2;
-      return nat_fwd_split<2>(a, fws, s);
-    case NAT_C3F:
-      if (b1 || (w1t && nat_fuse23())) return 0;
-      a.X = l2; a.Wt = P + L.off[N_L3W]; a.bias = P + L.off[N_L3B]; a.Y = (float*)l3;
-      a.M = (int)(B * NT3_P); a.N = NT3_N; a.K = NT_K3;
-      return nat_fwd_split<3>(a, fws, s);
+      else
+        hipLaunchKernelGGL(k_nat_conv23, dim3((unsigned)B), dim3(256), 0, s, w1t + A3C_NAT_W2T_OFF / 2,
+                           P + L.off[N_L2B], w1t + A3C_NAT_W3T_OFF / 2, P + L.off[N_L3B], (float*)l2, (float*)l3, sa,
+                           w1t, P + L.off[N_L1B], (float*)l1, 1.0f / 255.0f);
+      A3C_CHECK(hipGetLastError());
+      return 0;
     case NAT_FCF: {
       if (fws == nullptr) return a3c_set_error(A3C_ERR_INVALID, "a3c_nat_pass_launch", "fc: no slab workspace");
-      if (nat_bf(NAT_FCF)) {   // bf16 terms: K split over grid z into fws slabs, fold with bias + ReLU
-        a.X = l3; a.Wt = P + L.off[N_FCW]; a.bias = P + L.off[N_FCB]; a.Y = (float*)l4;
-        a.M = (int)B; a.N = NT_FC; a.K = NT_FLAT;
-        const int ns = fc_split(B);
-        if (ns <= 1) return nat_go_bf<NG_FWD, 4, 64, 3>(a, 1, s, nat_bf1(NAT_FCF), nat_pf2(NAT_FCF));
-        a.kchunk = ((a.K + ns - 1) / ns + 31) / 32 * 32;
-        const int nz = (a.K + a.kchunk - 1) / a.kchunk;
-        a.slab = fws;
-        int rc = nat_go_bf<NG_FWD, 4, 64, 3>(a, (unsigned)nz, s, nat_bf1(NAT_FCF), nat_pf2(NAT_FCF));
-        if (rc) return rc;
-        GemmArgs g = {};
-        g.slab = fws; g.nsplit = nz; g.M = a.M; g.N = a.N; g.C = a.Y; g.ldc = a.N; g.epi = EPI_BIAS_RELU; g.bias = a.bias;
-        return a3c_gemm_reduce(g, s);
-      }
       // l4 = relu(l3 W + b) (network.py:41-42, ops.py:41-44): split-K slabs, the fold applies the epilogue
       GemmArgs gf = {};
       gf.A = l3; gf.lda = NT_FLAT;
@@ -1839,44 +1135,31 @@ int a3c_nat_pass_launch(int pass, const NetLayout& L, const float* P, const Stat
       break;
   }
   const NatPlan p = nat_plan(L, B);
+  NatGemm a = {};
   switch (pass) {
     case NAT_C3W:     // dW3 (+ db3) over the (sample, pixel) rows
       a.X = l2; a.dY = bws + p.dl3; a.slab = bws + p.s3; a.colsum = bws + p.c3;
       a.M = NT_K3; a.N = NT3_N; a.K = (int)(B * NT3_P); a.kchunk = p.kc3;
-      if (b1) return nat_go_bf<NG_DW, 3, 64, 1, 1>(a, (unsigned)p.ns3, s, nat_bf1(NAT_C3W), nat_pf2(NAT_C3W));
-      return nat_bf(NAT_C3W) ? nat_go_bf<NG_DW, 3, 64, 3>(a, (unsigned)p.ns3, s, nat_bf1(NAT_C3W), nat_pf2(NAT_C3W))
-                           : nat_go<NG_DW, 3, 64>(a, (unsigned)p.ns3, s);
+      return b1 ? nat_go_bf<NG_DW, 3, 64, 1, 1, 1, 1>(a, (unsigned)p.ns3, s)
+                : nat_go_bf<NG_DW, 3, 64, 3, 3, 1, 1>(a, (unsigned)p.ns3, s);
     case NAT_C3X:     // dl2 = col2im(dl3 W3^T) * (l2 > 0)
-      if (!b1 && w1t && nat_fuse_dx()) {   // and dl1 in the same launch (k_nat_dx32); NAT_C2X then empty
-        hipLaunchKernelGGL(k_nat_dx32, dim3((unsigned)B), dim3(256), 0, s, bws + p.dl3, l2, l1,
-                           w1t + A3C_NAT_W3X_OFF / 2, w1t + A3C_NAT_W2X_OFF / 2, bws + p.dl2, bws + p.dl1);
-        A3C_CHECK(hipGetLastError());
-        return 0;
-      }
       a.X = l2; a.dY = bws + p.dl3; a.Wt = P + L.off[N_L3W]; a.Y = bws + p.dl2;
       a.M = (int)(B * NT2_P); a.N = NT2_N; a.K = 3 * 3 * NT3_N;
-      if (b1) return nat_go_bf<NG_DX, 3, 64, 1, 1>(a, 1, s, nat_bf1(NAT_C3X), nat_pf2(NAT_C3X));
-      return nat_bf(NAT_C3X) ? nat_go_bf<NG_DX, 3, 64, 3>(a, 1, s, nat_bf1(NAT_C3X), nat_pf2(NAT_C3X))
-                           : nat_go<NG_DX, 3, 64>(a, 1, s);
+      return b1 ? nat_go_bf<NG_DX, 3, 64, 1, 1, 1, 1>(a, 1, s) : nat_go_bf<NG_DX, 3, 64, 3, 3, 1, 1>(a, 1, s);
     case NAT_C2W:
       a.X = l1; a.dY = bws + p.dl2; a.slab = bws + p.s2; a.colsum = bws + p.c2;
       a.M = NT_K2; a.N = NT2_N; a.K = (int)(B * NT2_P); a.kchunk = p.kc2;
-      if (b1) return nat_go_bf<NG_DW, 2, 64, 1, 1>(a, (unsigned)p.ns2, s, nat_bf1(NAT_C2W), nat_pf2(NAT_C2W));
-      return nat_bf(NAT_C2W) ? nat_go_bf<NG_DW, 2, 64, 3>(a, (unsigned)p.ns2, s, nat_bf1(NAT_C2W), nat_pf2(NAT_C2W))
-                           : nat_go<NG_DW, 2, 64>(a, (unsigned)p.ns2, s);
+      return b1 ? nat_go_bf<NG_DW, 2, 64, 1, 1, 1, 1>(a, (unsigned)p.ns2, s)
+                : nat_go_bf<NG_DW, 2, 64, 3, 3, 1, 1>(a, (unsigned)p.ns2, s);
     case NAT_C2X:     // dl1 = col2im(dl2 W2^T) * (l1 > 0), per stride-2 parity class
-      if (!b1 && w1t && nat_fuse_dx()) return 0;
       a.X = l1; a.dY = bws + p.dl2; a.Wt = P + L.off[N_L2W]; a.Y = bws + p.dl1;
       a.M = (int)(B * (NT1_O / 2) * (NT1_O / 2)); a.N = NT1_N; a.K = 2 * 2 * NT2_N;
-      if (b1) return nat_go_bf<NG_DX, 2, 32, 1, 1>(a, 4, s, nat_bf1(NAT_C2X), nat_pf2(NAT_C2X));
-      return nat_bf(NAT_C2X) ? nat_go_bf<NG_DX, 2, 32, 3>(a, 4, s, nat_bf1(NAT_C2X), nat_pf2(NAT_C2X))
-                           : nat_go<NG_DX, 2, 32>(a, 4, s);
+      return b1 ? nat_go_bf<NG_DX, 2, 32, 1, 1, 1, 1>(a, 4, s) : nat_go_bf<NG_DX, 2, 32, 3, 3, 1, 1>(a, 4, s);
     case NAT_C1W:     // dW1 (+ db1) from the u8 planes (the input needs no gradient)
       a.sa = sa; a.dY = bws + p.dl1; a.slab = bws + p.s1; a.colsum = bws + p.c1;
       a.M = NT_K1; a.N = NT1_N; a.K = (int)(B * NT1_P); a.kchunk = p.kc1;
-      if (b1) return nat_go_bf<NG_DW1, 1, 32, 1, 1>(a, (unsigned)p.ns1, s, nat_bf1(NAT_C1W), nat_pf2(NAT_C1W));
-      return nat_bf(NAT_C1W) ? nat_go_bf<NG_DW1, 1, 32, 1>(a, (unsigned)p.ns1, s, nat_bf1(NAT_C1W), nat_pf2(NAT_C1W))
-                           : nat_go<NG_DW1, 1, 32>(a, (unsigned)p.ns1, s);
+      return b1 ? nat_go_bf<NG_DW1, 1, 32, 1, 1, 2, 2>(a, (unsigned)p.ns1, s)
+                : nat_go_bf<NG_DW1, 1, 32, 1, 3, 2, 2>(a, (unsigned)p.ns1, s);
     default:
       return a3c_set_error(A3C_ERR_INVALID, "a3c_nat_pass_launch", "unknown pass");
   }
@@ -1888,20 +1171,15 @@ __global__ void k_nat_prep(const int64_t* __restrict__ tau_src, int64_t* __restr
   if (tau_dst) *tau_dst = *tau_src;
   if (sig) (void)__hip_atomic_fetch_add(sig, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
+// the three forward forms: three terms each, or rn(W) alone in the bf16 mode (the backward tiles
+// split or round W at their LDS store)
 static int nat_w1_terms_launch(const NetLayout& L, const float* P, uint16_t* w1t, hipStream_t s) {
-  // (the forward forms for k_nat_conv23, the dX forms only for k_nat_dx32)
-  if (L.prec == A3C_PREC_BF16) {   // rn(W) alone: the three forward forms (the dX tiles round W at their LDS store)
-    const int n1 = NT1_N * NT_K1 + NT2_N * NT_K2 + NT3_N * NT_K3;
-    hipLaunchKernelGGL(k_nat_w_terms<1>, dim3((n1 + 255) / 256), dim3(256), 0, s, P + L.off[N_L1W], P + L.off[N_L2W],
-                       P + L.off[N_L3W], w1t, 1);
-    A3C_CHECK(hipGetLastError());
-    return 0;
-  }
-  const int all = nat_fuse23() || nat_fuse_dx() ? 1 : 0;
-  const int n = NT1_N * NT_K1 + (all ? NT2_N * NT_K2 + NT3_N * NT_K3 : 0) +
-                (nat_fuse_dx() ? NT1_N * NT_X2 + NT2_N * NT_K3 : 0);
-  hipLaunchKernelGGL(k_nat_w_terms<3>, dim3((n + 255) / 256), dim3(256), 0, s, P + L.off[N_L1W], P + L.off[N_L2W],
-                     P + L.off[N_L3W], w1t, all);
+  const int n = NT1_N * NT_K1 + NT2_N * NT_K2 + NT3_N * NT_K3;
+  const dim3 grid((n + 255) / 256);
+  if (L.prec == A3C_PREC_BF16)
+    hipLaunchKernelGGL(k_nat_w_terms<1>, grid, dim3(256), 0, s, P + L.off[N_L1W], P + L.off[N_L2W], P + L.off[N_L3W], w1t);
+  else
+    hipLaunchKernelGGL(k_nat_w_terms<3>, grid, dim3(256), 0, s, P + L.off[N_L1W], P + L.off[N_L2W], P + L.off[N_L3W], w1t);
   A3C_CHECK(hipGetLastError());
   return 0;
 }
@@ -1932,26 +1210,13 @@ int a3c_nat_forward_launch(const NetLayout& L, const FwdArgs& a, hipStream_t s, 
     if (int rc = nat_w1_terms_launch(L, P, t, s)) return rc;
     w1t = t;
   }
-  const bool step_tail = sel.mode >= 0 && sel.env_on && sel.pool;   // the engine's rollout step
-  const int fcs = fc_split(B);
-  // (the play step keeps the fc's own fold: its tail is the 512-wide play head alone)
-  const bool fold_in_head = step_tail && fcs > 1 && !nat_bf(NAT_FCF) && nat_fold_head() && !play_frozen;
-  for (int pass = NAT_C1F; pass <= (fold_in_head ? NAT_C3F : NAT_FCF); ++pass) {
+  for (int pass = NAT_C1F; pass <= NAT_FCF; ++pass) {
     const int rc = a3c_nat_pass_launch(pass, L, P, a.sa, B, a.act_l1, a.act_l2, l3, l4, w1t, ws, nullptr, s);
     if (rc) return rc;
   }
-  if (fold_in_head) {   // the fc's K-slice partials, folded by the head + act + screen kernel
-    GemmArgs gf = {};
-    gf.A = l3; gf.lda = NT_FLAT;
-    gf.B = P + L.off[N_FCW]; gf.ldb = NT_FC;
-    gf.C = l4; gf.ldc = NT_FC;
-    gf.M = (int)B; gf.N = NT_FC; gf.K = NT_FLAT;
-    gf.epi = EPI_BIAS_RELU; gf.bias = P + L.off[N_FCB];
-    gf.nsplit = fcs; gf.slab = ws; gf.defer_reduce = 1;
-    if (int rc = a3c_gemm(true, true, gf, s)) return rc;
-    return a3c_head_screen_fold_launch(ws, fcs, P + L.off[N_FCB], l4, P + L.off[N_HW], P + L.off[N_HB],
-                                       P + L.off[N_VW], P + L.off[N_VB], L.A, L.zs, B, z, sel, s, m);
-  }
+  // the step tail; the fc's own fold stays in front of it (folding inside the head + screen kernel
+  // lost, 1.29M against 1.33M: DESIGN §4d, profiles/round6/r6fh1_nature_fold_in_head_ab.txt)
+  const bool step_tail = sel.mode >= 0 && sel.env_on && sel.pool;   // the engine's rollout step
   if (play_frozen)   // Agent.play's step tail (agent.py:371-377)
     return a3c_head_screen_play_launch(NT_FC, l4, P + L.off[N_HW], P + L.off[N_HB], P + L.off[N_VW], P + L.off[N_VB],
                                        L.A, L.zs, B, z, sel, play_frozen, s, m);
@@ -2024,12 +1289,6 @@ int a3c_nat_backward_launch(const NetLayout& L, const BwdArgs& args, hipStream_t
   rc = a3c_gemm(false, true, gh, s);
   if (rc) return rc;
   // fc weights: dW[3136][512] = l3^T dl4 straight into grads (split-K inside the workgroups), db = colsum
-  if (nat_bf(NAT_FCW)) {   // bf16 terms, one reduction chain per tile straight into grads (+ db)
-    NatGemm a = {};
-    a.X = l3; a.dY = dl4; a.slab = grads + L.off[N_FCW]; a.colsum = ws + p.fccol;
-    a.M = NT_FLAT; a.N = NT_FC; a.K = (int)B; a.kchunk = (int)B;
-    rc = nat_go_bf<NG_DW, 4, 64, 3>(a, 1, s, nat_bf1(NAT_FCW), nat_pf2(NAT_FCW));
-  } else {
   GemmArgs gf = {};
   gf.A = l3; gf.lda = NT_FLAT;
   gf.B = dl4; gf.ldb = NT_FC;
@@ -2037,15 +1296,8 @@ int a3c_nat_backward_launch(const NetLayout& L, const BwdArgs& args, hipStream_t
   gf.M = NT_FLAT; gf.N = NT_FC; gf.K = (int)B;
   gf.epi = EPI_STORE; gf.colsum = ws + p.fccol; gf.wg_split = 4; gf.xcd = 1;
   rc = a3c_gemm(false, true, gf, s);
-  }
   if (rc) return rc;
   // dl3 = (dl4 W^T) * (l3 > 0)
-  if (nat_bf(NAT_FCX)) {
-    NatGemm a = {};
-    a.X = l3; a.dY = dl4; a.Wt = P + L.off[N_FCW]; a.Y = ws + p.dl3;
-    a.M = (int)B; a.N = NT_FLAT; a.K = NT_FC;
-    rc = nat_go_bf<NG_DX, 4, 64, 3>(a, 1, s, nat_bf1(NAT_FCX), nat_pf2(NAT_FCX));
-  } else {
   GemmArgs gd = {};
   gd.A = dl4; gd.lda = NT_FC;
   gd.B = P + L.off[N_FCW]; gd.ldb = NT_FC;
@@ -2053,7 +1305,6 @@ int a3c_nat_backward_launch(const NetLayout& L, const BwdArgs& args, hipStream_t
   gd.M = (int)B; gd.N = NT_FLAT; gd.K = NT_FC;
   gd.epi = EPI_MASK; gd.mask = l3; gd.ldm = NT_FLAT; gd.nsplit = 1;
   rc = a3c_gemm(true, false, gd, s);
-  }
   if (rc) return rc;
   for (int pass = NAT_C3W; pass <= NAT_C1W; ++pass) {
     rc = a3c_nat_pass_launch(pass, L, P, args.sa, B, args.act_l1, args.act_l2, l3, l4, wt, nullptr, ws, s);

@@ -841,43 +841,9 @@ __global__ void __launch_bounds__(256) k_select(const float* __restrict__ z, int
   if (lane == 0) sel.actions[b] = a;
 }
 
-// the nature trunk's rollout step tail with the fc's split-K fold in front: the workgroup folds
-// env b's row of the nsplit K-slice partials (slice order, + bias, ReLU: k_reduce_slabs' order, so
-// the row is bit-identical to the separate fold), keeps it in LDS for the head and writes it out for
-// the backward -- one launch per step fewer
-template <int HS_THREADS, int W, int GAME = A3C_GAME_SYNTH>
-__global__ void __launch_bounds__(HS_THREADS) k_head_screen_fold(const float* __restrict__ part, int nsplit,
-                                                                 int64_t pstride, const float* __restrict__ fbias,
-                                                                 float* __restrict__ hout,
-                                                                 const float* __restrict__ Wp,
-                                                                 const float* __restrict__ bp,
-                                                                 const float* __restrict__ Wv,
-                                                                 const float* __restrict__ bv, int A, int zs,
-                                                                 float* __restrict__ z, HeadSelect sel) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  __shared__ __attribute__((aligned(16))) float hrow[W];
-  const int64_t b = blockIdx.x;
-  const int64_t tau = *sel.tau_ptr + sel.tau_add;
-  for (int i = threadIdx.x; i < W; i += HS_THREADS) {
-    const float v = fmaxf(sum_strided(part + b * W + i, nsplit, pstride) + fbias[i], 0.f);
-    hrow[i] = v;
-    hout[b * W + i] = v;
-  }
-  __syncthreads();
-  const int32_t frame = head_act_env<W, false, GAME>(nullptr, Wp, bp, Wv, bv, A, zs, z, sel, b, tau, nullptr, hrow);
-  uint8_t* slot = sel.ring + b * sel.R * PLANE + ((tau + 1) % sel.R) * PLANE;
-  if (sel.frame84)
-    atari::copy_frame84<HS_THREADS>(sel.pool + (int64_t)frame * PLANE, slot);
-  else
-    atari::screen_frame<HS_THREADS>(sel.pool + (int64_t)frame * (atari::IH * atari::IW * 3), slot, smem, nullptr);
-}
-
 // The Catch instantiations (GAME = A3C_GAME_CATCH) of the kernels that step a device env, and their
 // launches, are at the end of this file, behind every default-game kernel.
 static bool catch_on(const HeadSelect& sel) { return sel.env_on && sel.envp.game == A3C_GAME_CATCH; }
-static int catch_fold_launch(const float* part, int nsplit, const float* fbias, float* l4, const float* Wp,
-                             const float* bp, const float* Wv, const float* bv, int A, int zs, int64_t B, float* z,
-                             const HeadSelect& sel, int nt, hipStream_t s);
 static int catch_head_screen_launch(int W, const float* h, const float* Wp, const float* bp, const float* Wv,
                                     const float* bv, int A, int zs, int64_t B, float* z, const HeadSelect& sel, int nt,
                                     hipStream_t s);
@@ -889,23 +855,6 @@ static int catch_conv12_launch(const float* h, const float* Wp, const float* bp,
 static int catch_head_fwd_launch(const float* h, const float* Wp, const float* bp, const float* Wv, const float* bv, int A,
                                  int zs, int64_t B, float* z, const HeadSelect& sel, hipStream_t s);
 static void catch_set_smem();
-
-int a3c_head_screen_fold_launch(const float* part, int nsplit, const float* fbias, float* l4, const float* Wp,
-                                const float* bp, const float* Wv, const float* bv, int A, int zs, int64_t B, float* z,
-                                const HeadSelect& sel, hipStream_t s, const LaunchMode& m) {
-  static const int env_t = (int)A3C_AB_KNOB("A3C_HS_THREADS", 0);
-  const int nt = env_t ? env_t : (m.shared_gpu ? 512 : 1024);
-  const int64_t ps = B * 512;
-  if (catch_on(sel)) return catch_fold_launch(part, nsplit, fbias, l4, Wp, bp, Wv, bv, A, zs, B, z, sel, nt, s);
-  if (nt == 1024)
-    hipLaunchKernelGGL((k_head_screen_fold<1024, 512>), dim3((unsigned)B), dim3(1024), SCREEN_FRAME_SMEM, s, part,
-                       nsplit, ps, fbias, l4, Wp, bp, Wv, bv, A, zs, z, sel);
-  else
-    hipLaunchKernelGGL((k_head_screen_fold<512, 512>), dim3((unsigned)B), dim3(512), SCREEN_FRAME_SMEM, s, part,
-                       nsplit, ps, fbias, l4, Wp, bp, Wv, bv, A, zs, z, sel);
-  A3C_CHECK(hipGetLastError());
-  return 0;
-}
 
 // the same for the nature trunk's 512-wide fc output (nature.hip's rollout steps)
 int a3c_head_screen_wide_launch(const float* l4, const float* Wp, const float* bp, const float* Wv, const float* bv,
@@ -1119,10 +1068,6 @@ void a3c_conv12_set_smem() {
   (void)hipFuncSetAttribute((const void*)k_head_screen<512, 512>, hipFuncAttributeMaxDynamicSharedMemorySize,
                             SCREEN_FRAME_SMEM);
   (void)hipFuncSetAttribute((const void*)k_head_screen<1024, 512>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            SCREEN_FRAME_SMEM);
-  (void)hipFuncSetAttribute((const void*)k_head_screen_fold<512, 512>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            SCREEN_FRAME_SMEM);
-  (void)hipFuncSetAttribute((const void*)k_head_screen_fold<1024, 512>, hipFuncAttributeMaxDynamicSharedMemorySize,
                             SCREEN_FRAME_SMEM);
   (void)hipFuncSetAttribute((const void*)k_head_screen_play<512, FC>, hipFuncAttributeMaxDynamicSharedMemorySize,
                             SCREEN_FRAME_SMEM);
@@ -1614,20 +1559,6 @@ WGLOG_BIND(a3c_wglog_bind_fwd)
 // sizes and LDS of the default-game launches above; nt: the 512 / 1024 threads they chose).
 // ---------------------------------------------------------------------------------------
 #define CG A3C_GAME_CATCH
-static int catch_fold_launch(const float* part, int nsplit, const float* fbias, float* l4, const float* Wp,
-                             const float* bp, const float* Wv, const float* bv, int A, int zs, int64_t B, float* z,
-                             const HeadSelect& sel, int nt, hipStream_t s) {
-  const int64_t ps = B * 512;
-  if (nt == 1024)
-    hipLaunchKernelGGL((k_head_screen_fold<1024, 512, CG>), dim3((unsigned)B), dim3(1024), SCREEN_FRAME_SMEM, s, part,
-                       nsplit, ps, fbias, l4, Wp, bp, Wv, bv, A, zs, z, sel);
-  else
-    hipLaunchKernelGGL((k_head_screen_fold<512, 512, CG>), dim3((unsigned)B), dim3(512), SCREEN_FRAME_SMEM, s, part,
-                       nsplit, ps, fbias, l4, Wp, bp, Wv, bv, A, zs, z, sel);
-  A3C_CHECK(hipGetLastError());
-  return 0;
-}
-
 static int catch_head_screen_launch(int W, const float* h, const float* Wp, const float* bp, const float* Wv,
                                     const float* bv, int A, int zs, int64_t B, float* z, const HeadSelect& sel, int nt,
                                     hipStream_t s) {
@@ -1692,8 +1623,6 @@ static void catch_set_smem() {
   CSM((k_head_screen<1024, FC, CG>), SCREEN_FRAME_SMEM);
   CSM((k_head_screen<512, 512, CG>), SCREEN_FRAME_SMEM);
   CSM((k_head_screen<1024, 512, CG>), SCREEN_FRAME_SMEM);
-  CSM((k_head_screen_fold<512, 512, CG>), SCREEN_FRAME_SMEM);
-  CSM((k_head_screen_fold<1024, 512, CG>), SCREEN_FRAME_SMEM);
   CSM((k_head_screen_play<512, FC, CG>), SCREEN_FRAME_SMEM);
   CSM((k_head_screen_play<1024, FC, CG>), SCREEN_FRAME_SMEM);
   CSM((k_head_screen_play<512, 512, CG>), SCREEN_FRAME_SMEM);

@@ -17,8 +17,8 @@ Sources (async-rl-tensorflow_amd/csrc):
   nature.h   the nature trunk's geometry, A3C_NAT_PREP_BYTES
   nature.hip   dw_split, nat_plan, fc_split, nat_fwd_slab_floats, a3c_nat_fwd_ws_floats; k_nat_gemm_bf's K slices
   lstm.hip   lstm_ws
-The plans' A/B environment knobs (A3C_CB_NWG, A3C_NAT_DW_WGS*, A3C_NAT_FC_SPLIT) are taken at
-their defaults."""
+The NIPS plan's A/B environment knob (A3C_CB_NWG) is taken at its default; the nature plans have
+no knobs."""
 from collections import namedtuple
 
 # gemm.hip:12-14
@@ -49,22 +49,18 @@ FC_WKS_MAXB = 2560                       # net_bwd.hip:977-981 fc_wks_on: the ov
 #                                          splits K inside its workgroups (wg_split = 4) up to this B
 LSTM_TILE = 16                         # lstm.hip LT: envs per k_lstm_fwd / k_lstm_bptt_step tile
 
-# nature.h:10-25, 69-76
+# nature.h:10-25, 67-70
 NT1_N, NT1_P, NT2_N, NT2_P, NT3_N, NT3_P = 32, 400, 64, 81, 64, 49
 NT_K1, NT_K2, NT_K3 = 8 * 8 * HIST, 4 * 4 * NT1_N, 3 * 3 * NT2_N        # 256, 512, 576
 NT_FLAT, NT_FC = NT3_P * NT3_N, 512
 NT_A1, NT_A2 = NT1_P * NT1_N, NT2_P * NT2_N
-NT_X2 = 4 * 4 * NT2_N
 NAT_W2T_OFF = 3 * NT1_N * NT_K1 * 2
 NAT_W3T_OFF = NAT_W2T_OFF + 3 * NT2_N * NT_K2 * 2
-NAT_W2X_OFF = NAT_W3T_OFF + 3 * NT3_N * NT_K3 * 2
-NAT_W3X_OFF = NAT_W2X_OFF + 3 * NT1_N * NT_X2 * 2
-NAT_PREP_BYTES = NAT_W3X_OFF + 3 * NT2_N * NT_K3 * 2
-NAT_GROUPS = 8                           # nature.hip:1600
-NAT_DW_WGS = (768, 2048, 768)            # nature.hip:1625-1627
-NAT_DW_MTILES = (2, 8, 9)                # nature.hip:1628-1630
-NAT_FWD_SPLIT_MAX = 4                    # nature.hip:1663
-NAT_BK = 32                              # nature.hip:405 k_nat_gemm_bf: BK, the rows of one K slice
+NAT_PREP_BYTES = NAT_W3T_OFF + 3 * NT3_N * NT_K3 * 2
+NAT_GROUPS = 8                           # nature.hip:1022
+NAT_DW_WGS = (768, 2048, 768)            # nature.hip:1032-1034
+NAT_DW_MTILES = (2, 8, 9)                # nature.hip:1050-1052
+NAT_BK = 32                              # nature.hip:146 k_nat_gemm_bf: BK, the rows of one K slice
 
 
 def cdiv(a, b):
@@ -152,7 +148,7 @@ def workspace_bytes(A, algo, B):
 
 
 def dw_split(R, mtiles, target):
-    """nature.hip:1606-1614 dw_split -> (ns, kc)."""
+    """nature.hip:1036-1044 dw_split -> (ns, kc)."""
     want = max(target // mtiles, 1)
     per = cdiv(R, want)
     per = max(cdiv(per, 32) * 32, 32)
@@ -163,7 +159,7 @@ NatPlan = namedtuple('NatPlan', 'B head_split ns kc off regions total')
 
 
 def nat_plan(A, B):
-    """nature.hip:1615-1653 nat_plan; ns / kc are the (conv1, conv2, conv3) triples."""
+    """nature.hip:1045-1075 nat_plan; ns / kc are the (conv1, conv2, conv3) triples."""
     z = zs('a3c', A)
     head_split = gemm_effective_split(B, gemm_plan_split(NT_FC, z, B, 128))
     sp = [dw_split(B * P, m, t) for P, m, t in zip((NT1_P, NT2_P, NT3_P), NAT_DW_MTILES, NAT_DW_WGS)]
@@ -186,7 +182,7 @@ NatDwSlices = namedtuple('NatDwSlices', 'kc slices last_rows last_slice_rows')
 
 
 def nat_dw_slices(A, B):
-    """k_nat_gemm_bf's K loop over a dW chunk (nature.hip:432-433 kbeg / kend, :653-707 the three loop forms), per
+    """k_nat_gemm_bf's K loop over a dW chunk (nature.hip:172-173 kbeg / kend, :383-437 the three loop forms), per
     (conv1, conv2, conv3) pass: the slices of NAT_BK rows a full chunk holds (kc // NAT_BK: dw_split makes kc whole
     slices), the rows of the last chunk (kend stops at K = B * P) and the rows of that chunk's last slice (fewer
     than NAT_BK: the loads' `r >= kend` leaves the rest of the slice zero)."""
@@ -199,20 +195,19 @@ def nat_dw_slices(A, B):
 
 
 def nat_fc_split(B):
-    """nature.hip:1655-1658 fc_split: the forward fc GEMM (M = B, N = 512, K = 3136)."""
+    """nature.hip:1079-1081 fc_split: the forward fc GEMM (M = B, N = 512, K = 3136)."""
     return gemm_effective_split(NT_FLAT, gemm_plan_split(B, NT_FC, NT_FLAT, 512))
 
 
 def nat_fwd_ws_floats(B):
-    """nature.hip:1682-1688 nat_fwd_slab_floats + the prepared weights."""
+    """nature.hip:1083-1088 nat_fwd_slab_floats (the fc's split-K slabs) + the prepared weights."""
     sp = nat_fc_split(B)
     fc = sp * B * NT_FC if sp > 1 else 0
-    cv = NAT_FWD_SPLIT_MAX * B * max(NT2_P * NT2_N, NT3_P * NT3_N)
-    return cdiv(max(fc, cv), 64) * 64 + NAT_PREP_BYTES // 4
+    return cdiv(fc, 64) * 64 + NAT_PREP_BYTES // 4
 
 
 def nature_workspace_bytes(A, B):
-    """nature.hip:2123-2130 a3c_nature_workspace_bytes."""
+    """nature.hip:1374-1381 a3c_nature_workspace_bytes."""
     return max(nat_fwd_ws_floats(B), nat_plan(A, B).total) * 4 + 256
 
 

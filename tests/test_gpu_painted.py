@@ -35,7 +35,6 @@ threads; overlap: LaunchMode::shared_gpu, 512):
   k_play_observe_refill (screen_frame<512>)   Engine.play(refill=True)                  play-refill
   k_env_init_screens (a3c_preprocess_part)    a3c_engine_ext_begin                      host-env
   a3c_env_screen (k_env_screen)               BatchedEnvironment.screens                batched-env
-  k_head_screen_fold<., 512>                  only with the A/B knob A3C_NAT_FOLD_HEAD of a -DA3C_KNOBS build -- skipped
   k_screen_atari, k_preprocess                the standalone entry points               tests/test_gpu_kernels.py
 
 (The Catch forms of k_head_screen / k_head_screen_play and the device reset's k_env_init_screens see their
