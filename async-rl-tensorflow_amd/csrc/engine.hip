@@ -1330,6 +1330,23 @@ extern "C" int a3c_engine_set_precision(a3c_engine* e, int precision) {
   return 0;
 }
 
+// fc_precision: the nature trunk's fc compute mode, beside and independent of precision: read
+// from the layout by the fc forward (rollout steps, bootstrap state, play) and the backward's two fc GEMMs.
+extern "C" int a3c_engine_set_fc_precision(a3c_engine* e, int precision) {
+  if (precision != A3C_PREC_FP32 && precision != A3C_PREC_BF16)
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_set_fc_precision", "precision: A3C_PREC_FP32 or A3C_PREC_BF16");
+  if (!e) return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_set_fc_precision", "null");
+  if (precision == A3C_PREC_BF16 && !e->nat)
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_set_fc_precision",
+                         "the bf16 fc is the nature trunk's (the NIPS fc kernels have no such mode)");
+  if (e->grad_ready && !e->grad_applied)
+    return a3c_set_error(A3C_ERR_STATE, "a3c_engine_set_fc_precision", "a gradient is pending: apply it first");
+  A3C_CHECK(hipDeviceSynchronize());
+  e->L.fc_prec = precision;
+  drop_graphs(e);   // (they hold the other mode's kernels)
+  return 0;
+}
+
 extern "C" int a3c_engine_reset(a3c_engine* e, const float* host_params, void* stream) {
   if (!e) return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_reset", "null");
   hipStream_t s = (hipStream_t)stream;
@@ -2297,15 +2314,19 @@ extern "C" int a3c_engine_time_kernel(a3c_engine* e, int kernel, int iters, void
     if (pass == NAT_C3F || pass == NAT_C1F)
       return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_time_kernel",
                            "this pass runs inside another pass's launch (k_nat_conv23 under A3C_KER_NAT_C2F, k_nat_dx32 under A3C_KER_NAT_C3X)");
+    if (pass < 0 || pass > NAT_FCX)
+      return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_time_kernel", "unknown kernel id");
     if (!fwd && !e->grad_ready)
       return a3c_set_error(A3C_ERR_STATE, "a3c_engine_time_kernel", "backward passes: run an iteration first");
+    if (pass == NAT_FCW && !e->grad_applied)   // (it writes the fc weights' gradient again)
+      return a3c_set_error(A3C_ERR_STATE, "a3c_engine_time_kernel", "fc dW: a gradient is pending, apply it first");
     const Slot& bs = e->slot[e->nslot == 2 ? (int)((e->iter - 2) & 1) : 0];   // the last back-propagated rollout
     const StateAddr sa = fwd ? ring_addr(e, 0, e->counters) : ring_addr(e, 0, bs.tau);
     auto go = [&]() -> int {
       return fwd ? a3c_nat_pass_launch(pass, L, e->params, sa, E, sl.act_l1, sl.act_l2, sl.act_l3, sl.act_l4,
                                        (const uint16_t*)sl.prep, e->nat_fws, nullptr, s)
                  : a3c_nat_pass_launch(pass, L, bs.P, sa, e->nE, bs.act_l1, bs.act_l2, bs.act_l3, bs.act_l4,
-                                       (const uint16_t*)bs.prep, nullptr, e->ws, s);
+                                       (const uint16_t*)bs.prep, nullptr, e->ws, s, e->grads);
     };
     return time_launches(go, iters, s, avg_ms);
   }

@@ -55,10 +55,20 @@ int a3c_nat_fused_tab(const NetLayout& L, TensorTab* tt);
 // reads it: null there is A3C_ERR_INVALID; the backward passes do not).
 // The three conv forwards run as one launch under NAT_C2F (k_nat_conv23, bf16 mode:
 // k_nat_conv123_b1); NAT_C1F and NAT_C3F launch nothing.
-enum { NAT_C1F = 0, NAT_C2F, NAT_C3F, NAT_FCF, NAT_C3W, NAT_C3X, NAT_C2W, NAT_C2X, NAT_C1W };
+// NAT_FCW / NAT_FCX: the fc's weight gradient (into grads + its offset, its dl4 column sums into the
+// plan's fccol) and input gradient dl3, the backward's first two GEMMs, from the plan's dl4 in bws.
+// L.fc_prec selects the fc passes' kernels: gemm.hip's fp32 GEMMs or nature_fc.hip's.
+enum { NAT_C1F = 0, NAT_C2F, NAT_C3F, NAT_FCF, NAT_C3W, NAT_C3X, NAT_C2W, NAT_C2X, NAT_C1W, NAT_FCW, NAT_FCX };
 int a3c_nat_pass_launch(int pass, const NetLayout& L, const float* P, const StateAddr& sa, int64_t B, const float* l1,
                         const float* l2, const float* l3, const float* l4, const uint16_t* w1t, float* fws,
-                        float* bws, hipStream_t s);
+                        float* bws, hipStream_t s, float* grads = nullptr);
+// the fc on single bf16 operands (nature_fc.hip): l4 = relu(rn(l3) rn(W) + bias), its K split into at
+// most max_split chunks of slab ([chunk][B][512]); dW = rn(l3)^T rn(dl4) with colsum = the column sums
+// of the unrounded dl4; dl3 = (rn(dl4) rn(W)^T) * (l3 > 0)
+int a3c_nat_fc_fwd_launch(const float* l3, const float* W, const float* bias, float* l4, int64_t B, float* slab,
+                          int max_split, hipStream_t s);
+int a3c_nat_fc_dw_launch(const float* l3, const float* dl4, int64_t B, float* dW, float* colsum, hipStream_t s);
+int a3c_nat_fc_dx_launch(const float* dl4, const float* W, const float* l3, int64_t B, float* dl3, hipStream_t s);
 // the rollout start on the nature trunk: the bf16 weight terms of P into w1t (the prepared block,
 // A3C_NAT_PREP_BYTES: conv1's [3][32][256] in (cin, kh, kw) order, then conv2's [3][64][512] and
 // conv3's [3][64][576], each [term][cout][k] in TF k order), tau snapshot (overlap) and the

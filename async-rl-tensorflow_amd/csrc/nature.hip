@@ -24,7 +24,8 @@
 //             order by k_slab_group + k_finalize (net_bwd.hip) -- deterministic, no atomics
 //    NG_DW1   the same for conv1 (patches from the u8 ring; the 1/255 is the finalize's scale)
 //  fc 3136 -> 512 and its backward: gemm.hip (split-K slabs with the bias + ReLU epilogue; the
-//  weight gradient in-workgroup split-K).  Head (k_nat_head): head_row<512> + the action draw and the
+//  weight gradient in-workgroup split-K); with NetLayout::fc_prec A3C_PREC_BF16 nature_fc.hip's
+//  three kernels on single bf16 operands.  Head (k_nat_head): head_row<512> + the action draw and the
 //  fused env act of net_head.h; the rollout step's head + screen kernels: net_fwd.hip; head
 //  backward: k_head_bwd<512> (net_bwd.hip).
 #include "nature.h"
@@ -1100,7 +1101,7 @@ int64_t a3c_nat_bwd_ws_floats(const NetLayout& L, int64_t B) { return nat_plan(L
 // their CUs, r6fu_nature_fusion_ab.txt, r6dxp_nature_dx_fc_ab.txt).  All in DESIGN §4d.
 int a3c_nat_pass_launch(int pass, const NetLayout& L, const float* P, const StateAddr& sa, int64_t B, const float* l1,
                         const float* l2, const float* l3, const float* l4, const uint16_t* w1t, float* fws,
-                        float* bws, hipStream_t s) {
+                        float* bws, hipStream_t s, float* grads) {
   const bool b1 = L.prec == A3C_PREC_BF16;
   if (!w1t && pass >= NAT_C1F && pass <= NAT_C3F)
     return a3c_set_error(A3C_ERR_INVALID, "a3c_nat_pass_launch", "the conv forward needs the prepared block");
@@ -1121,6 +1122,8 @@ int a3c_nat_pass_launch(int pass, const NetLayout& L, const float* P, const Stat
       return 0;
     case NAT_FCF: {
       if (fws == nullptr) return a3c_set_error(A3C_ERR_INVALID, "a3c_nat_pass_launch", "fc: no slab workspace");
+      if (L.fc_prec == A3C_PREC_BF16)   // (its K chunks within the slabs of the fp32 plan)
+        return a3c_nat_fc_fwd_launch(l3, P + L.off[N_FCW], P + L.off[N_FCB], (float*)l4, B, fws, fc_split(B), s);
       // l4 = relu(l3 W + b) (network.py:41-42, ops.py:41-44): split-K slabs, the fold applies the epilogue
       GemmArgs gf = {};
       gf.A = l3; gf.lda = NT_FLAT;
@@ -1137,6 +1140,29 @@ int a3c_nat_pass_launch(int pass, const NetLayout& L, const float* P, const Stat
   const NatPlan p = nat_plan(L, B);
   NatGemm a = {};
   switch (pass) {
+    case NAT_FCW: {   // fc weights: dW[3136][512] = l3^T dl4 straight into grads (split-K inside the workgroups), db = colsum
+      if (!grads) return a3c_set_error(A3C_ERR_INVALID, "a3c_nat_pass_launch", "fc dW: no gradient buffer");
+      if (L.fc_prec == A3C_PREC_BF16)
+        return a3c_nat_fc_dw_launch(l3, bws + p.dl4, B, grads + L.off[N_FCW], bws + p.fccol, s);
+      GemmArgs gf = {};
+      gf.A = l3; gf.lda = NT_FLAT;
+      gf.B = bws + p.dl4; gf.ldb = NT_FC;
+      gf.C = grads + L.off[N_FCW]; gf.ldc = NT_FC;
+      gf.M = NT_FLAT; gf.N = NT_FC; gf.K = (int)B;
+      gf.epi = EPI_STORE; gf.colsum = bws + p.fccol; gf.wg_split = 4; gf.xcd = 1;
+      return a3c_gemm(false, true, gf, s);
+    }
+    case NAT_FCX: {   // dl3 = (dl4 W^T) * (l3 > 0)
+      if (L.fc_prec == A3C_PREC_BF16)
+        return a3c_nat_fc_dx_launch(bws + p.dl4, P + L.off[N_FCW], l3, B, bws + p.dl3, s);
+      GemmArgs gd = {};
+      gd.A = bws + p.dl4; gd.lda = NT_FC;
+      gd.B = P + L.off[N_FCW]; gd.ldb = NT_FC;
+      gd.C = bws + p.dl3; gd.ldc = NT_FLAT;
+      gd.M = (int)B; gd.N = NT_FLAT; gd.K = NT_FC;
+      gd.epi = EPI_MASK; gd.mask = l3; gd.ldm = NT_FLAT; gd.nsplit = 1;
+      return a3c_gemm(true, false, gd, s);
+    }
     case NAT_C3W:     // dW3 (+ db3) over the (sample, pixel) rows
       a.X = l2; a.dY = bws + p.dl3; a.slab = bws + p.s3; a.colsum = bws + p.c3;
       a.M = NT_K3; a.N = NT3_N; a.K = (int)(B * NT3_P); a.kchunk = p.kc3;
@@ -1288,24 +1314,11 @@ int a3c_nat_backward_launch(const NetLayout& L, const BwdArgs& args, hipStream_t
   gh.defer_reduce = 1;
   rc = a3c_gemm(false, true, gh, s);
   if (rc) return rc;
-  // fc weights: dW[3136][512] = l3^T dl4 straight into grads (split-K inside the workgroups), db = colsum
-  GemmArgs gf = {};
-  gf.A = l3; gf.lda = NT_FLAT;
-  gf.B = dl4; gf.ldb = NT_FC;
-  gf.C = grads + L.off[N_FCW]; gf.ldc = NT_FC;
-  gf.M = NT_FLAT; gf.N = NT_FC; gf.K = (int)B;
-  gf.epi = EPI_STORE; gf.colsum = ws + p.fccol; gf.wg_split = 4; gf.xcd = 1;
-  rc = a3c_gemm(false, true, gf, s);
-  if (rc) return rc;
-  // dl3 = (dl4 W^T) * (l3 > 0)
-  GemmArgs gd = {};
-  gd.A = dl4; gd.lda = NT_FC;
-  gd.B = P + L.off[N_FCW]; gd.ldb = NT_FC;
-  gd.C = ws + p.dl3; gd.ldc = NT_FLAT;
-  gd.M = (int)B; gd.N = NT_FLAT; gd.K = NT_FC;
-  gd.epi = EPI_MASK; gd.mask = l3; gd.ldm = NT_FLAT; gd.nsplit = 1;
-  rc = a3c_gemm(true, false, gd, s);
-  if (rc) return rc;
+  // the fc's weight and input gradients (passes of their own), then the conv passes
+  for (int pass = NAT_FCW; pass <= NAT_FCX; ++pass) {
+    rc = a3c_nat_pass_launch(pass, L, P, args.sa, B, args.act_l1, args.act_l2, l3, l4, wt, nullptr, ws, s, grads);
+    if (rc) return rc;
+  }
   for (int pass = NAT_C3W; pass <= NAT_C1W; ++pass) {
     rc = a3c_nat_pass_launch(pass, L, P, args.sa, B, args.act_l1, args.act_l2, l3, l4, wt, nullptr, ws, s);
     if (rc) return rc;
@@ -1386,13 +1399,15 @@ static int nat_prec_ok(int precision, const char* what) {
   return 0;
 }
 
-extern "C" int a3c_nature_forward_prec(const a3c_net_desc* net, const float* params, const uint8_t* states, int64_t B,
-                                       float* l1, float* l2, float* l3, float* l4, float* z, void* workspace,
-                                       void* stream, int precision) {
+extern "C" int a3c_nature_forward_prec2(const a3c_net_desc* net, const float* params, const uint8_t* states, int64_t B,
+                                        float* l1, float* l2, float* l3, float* l4, float* z, void* workspace,
+                                        void* stream, int precision, int fc_precision) {
   NetLayout L;
   if (int rc = nat_prec_ok(precision, "a3c_nature_forward")) return rc;
+  if (int rc = nat_prec_ok(fc_precision, "a3c_nature_forward")) return rc;
   if (int rc = nat_layout(net, &L, "a3c_nature_forward")) return rc;
   L.prec = precision;
+  L.fc_prec = fc_precision;
   if (!params || !states || !l1 || !l2 || !l3 || !l4 || !z || !workspace || B < 0 || B * NT1_P > 0x7fffffffLL ||
       (((uintptr_t)params | (uintptr_t)l1 | (uintptr_t)l2 | (uintptr_t)l3 | (uintptr_t)l4) & 15))
     return a3c_set_error(A3C_ERR_INVALID, "a3c_nature_forward", "bad argument");
@@ -1405,21 +1420,30 @@ extern "C" int a3c_nature_forward_prec(const a3c_net_desc* net, const float* par
   a.act_l1 = l1; a.act_l2 = l2; a.act_l3 = l3; a.act_l4 = l4; a.nat_ws = nat_align(workspace);
   return a3c_nat_forward_launch(L, a, (hipStream_t)stream, LAUNCH_ALONE);
 }
+extern "C" int a3c_nature_forward_prec(const a3c_net_desc* net, const float* params, const uint8_t* states, int64_t B,
+                                       float* l1, float* l2, float* l3, float* l4, float* z, void* workspace,
+                                       void* stream, int precision) {
+  return a3c_nature_forward_prec2(net, params, states, B, l1, l2, l3, l4, z, workspace, stream, precision,
+                                  A3C_PREC_FP32);
+}
 extern "C" int a3c_nature_forward(const a3c_net_desc* net, const float* params, const uint8_t* states, int64_t B,
                                   float* l1, float* l2, float* l3, float* l4, float* z, void* workspace,
                                   void* stream) {
   return a3c_nature_forward_prec(net, params, states, B, l1, l2, l3, l4, z, workspace, stream, A3C_PREC_FP32);
 }
 
-extern "C" int a3c_nature_loss_backward_prec(const a3c_net_desc* net, const float* params, const uint8_t* states,
-                                             int64_t B, const float* l1, const float* l2, const float* l3,
-                                             const float* l4, const float* z, const int32_t* actions,
-                                             const float* target, float beta, int literal_adv, float* grads,
-                                             float* loss_out, void* workspace, void* stream, int precision) {
+extern "C" int a3c_nature_loss_backward_prec2(const a3c_net_desc* net, const float* params, const uint8_t* states,
+                                              int64_t B, const float* l1, const float* l2, const float* l3,
+                                              const float* l4, const float* z, const int32_t* actions,
+                                              const float* target, float beta, int literal_adv, float* grads,
+                                              float* loss_out, void* workspace, void* stream, int precision,
+                                              int fc_precision) {
   NetLayout L;
   if (int rc = nat_prec_ok(precision, "a3c_nature_loss_backward")) return rc;
+  if (int rc = nat_prec_ok(fc_precision, "a3c_nature_loss_backward")) return rc;
   if (int rc = nat_layout(net, &L, "a3c_nature_loss_backward")) return rc;
   L.prec = precision;
+  L.fc_prec = fc_precision;
   if (!params || !states || !l1 || !l2 || !l3 || !l4 || !z || !actions || !target || !grads || !workspace ||
       B <= 0 || B * NT1_P > 0x7fffffffLL || (((uintptr_t)grads | (uintptr_t)l3 | (uintptr_t)l4) & 15))
     return a3c_set_error(A3C_ERR_INVALID, "a3c_nature_loss_backward", "bad argument");
@@ -1428,6 +1452,14 @@ extern "C" int a3c_nature_loss_backward_prec(const a3c_net_desc* net, const floa
   a.act_l1 = l1; a.act_l2 = l2; a.act_l3 = l3; a.act_l4 = l4; a.z = z; a.actions = actions; a.target = target;
   a.beta = beta; a.literal = literal_adv; a.grads = grads; a.loss_out = loss_out; a.ws = nat_align(workspace);
   return a3c_nat_backward_launch(L, a, (hipStream_t)stream);
+}
+extern "C" int a3c_nature_loss_backward_prec(const a3c_net_desc* net, const float* params, const uint8_t* states,
+                                             int64_t B, const float* l1, const float* l2, const float* l3,
+                                             const float* l4, const float* z, const int32_t* actions,
+                                             const float* target, float beta, int literal_adv, float* grads,
+                                             float* loss_out, void* workspace, void* stream, int precision) {
+  return a3c_nature_loss_backward_prec2(net, params, states, B, l1, l2, l3, l4, z, actions, target, beta, literal_adv,
+                                        grads, loss_out, workspace, stream, precision, A3C_PREC_FP32);
 }
 extern "C" int a3c_nature_loss_backward(const a3c_net_desc* net, const float* params, const uint8_t* states,
                                         int64_t B, const float* l1, const float* l2, const float* l3, const float* l4,

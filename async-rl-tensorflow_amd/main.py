@@ -15,6 +15,8 @@ accepted but the TF ps/worker cluster is replaced by one process per GPU under t
                  --sarsa true Sarsa(lambda), with --double_q true its double-Q form
   python main.py --mode engine --dqn_type nature --precision bf16   the nature trunk's convolutions on single bf16 operands,
                  fp32 accumulation, parameters and activations
+  python main.py --mode engine --dqn_type nature --precision bf16 --fc_precision bf16   ... and the fc's three GEMMs too
+                 
   python main.py --mode engine --algo q --optimizer adam --env_name Catch-v0             shared Adam instead of RMSProp
   python main.py --mode engine --lstm true --env_name CatchMemory-v0   Catch that only a head with memory learns
   python main.py --mode engine --lstm true --env_name CatchMemory-v0 --first_screen true   ... with each episode's first
@@ -125,6 +127,10 @@ def parse_flags(argv=None):
                  help="engine mode, --dqn_type nature: fp32 (every convolution operand as three bf16 terms, fp32-class "
                       "results) or bf16 (mixed precision: one bf16 term per operand, fp32 accumulation, parameters and "
                       "saved activations; DESIGN §4n)")
+  p.add_argument('--fc_precision', default='fp32',
+                 help="engine mode, --dqn_type nature: fp32 (the fc 3136 -> 512 and its backward as exact-fp32 GEMMs) or "
+                      "bf16 (both operands of the three fc GEMMs rounded to bf16, fp32 accumulation; independent of "
+                      "--precision; DESIGN §4p)")
   # evaluation: --mode engine --is_train false (Agent.play, agent.py:351-391)
   p.add_argument('--n_episode', type=int, default=100, help='play: episodes (agent.py:351)')
   p.add_argument('--play_steps', type=int, default=10000, help="play: cap on an episode's env steps (agent.py:351 n_step)")
@@ -181,6 +187,12 @@ def engine_options(flags):
   if precision == 'bf16' and flags.dqn_type != 'nature':
     raise ValueError('--precision bf16 is the compute mode of the nature trunk (DESIGN §4n; the nips rollout kernel '
                      'has none): use it with --dqn_type nature')
+  fc_precision = getattr(flags, 'fc_precision', 'fp32')
+  if fc_precision not in ('fp32', 'bf16'):
+    raise ValueError("--fc_precision must be fp32 or bf16 (got %r)" % (fc_precision,))
+  if fc_precision == 'bf16' and flags.dqn_type != 'nature':
+    raise ValueError('--fc_precision bf16 is the fc compute mode of the nature trunk (DESIGN §4p; the nips fc kernels '
+                     'have none): use it with --dqn_type nature')
   first_screen = bool(getattr(flags, 'first_screen', False))
   if first_screen and game_kind(flags.env_name) != 'catch':
     raise ValueError('--first_screen is an option of the device game Catch (--env_name Catch-v0 or CatchMemory-v0, '
@@ -208,6 +220,8 @@ def engine_options(flags):
     kw['first_screen'] = True
   if precision != 'fp32':
     kw['precision'] = precision
+  if fc_precision != 'fp32':
+    kw['fc_precision'] = fc_precision
   return kw
 
 
@@ -496,6 +510,9 @@ def main(argv=None):
     raise ValueError('--q_lambda is an engine option: --mode agent is the per-step Q-learning loop (one-step targets)')
   if flags.mode == 'agent' and flags.precision != 'fp32':
     raise ValueError('--precision is an engine option (the nature trunk of --mode engine, DESIGN §4n): --mode agent '
+                     'is the per-op loop in fp32')
+  if flags.mode == 'agent' and flags.fc_precision != 'fp32':
+    raise ValueError('--fc_precision is an engine option (the nature trunk of --mode engine, DESIGN §4p): --mode agent '
                      'is the per-op loop in fp32')
   if flags.mode == 'agent' and flags.first_screen:
     raise ValueError('--first_screen is an engine option: --mode agent is the reference loop (agent.py:59-67) as it stands')

@@ -137,6 +137,11 @@ SIGNATURES = {
     'a3c_nature_loss_backward_prec': (c_int, [ctypes.POINTER(NetDesc), c_void_p, c_void_p, c_i64, c_void_p, c_void_p,
                                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int,
                                               c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
+    'a3c_nature_forward_prec2': (c_int, [ctypes.POINTER(NetDesc), c_void_p, c_void_p, c_i64, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int]),
+    'a3c_nature_loss_backward_prec2': (c_int, [ctypes.POINTER(NetDesc), c_void_p, c_void_p, c_i64, c_void_p, c_void_p,
+                                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int,
+                                               c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int]),
     'a3c_optim_workspace_bytes': (c_int, [c_i64, ctypes.POINTER(c_i64)]),
     'a3c_clip_grads': (c_int, [c_void_p, c_int, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), c_float,
                                c_void_p, c_void_p, c_void_p]),
@@ -182,6 +187,7 @@ SIGNATURES = {
     'a3c_engine_set_first_screen': (c_int, [c_void_p, c_int]),
     'a3c_engine_set_q_lambda': (c_int, [c_void_p, c_int, c_double]),
     'a3c_engine_set_precision': (c_int, [c_void_p, c_int]),
+    'a3c_engine_set_fc_precision': (c_int, [c_void_p, c_int]),
     'a3c_engine_reset': (c_int, [c_void_p, c_void_p, c_void_p]),
     'a3c_engine_rollout_grad': (c_int, [c_void_p, c_void_p]),
     'a3c_engine_apply': (c_int, [c_void_p, c_void_p]),
@@ -251,7 +257,8 @@ OPTIONAL_IN_OLD_BUILDS = MEASUREMENT_ONLY + ('a3c_engine_exchange_split', 'a3c_e
                                              'a3c_env_set_catch_rules', 'a3c_engine_set_first_screen',
                                              'a3c_lambda_q_target', 'a3c_engine_set_q_lambda',
                                              'a3c_nature_forward_prec', 'a3c_nature_loss_backward_prec',
-                                             'a3c_engine_set_precision',
+                                             'a3c_engine_set_precision', 'a3c_nature_forward_prec2',
+                                             'a3c_nature_loss_backward_prec2', 'a3c_engine_set_fc_precision',
                                              'a3c_gemm_workspace_bytes', 'a3c_gemm_f32', 'a3c_gemm3_f32')
 
 # the nature trunk's conv compute modes (include/a3c_hip.h A3C_PREC_*)
@@ -259,10 +266,10 @@ PREC_FP32, PREC_BF16 = 0, 1
 PRECISIONS = {'fp32': PREC_FP32, 'bf16': PREC_BF16}
 
 
-def precision_code(precision):
+def precision_code(precision, option='precision'):
     """'fp32' | 'bf16' -> A3C_PREC_*; anything else: ValueError naming the option."""
     if precision not in PRECISIONS:
-        raise ValueError("precision must be 'fp32' or 'bf16' (got %r)" % (precision,))
+        raise ValueError("%s must be 'fp32' or 'bf16' (got %r)" % (option, precision))
     return PRECISIONS[precision]
 
 
@@ -270,6 +277,8 @@ KER_CONV12_FWD, KER_FC_FWD, KER_ENV_STEP, KER_CONV_BWD, KER_HEAD_SCREEN, KER_HEA
 # nature trunk passes (include/a3c_hip.h A3C_KER_NAT_*)
 KER_NAT = {'conv1_fwd': 7, 'conv2_fwd': 8, 'conv3_fwd': 9, 'fc_fwd': 10, 'conv3_dw': 11, 'conv3_dx': 12, 'conv2_dw': 13,
            'conv2_dx': 14, 'conv1_dw': 15}
+# the fc's two backward GEMMs, passes of their own (A3C_KER_NAT_FCW / _FCX)
+KER_NAT_FC_BWD = {'fc_dw': 16, 'fc_dx': 17}
 
 _lib = None
 

@@ -57,7 +57,7 @@ class Engine:
     def __init__(self, num_envs=256, n_step=5, action_size=6, algo='a3c', start_lives=0, num_frames=None,
                  seed=123, env_id_base=0, world_size=1, use_graph=False, overlap=False, lstm=False,
                  external_env=False, dqn_type='nips', game='synth', catch_rules=None, first_screen=None, q_lambda=None,
-                 precision='fp32', **overrides):
+                 precision='fp32', fc_precision='fp32', **overrides):
         """game: 'synth' (the synthetic Atari stand-in) or 'catch' (Catch-v0, DESIGN §4g: action_size 3,
         start_lives 0, device envs, raw RGB pool; random_start is ignored).  num_frames=None: 1024
         frames (Catch needs its 640: a smaller explicit value is rejected by the library).
@@ -83,8 +83,13 @@ class Engine:
         precision='fp32' | 'bf16' ('fp32': no call is made): a3c_engine_set_precision right after
         the create -- 'bf16' (dqn_type 'nature' only) runs every convolution pass on one bf16 term per operand
         with fp32 accumulation; parameters, optimizer slots and saved activations stay fp32; kept as
-        ``precision``.  Not in the saved state: a resumed run gives it again."""
+        ``precision``.  Not in the saved state: a resumed run gives it again.
+        fc_precision='fp32' | 'bf16' ('fp32': no call is made): a3c_engine_set_fc_precision right
+        after the create -- 'bf16' (dqn_type 'nature' only) runs the fc forward and its two backward GEMMs on one
+        bf16 term per operand with fp32 accumulation, independently of ``precision``; kept as ``fc_precision``.
+        Not in the saved state either."""
         self.precision = self._check_precision(precision, str(dqn_type).lower())
+        self.fc_precision = self._check_fc_precision(fc_precision, str(dqn_type).lower())
         self.q_lambda = self._check_q_lambda(q_lambda, algo, overrides.get('q_nstep', 0))
         if first_screen is not None and game != 'catch':
             raise ValueError('first_screen is an option of game catch, not of %r' % (game,))
@@ -165,6 +170,9 @@ class Engine:
             check(lib().a3c_engine_set_q_lambda(h, 1, self.q_lambda), 'a3c_engine_set_q_lambda')
         if self.precision != 'fp32':
             check(lib().a3c_engine_set_precision(h, _lib.PRECISIONS[self.precision]), 'a3c_engine_set_precision')
+        if self.fc_precision != 'fp32':
+            check(lib().a3c_engine_set_fc_precision(h, _lib.PRECISIONS[self.fc_precision]),
+                  'a3c_engine_set_fc_precision')
         b = _lib.EngineBuffers()
         check(lib().a3c_engine_get_buffers(h, ctypes.byref(b)), 'a3c_engine_get_buffers')
         self._b = b
@@ -235,6 +243,19 @@ class Engine:
         value = self._check_precision(value, self.dqn_type)
         check(lib().a3c_engine_set_precision(self._h, _lib.PRECISIONS[value]), 'a3c_engine_set_precision')
         self.precision = value
+
+    @staticmethod
+    def _check_fc_precision(value, dqn_type):
+        _lib.precision_code(value, 'fc_precision')
+        if value == 'bf16' and dqn_type != 'nature':
+            raise ValueError("fc_precision 'bf16' is the nature trunk's fc mode (dqn_type %r has none)" % (dqn_type,))
+        return value
+
+    def set_fc_precision(self, value):
+        """a3c_engine_set_fc_precision between iterations: no reset, the next rollout and gradient follow it."""
+        value = self._check_fc_precision(value, self.dqn_type)
+        check(lib().a3c_engine_set_fc_precision(self._h, _lib.PRECISIONS[value]), 'a3c_engine_set_fc_precision')
+        self.fc_precision = value
 
     def _slot_views(self, k):
         b = _lib.EngineBuffers()

@@ -172,10 +172,11 @@ class NatureNet:
               'a3c_nature_workspace_bytes')
         return torch.empty(int(n.value), dtype=torch.uint8, device=device)
 
-    def forward(self, params, states, workspace=None, z=None, precision=None):
+    def forward(self, params, states, workspace=None, z=None, precision=None, fc_precision=None):
         """states [B,4,84,84] u8 (oldest frame first).  Returns dict z/l1/l2/l3/l4.
         z: caller-owned head rows [>= B, zs] to write into (rows past B are left alone).
-        precision: None (a3c_nature_forward) or 'fp32' | 'bf16' (a3c_nature_forward_prec)."""
+        precision: None (a3c_nature_forward) or 'fp32' | 'bf16' (a3c_nature_forward_prec).
+        fc_precision: None, or 'fp32' | 'bf16' (a3c_nature_forward_prec2; precision None is 'fp32')."""
         _dev(params, torch.float32, 'params')
         _dev(states, torch.uint8, 'states')
         B = int(states.shape[0])
@@ -187,6 +188,13 @@ class NatureNet:
                    l4=torch.empty((B, 512), dtype=torch.float32, device=dev),
                    z=_z_rows(z, B, self.zs, dev))
         ws = workspace if workspace is not None else self.workspace(B, dev)
+        if fc_precision is not None:
+            check(lib().a3c_nature_forward_prec2(ctypes.byref(self.desc), ptr(params), ptr(states), B, ptr(out['l1']),
+                                                 ptr(out['l2']), ptr(out['l3']), ptr(out['l4']), ptr(out['z']), ptr(ws),
+                                                 stream_handle(), prec or 0,
+                                                 _lib.precision_code(fc_precision, 'fc_precision')),
+                  'a3c_nature_forward_prec2')
+            return out
         if prec is not None:
             check(lib().a3c_nature_forward_prec(ctypes.byref(self.desc), ptr(params), ptr(states), B, ptr(out['l1']),
                                                 ptr(out['l2']), ptr(out['l3']), ptr(out['l4']), ptr(out['z']), ptr(ws),
@@ -198,8 +206,9 @@ class NatureNet:
         return out
 
     def loss_backward(self, params, states, fwd, actions, target, beta=0.01, literal_adv=False, grads=None,
-                      workspace=None, precision=None):
-        """precision: None (a3c_nature_loss_backward) or 'fp32' | 'bf16' (a3c_nature_loss_backward_prec)."""
+                      workspace=None, precision=None, fc_precision=None):
+        """precision: None (a3c_nature_loss_backward) or 'fp32' | 'bf16' (a3c_nature_loss_backward_prec).
+        fc_precision: None, or 'fp32' | 'bf16' (a3c_nature_loss_backward_prec2; precision None is 'fp32')."""
         prec = None if precision is None else _lib.precision_code(precision)
         _dev(actions, torch.int32, 'actions')
         _dev(target, torch.float32, 'target')
@@ -209,6 +218,15 @@ class NatureNet:
             grads = torch.zeros(self.total, dtype=torch.float32, device=dev)
         loss = torch.zeros(4, dtype=torch.float32, device=dev)
         ws = workspace if workspace is not None else self.workspace(B, dev)
+        if fc_precision is not None:
+            check(lib().a3c_nature_loss_backward_prec2(ctypes.byref(self.desc), ptr(params), ptr(states), B,
+                                                       ptr(fwd['l1']), ptr(fwd['l2']), ptr(fwd['l3']), ptr(fwd['l4']),
+                                                       ptr(fwd['z']), ptr(actions), ptr(target), float(beta),
+                                                       1 if literal_adv else 0, ptr(grads), ptr(loss), ptr(ws),
+                                                       stream_handle(), prec or 0,
+                                                       _lib.precision_code(fc_precision, 'fc_precision')),
+                  'a3c_nature_loss_backward_prec2')
+            return grads, loss
         if prec is not None:
             check(lib().a3c_nature_loss_backward_prec(ctypes.byref(self.desc), ptr(params), ptr(states), B,
                                                       ptr(fwd['l1']), ptr(fwd['l2']), ptr(fwd['l3']), ptr(fwd['l4']),

@@ -122,6 +122,26 @@ int a3c_nature_loss_backward_prec(const a3c_net_desc* net, const float* params, 
                                   const float* z, const int32_t* actions, const float* target, float beta,
                                   int literal_adv, float* grads, float* loss_out, void* workspace, void* stream,
                                   int precision);
+/* The nature trunk's fc compute mode, a second switch, independent of the convolutions'
+ * (all four combinations run).  fc_precision A3C_PREC_FP32: the exact-fp32 GEMMs (the default, and what
+ * every entry above runs).  A3C_PREC_BF16: the three fc GEMMs round both operands to nearest-even bf16
+ * where they are staged and accumulate in fp32 --
+ *   forward   l4 = relu(rn(l3) . rn(W4) + b4)
+ *   backward  dW4 = rn(l3)^T . rn(dl4), db4 = the column sums of the unrounded dl4,
+ *             dl3 = (rn(dl4) . rn(W4)^T) * (l3 > 0)
+ * Parameters, saved activations, bias, ReLU and masks stay fp32; the heads, the loss and the optimizer
+ * are unchanged; the workspace is the same size.  Reductions run in one fixed order (no atomics).
+ * The two entries are the _prec entries with a trailing fc_precision; with A3C_PREC_FP32 there they
+ * launch exactly what the _prec entries launch.  A3C_ERR_INVALID, in this order: a precision that is
+ * neither constant, an fc_precision that is neither, then the _prec entry's own checks. */
+int a3c_nature_forward_prec2(const a3c_net_desc* net, const float* params, const uint8_t* states, int64_t B,
+                             float* l1, float* l2, float* l3, float* l4, float* z, void* workspace, void* stream,
+                             int precision, int fc_precision);
+int a3c_nature_loss_backward_prec2(const a3c_net_desc* net, const float* params, const uint8_t* states, int64_t B,
+                                   const float* l1, const float* l2, const float* l3, const float* l4,
+                                   const float* z, const int32_t* actions, const float* target, float beta,
+                                   int literal_adv, float* grads, float* loss_out, void* workspace, void* stream,
+                                   int precision, int fc_precision);
 
 /* ----------------------------------------------------------------------------
  * K1  Environment.screen (environment.py:49-53): fp64 luminance truncated to u8, then
@@ -679,6 +699,16 @@ int a3c_engine_set_q_lambda(a3c_engine* eng, int on, double lambda);
  * (a resumed run gives it again); a3c_engine_play follows it (it runs the same forward launch).
  * python async-rl-tensorflow_amd/main.py --mode engine --dqn_type nature --precision bf16 */
 int a3c_engine_set_precision(a3c_engine* eng, int precision);
+/* fc_precision: the fc compute mode of a nature-trunk engine, A3C_PREC_FP32 (the default:
+ * every launch is what it is without this call) or A3C_PREC_BF16 (the definition stands at
+ * a3c_nature_forward_prec2), independent of a3c_engine_set_precision.  In BF16 the fc forward of the
+ * rollout steps, the bootstrap state and play, and the gradient's fc weight and input GEMMs, run on
+ * single bf16 operands.  A setter with the rules of a3c_engine_set_precision: no reset, the next
+ * rollout and gradient follow it, captured graphs are dropped.  A3C_ERR_INVALID, in this order: a
+ * precision that is neither constant, eng NULL, A3C_PREC_BF16 on a NIPS-trunk engine.  A3C_ERR_STATE: a
+ * computed gradient not yet applied.  Not in the checkpoint's state (a resumed run gives it again).
+ * python async-rl-tensorflow_amd/main.py --mode engine --dqn_type nature --precision bf16 --fc_precision bf16 */
+int a3c_engine_set_fc_precision(a3c_engine* eng, int precision);
 /* fill the frame pool, reset the envs (new_random_game, environment.py:35-40), fill each
  * history with 4 copies of the first screen (agent.py:37-38) and initialise params
  * from host memory (nullable -> keep), rms slot = 1, mom = 0 (Adam: m = v = 0, products = 1). */
@@ -967,12 +997,16 @@ int a3c_engine_play_buffers(a3c_engine* eng, a3c_play_buffers* out);
 #define A3C_KER_NAT_C1F 7      /* conv1 8x8/4 4->32 forward: inside A3C_KER_NAT_C2F        */
 #define A3C_KER_NAT_C2F 8      /* conv1+conv2+conv3 forward (u8 ring -> l1, l2, l3), B = E  */
 #define A3C_KER_NAT_C3F 9      /* conv3 3x3/1 64->64 forward: inside A3C_KER_NAT_C2F       */
-#define A3C_KER_NAT_FCF 10     /* fc 3136->512 forward (split-K GEMM + bias/ReLU fold)      */
+#define A3C_KER_NAT_FCF 10     /* fc 3136->512 forward (split-K GEMM + bias/ReLU fold), in the engine's fc mode */
 #define A3C_KER_NAT_C3W 11     /* conv3 weight gradient (slabs), B = n*E                  */
 #define A3C_KER_NAT_C3X 12     /* conv3 input gradient dl2                                 */
 #define A3C_KER_NAT_C2W 13     /* conv2 weight gradient                                    */
 #define A3C_KER_NAT_C2X 14     /* conv2 input gradient dl1 (4 stride-parity classes)       */
 #define A3C_KER_NAT_C1W 15     /* conv1 weight gradient from the u8 planes                 */
+/* The fc's two backward GEMMs, the first launches after the head's, in the engine's fc mode.  _FCW
+ * writes the fc weights' gradient again: A3C_ERR_STATE while a computed gradient is not yet applied. */
+#define A3C_KER_NAT_FCW 16     /* fc weight gradient l3^T dl4 into grads (+ the dl4 column sums) */
+#define A3C_KER_NAT_FCX 17     /* fc input gradient dl3 = (dl4 W4^T) * (l3 > 0)             */
 /* Live launch spans, recorded by the kernels themselves inside the engine's graphs (which 0:
  * k_conv_bwd, 1: k_head_screen_conv12): per launch, last workgroup end - first workgroup start
  * (s_memrealtime).  reset = 1 clears the records (before a timed region); otherwise returns the

@@ -7,6 +7,8 @@ passed.  Then the kernel-alone times (a3c_engine_time_kernel, HIP events) of the
 backward passes in both modes.  One JSON line per window and per kernel table:
 
   python tools/nat_precision_throughput.py                 every figure of §4n
+  python tools/nat_precision_throughput.py --compare fc    §4p: precision bf16 throughout, fc_precision fp32 against bf16
+                                                           (Engine.set_fc_precision), and the three fc passes alone
   python tools/nat_precision_throughput.py --overlap 1 --rounds 2"""
 import argparse
 import json
@@ -23,6 +25,7 @@ ap.add_argument('--rounds', type=int, default=3, help='A B pairs per pipeline')
 ap.add_argument('--warmup', type=int, default=30, help='iterations after every switch')
 ap.add_argument('--seconds', type=float, default=2.0)
 ap.add_argument('--kernel_iters', type=int, default=50)
+ap.add_argument('--compare', choices=['conv', 'fc'], default='conv', help='the switch that alternates')
 args = ap.parse_args()
 
 sys.path.insert(0, os.path.join(ROOT, 'async-rl-tensorflow_amd'))
@@ -36,6 +39,9 @@ from src.kernels import param_names_shapes  # noqa: E402
 A = 6
 BLOCK = max(1, 200 // args.n_step)             # iterations per 200 steps
 PASSES = ('conv2_fwd', 'conv3_dw', 'conv3_dx', 'conv2_dw', 'conv2_dx', 'conv1_dw')   # conv2_fwd: the fused forward launch
+KERNELS = {k: _lib.KER_NAT[k] for k in PASSES}
+if args.compare == 'fc':
+    KERNELS = dict(fc_fwd=_lib.KER_NAT['fc_fwd'], **_lib.KER_NAT_FC_BWD)
 
 
 def window(eng):
@@ -55,21 +61,26 @@ for overlap in ((1, 0) if args.overlap is None else (args.overlap,)):
                  seed=1, overlap=bool(overlap), dqn_type='nature')
     ns = param_names_shapes(A, 'a3c', dqn_type='nature')
     eng.reset(flatten_host(ns, eng.offsets, eng.params.numel(), init_params(ns, seed=1)))
+    switch, key = eng.set_precision, 'precision'
+    if args.compare == 'fc':
+        eng.set_precision('bf16')
+        switch, key = eng.set_fc_precision, 'fc_precision'
     for _ in range(args.rounds):
         for mode in ('fp32', 'bf16'):
-            eng.set_precision(mode)
+            switch(mode)
             for _ in range(args.warmup):
                 eng.iterate()
             torch.cuda.synchronize()
             rate, ms = window(eng)
-            print(json.dumps(dict(precision=mode, overlap=overlap, envs=args.envs, n_step=args.n_step,
-                                  env_steps_per_s=round(rate), ms_per_iteration=round(ms, 4))), flush=True)
+            print(json.dumps(dict({'precision': eng.precision, key: mode}, overlap=overlap, envs=args.envs,
+                                  n_step=args.n_step, env_steps_per_s=round(rate), ms_per_iteration=round(ms, 4))),
+                  flush=True)
     assert torch.isfinite(eng.params).all()
     if not overlap or args.overlap is not None:    # kernels alone, on the last engine (an iteration has run in each mode)
         for mode in ('fp32', 'bf16'):
-            eng.set_precision(mode)
+            switch(mode)
             eng.iterate()
             torch.cuda.synchronize()
-            us = {k: round(1e3 * eng.time_kernel(_lib.KER_NAT[k], args.kernel_iters), 2) for k in PASSES}
-            print(json.dumps(dict(precision=mode, kernel_alone_us=us)), flush=True)
+            us = {k: round(1e3 * eng.time_kernel(v, args.kernel_iters), 2) for k, v in KERNELS.items()}
+            print(json.dumps({'precision': eng.precision, key: mode, 'kernel_alone_us': us}), flush=True)
     eng.close()
