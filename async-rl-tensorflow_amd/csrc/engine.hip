@@ -721,8 +721,9 @@ static int enqueue_rollout_begin(a3c_engine* e, const Slot& sl, hipStream_t s) {
   int rc = a3c_prep_fwd_launch(e->L, sl.P, sl.prep, s, e->overlap ? e->counters : nullptr,
                            e->overlap ? sl.tau : nullptr, kernel_go(e) ? e->xflags + 1 : nullptr);
   if (rc) return rc;
-  if (e->L.lstm) {
-    rc = a3c_lstm_transpose_launch(sl.P + e->L.off[T_LW], sl.lwt, s);
+  if (e->L.lstm) {   // (bf16 mode: the two rounded copies in the same 2 MB)
+    rc = e->L.lstm_prec == A3C_PREC_BF16 ? a3c_lstm_prep_bf_launch(sl.P + e->L.off[T_LW], (uint16_t*)sl.lwt, s)
+                                         : a3c_lstm_transpose_launch(sl.P + e->L.off[T_LW], sl.lwt, s);
     if (rc) return rc;
   }
   return 0;
@@ -1098,6 +1099,7 @@ static int enqueue_grad(a3c_engine* e, const Slot& sl, hipStream_t s) {
     lb.n = n; lb.E = E;
     lb.h = sl.lh; lb.c = sl.lc; lb.hp = sl.lhp; lb.cp = sl.lcp; lb.gates = sl.lg;
     lb.dh = e->ldh; lb.ws = e->lws;
+    lb.wprep = L.lstm_prec == A3C_PREC_BF16 ? (const uint16_t*)sl.lwt : nullptr;   // (of sl.P, since the rollout start)
   }
   // the per-tensor squared norms (+ lr / target-sync schedule from the device step counter) come
   // out of the backward's last kernel (k_finalize): no separate k_sumsq launch (round 3)
@@ -1343,6 +1345,32 @@ extern "C" int a3c_engine_set_fc_precision(a3c_engine* e, int precision) {
     return a3c_set_error(A3C_ERR_STATE, "a3c_engine_set_fc_precision", "a gradient is pending: apply it first");
   A3C_CHECK(hipDeviceSynchronize());
   e->L.fc_prec = precision;
+  drop_graphs(e);   // (they hold the other mode's kernels)
+  return 0;
+}
+
+// lstm_precision: the LSTM head's compute mode, beside and independent of the other two: read from
+// the layout by the weight prep at the rollout start, the cell step (rollout steps, bootstrap state, play) and the
+// backward's BPTT and gate-matrix gradient.
+extern "C" int a3c_engine_set_lstm_precision(a3c_engine* e, int precision) {
+  if (precision != A3C_PREC_FP32 && precision != A3C_PREC_BF16)
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_set_lstm_precision", "precision: A3C_PREC_FP32 or A3C_PREC_BF16");
+  if (!e) return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_set_lstm_precision", "null");
+  if (!e->L.lstm)
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_set_lstm_precision",
+                         "lstm_precision is the LSTM head's compute mode (this engine has a feed-forward head)");
+  if (e->grad_ready && !e->grad_applied)
+    return a3c_set_error(A3C_ERR_STATE, "a3c_engine_set_lstm_precision", "a gradient is pending: apply it first");
+  A3C_CHECK(hipDeviceSynchronize());      // (the engine's streams: nothing in flight reads the prepared gate matrix)
+  e->L.lstm_prec = precision;
+  // overlap: the next backward is of a rollout already taken, whose prepared gate matrix is the other mode's
+  for (int k = 0; e->reset_done && k < e->nslot; ++k) {
+    const Slot& sl = e->slot[k];
+    int rc = precision == A3C_PREC_BF16 ? a3c_lstm_prep_bf_launch(sl.P + e->L.off[T_LW], (uint16_t*)sl.lwt, nullptr)
+                                        : a3c_lstm_transpose_launch(sl.P + e->L.off[T_LW], sl.lwt, nullptr);
+    if (rc) return rc;
+  }
+  A3C_CHECK(hipDeviceSynchronize());
   drop_graphs(e);   // (they hold the other mode's kernels)
   return 0;
 }
@@ -2173,7 +2201,9 @@ static int play_impl(a3c_engine* e, const a3c_play_config& pc, int refill, float
   // forward weights of the live parameters, once per call
   int rc = e->nat ? a3c_nat_prep_launch(L, e->params, (uint16_t*)c.prep, nullptr, nullptr, nullptr, s)
                   : a3c_prep_fwd_launch(L, e->params, c.prep, s);
-  if (!rc && L.lstm) rc = a3c_lstm_transpose_launch(e->params + L.off[T_LW], c.lwt, s);
+  if (!rc && L.lstm)
+    rc = L.lstm_prec == A3C_PREC_BF16 ? a3c_lstm_prep_bf_launch(e->params + L.off[T_LW], (uint16_t*)c.lwt, s)
+                                      : a3c_lstm_transpose_launch(e->params + L.off[T_LW], c.lwt, s);
   if (rc) return rc;
   c.sched_env.assign(pc.n_episode, 0);
   c.sched_tau0.assign(pc.n_episode, 0);
@@ -2306,6 +2336,37 @@ extern "C" int a3c_engine_time_kernel(a3c_engine* e, int kernel, int iters, void
   const Slot& sl = e->slot[0];
   if (e->rs) A3C_CHECK(hipStreamSynchronize(e->rs));
   const LaunchMode& m = e->mode;            // time the variants the engine runs
+  if (kernel >= A3C_KER_LSTM_FWD && kernel <= A3C_KER_LSTM_DW) {   // the LSTM head's passes in the engine's lstm mode
+    if (!L.lstm) return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_time_kernel", "kernel id of the LSTM head");
+    const bool bf = L.lstm_prec == A3C_PREC_BF16;
+    if (kernel == A3C_KER_LSTM_FWD) {   // one cell step over E envs on act_l3 (the x form), into the bootstrap step's h, c
+      int rc0 = bf ? a3c_lstm_prep_bf_launch(e->params + L.off[T_LW], (uint16_t*)sl.lwt, s)
+                   : a3c_lstm_transpose_launch(e->params + L.off[T_LW], sl.lwt, s);
+      if (rc0) return rc0;
+      LstmStep st = {};
+      st.wt = sl.lwt; st.h_src = sl.lh; st.c_src = sl.lc; st.prev_terms = sl.terms; st.h = sl.lhb; st.c = sl.lcb;
+      auto go = [&]() -> int {
+        return bf ? a3c_lstm_fwd_bf_launch(e->params + L.off[T_LB], sl.act_l3, st, E, s)
+                  : a3c_lstm_fwd_launch(e->params + L.off[T_LB], sl.act_l3, st, E, s);
+      };
+      return time_launches(go, iters, s, avg_ms);
+    }
+    // the backward's chain (cell backwards + n fused step launches) or its gate-matrix gradient, on the last
+    // back-propagated rollout; they write dh3, the BPTT workspace and the gate tensors' gradient again
+    if (!e->grad_ready || !e->grad_applied)
+      return a3c_set_error(A3C_ERR_STATE, "a3c_engine_time_kernel", "LSTM backward passes: run and apply an iteration first");
+    const Slot& bs = e->slot[e->nslot == 2 ? (int)((e->iter - 2) & 1) : 0];
+    const LstmSeq q = {bs.act_l3, bs.lhp, bs.lcp, bs.lg, bs.lc, bs.terms};
+    float* dx = e->ws + a3c_bwd_plan(L, e->nE).dh3;
+    const int parts = kernel == A3C_KER_LSTM_BPTT ? LSTM_BPTT_CHAIN : LSTM_BPTT_DW;
+    auto go = [&]() -> int {
+      return bf ? a3c_lstm_bptt_bf_launch((const uint16_t*)bs.lwt, e->n, E, q, e->ldh, dx, e->grads + L.off[T_LW],
+                                          e->grads + L.off[T_LB], e->lws, s, parts)
+                : a3c_lstm_bptt_launch(bs.P + L.off[T_LW], e->n, E, q, e->ldh, dx, e->grads + L.off[T_LW],
+                                       e->grads + L.off[T_LB], e->lws, s, parts);
+    };
+    return time_launches(go, iters, s, avg_ms);
+  }
   if (e->nat != (kernel >= A3C_KER_NAT_C1F))
     return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_time_kernel", "kernel id of another trunk");
   if (e->nat) {   // one pass of the nature trunk: forward over E states, backward passes over n*E samples

@@ -15,10 +15,6 @@
 #include "lstm.h"
 #include "gemm.h"
 
-#define LT 16                    // envs per workgroup tile
-
-__device__ inline float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
-
 // Wt[c][k] = W[k][c]: W [512][1024] -> Wt [1024][512]; 32x32 tiles through LDS
 __global__ void __launch_bounds__(256) k_lstm_transpose(const float* __restrict__ W, float* __restrict__ Wt) {
   __shared__ float tile[32][33];
@@ -174,23 +170,6 @@ int a3c_lstm_fwd_launch(const float* bias, const float* x, const LstmStep& st, i
 }
 
 // ---------------------------------------------------------------------------------------
-// cell backward of step t at (e, u) given dh (heads + recurrence) and the carried dc
-__device__ inline void lstm_cell_bwd(int64_t e, int u, float dh, float dcn, const float* __restrict__ G,
-                                     const float* __restrict__ C, const float* __restrict__ CP,
-                                     float* __restrict__ dcp, float* __restrict__ DA) {
-  const int64_t i = e * LSTM_U + u;
-  const float* gp = G + e * LSTM_G + u;
-  const float ig = gp[0], jg = gp[LSTM_U], fg = gp[2 * LSTM_U], og = gp[3 * LSTM_U];
-  const float tc = tanhf(C[i]);
-  const float dc = dcn + dh * og * (1.f - tc * tc);
-  float* da = DA + e * LSTM_G + u;
-  da[0] = dc * jg * ig * (1.f - ig);
-  da[LSTM_U] = dc * ig * (1.f - jg * jg);
-  da[2 * LSTM_U] = dc * CP[i] * fg * (1.f - fg);
-  da[3 * LSTM_U] = dh * tc * og * (1.f - og);
-  dcp[i] = dc * fg;
-}
-
 // last step (t = n-1): nothing flows in from the future
 __global__ void __launch_bounds__(256) k_lstm_cell_bwd_last(int64_t E, const float* __restrict__ G,
                                                             const float* __restrict__ C, const float* __restrict__ CP,
@@ -201,17 +180,6 @@ __global__ void __launch_bounds__(256) k_lstm_cell_bwd_last(int64_t E, const flo
   const int64_t e = i / LSTM_U;
   lstm_cell_bwd(e, (int)(i - e * LSTM_U), dH[i], 0.f, G, C, CP, dcp, DA);
 }
-
-struct BpttStep {
-  const float* DAn;       // da of step t+1 [E][1024]
-  const float* xn;        // x of step t+1 [E][256] (fc ReLU output: the dx mask)
-  float* dxn;             // dx of step t+1 [E][256]
-  int cell;               // 1: run the cell backward of step t in the h-half epilogue
-  const float *G, *C, *CP, *dH;   // step t
-  const uint8_t* terms;   // terms[t] [E]
-  float* dcp;             // [E][U] carried dc (in: step t+1's dc*f, out: step t's)
-  float* DA;              // da of step t [E][1024]
-};
 
 // d[x, hp]_{t+1} = da_{t+1} W^T for a tile of 16 envs x 32 of the 512 columns, 8 waves = (16-col
 // half ct, K quarter kq); the epilogue writes dx_{t+1} (x half, fc ReLU mask) or, for the hp half,
@@ -287,11 +255,10 @@ static LstmWs lstm_ws(int n, int64_t E) {
 
 int64_t a3c_lstm_ws_floats(int n, int64_t E) { return lstm_ws(n, E).total; }
 
-// truncated BPTT: cell backward of step n-1, then per step one fused launch (d[x, hp]_{t+1} GEMM
-// + dx_{t+1} + cell backward of step t), then dx_0, then the gate-matrix gradients over n*E rows
-int a3c_lstm_bptt_launch(const float* W, int n, int64_t E, const LstmSeq& q, const float* dh, float* dx,
-                         float* dw, float* db, float* ws, hipStream_t s) {
-  if (n < 1 || E < 1 || E > 0x7fffffff / 8) return a3c_set_error(A3C_ERR_INVALID, "a3c_lstm_bptt", "bad shape");
+// the chain of a truncated BPTT: cell backward of step n-1, then per step one fused launch (d[x, hp]_{t+1} GEMM
+// + dx_{t+1} + cell backward of step t), then dx_0
+int a3c_lstm_bptt_chain(int n, int64_t E, const LstmSeq& q, const float* dh, float* dx, float* ws, hipStream_t s,
+                        int (*step)(int t, int64_t E, const BpttStep& b, const void* W, hipStream_t s), const void* W) {
   const LstmWs w = lstm_ws(n, E);
   float* DA = ws + w.da;
   float* dcp = ws + w.dcp;
@@ -301,7 +268,6 @@ int a3c_lstm_bptt_launch(const float* W, int n, int64_t E, const LstmSeq& q, con
                      q.gates + last * LSTM_G, q.c + last * LSTM_U, q.cp + last * LSTM_U, dh + last * LSTM_U, dcp,
                      DA + last * LSTM_G);
   A3C_CHECK(hipGetLastError());
-  const unsigned etiles = (unsigned)((E + LT - 1) / LT);
   for (int t = n - 2; t >= -1; --t) {
     const int64_t on = (int64_t)(t + 1) * E, ot = (int64_t)(t < 0 ? 0 : t) * E;
     BpttStep b = {};
@@ -313,10 +279,28 @@ int a3c_lstm_bptt_launch(const float* W, int n, int64_t E, const LstmSeq& q, con
     b.terms = q.terms + ot;
     b.dcp = dcp;
     b.DA = DA + ot * LSTM_G;
-    // t = -1: dx_0 only (x half of the columns)
-    hipLaunchKernelGGL(k_lstm_bptt_step, dim3(etiles, (t >= 0 ? LSTM_K : FC) / 32), dim3(512), 0, s, E, W, b);
-    A3C_CHECK(hipGetLastError());
+    if (int rc = step(t, E, b, W, s)) return rc;
   }
+  return 0;
+}
+
+static int bptt_step_f32(int t, int64_t E, const BpttStep& b, const void* W, hipStream_t s) {
+  // t = -1: dx_0 only (x half of the columns)
+  hipLaunchKernelGGL(k_lstm_bptt_step, dim3((unsigned)((E + LT - 1) / LT), (t >= 0 ? LSTM_K : FC) / 32), dim3(512), 0, s,
+                     E, (const float*)W, b);
+  A3C_CHECK(hipGetLastError());
+  return 0;
+}
+
+// truncated BPTT: the chain, then the gate-matrix gradients over n*E rows
+int a3c_lstm_bptt_launch(const float* W, int n, int64_t E, const LstmSeq& q, const float* dh, float* dx,
+                         float* dw, float* db, float* ws, hipStream_t s, int parts) {
+  if (n < 1 || E < 1 || E > 0x7fffffff / 8) return a3c_set_error(A3C_ERR_INVALID, "a3c_lstm_bptt", "bad shape");
+  const LstmWs w = lstm_ws(n, E);
+  float* DA = ws + w.da;
+  if (parts & LSTM_BPTT_CHAIN)
+    if (int rc = a3c_lstm_bptt_chain(n, E, q, dh, dx, ws, s, bptt_step_f32, W)) return rc;
+  if (!(parts & LSTM_BPTT_DW)) return 0;
   // dW[0:256] = x^T da (+ colsum -> db), dW[256:512] = hp^T da over all n*E rows
   const int64_t nE = (int64_t)n * E;
   for (int part = 0; part < 2; ++part) {

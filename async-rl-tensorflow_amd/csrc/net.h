@@ -43,6 +43,8 @@ struct NetLayout {
                             // a3c_make_layout leaves FP32, a3c_engine_set_precision / the _prec entries set it)
   int fc_prec;              // A3C_PREC_*: the nature trunk's fc compute mode, as prec (a3c_engine_set_fc_precision,
                             // the _prec2 entries)
+  int lstm_prec;            // A3C_PREC_*: the LSTM head's compute mode, as prec (a3c_engine_set_lstm_precision,
+                            // DESIGN §4q): lstm.hip's fp32 passes or lstm_bf16.hip's
   int nt;
   int64_t off[A3C_MAX_TENSORS], size[A3C_MAX_TENSORS];
   int64_t total;
@@ -72,6 +74,7 @@ inline int a3c_make_layout(const a3c_net_desc* d, NetLayout* L) {
   L->lstm = d->lstm_units != 0;
   L->prec = A3C_PREC_FP32;
   L->fc_prec = A3C_PREC_FP32;
+  L->lstm_prec = A3C_PREC_FP32;
   if (nature) {   // l1..l3 conv [kh,kw,cin,cout] + bias, l4 [3136,512] + bias, p [512,A] + bias, q [512,1] + bias
     const int64_t ns[12] = {8 * 8 * HIST * 32, 32, 4 * 4 * 32 * 64, 64, 3 * 3 * 64 * 64, 64, 3136LL * 512, 512,
                             512LL * A, A, 512, 1};

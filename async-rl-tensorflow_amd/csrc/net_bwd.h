@@ -89,6 +89,7 @@ struct LstmBwd {
   const float *h, *c, *hp, *cp, *gates;   // [n][E][...]
   float* dh;                              // [n*E][U] scratch: dL/dh_t from the heads
   float* ws;                              // a3c_lstm_ws_floats(n, E) floats
+  const uint16_t* wprep;                  // L.lstm_prec BF16: the prepared gate matrix of params (a3c_lstm_prep_bf_launch)
 };
 
 BwdPlan a3c_bwd_plan(const NetLayout& L, int64_t B, bool wks = false);

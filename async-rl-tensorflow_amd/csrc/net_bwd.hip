@@ -1178,8 +1178,13 @@ int a3c_backward_launch(const NetLayout& L, const BwdArgs& a, hipStream_t s, con
   if (lb) {
     // truncated BPTT: dL/dh_t -> dl3 (masked by the fc ReLU) + the gate-matrix gradients
     LstmSeq q = {act_l3, lb->hp, lb->cp, lb->gates, lb->c, ra.terms};
-    int rc0 = a3c_lstm_bptt_launch(P + L.off[T_LW], lb->n, lb->E, q, lb->dh, dh3, grads + L.off[T_LW],
-                                   grads + L.off[T_LB], lb->ws, s);
+    if (L.lstm_prec == A3C_PREC_BF16 && !lb->wprep)
+      return a3c_set_error(A3C_ERR_INVALID, "a3c_loss_backward", "the bf16 LSTM passes need the prepared gate matrix");
+    int rc0 = L.lstm_prec == A3C_PREC_BF16
+                  ? a3c_lstm_bptt_bf_launch(lb->wprep, lb->n, lb->E, q, lb->dh, dh3, grads + L.off[T_LW],
+                                            grads + L.off[T_LB], lb->ws, s)
+                  : a3c_lstm_bptt_launch(P + L.off[T_LW], lb->n, lb->E, q, lb->dh, dh3, grads + L.off[T_LW],
+                                         grads + L.off[T_LB], lb->ws, s);
     if (rc0) return rc0;
   }
 

@@ -935,7 +935,8 @@ int a3c_forward_launch(const NetLayout& L, const FwdArgs& a, hipStream_t s, cons
       st.fc_bias = P + L.off[T_FCB];
       st.l3_out = act_l3;
     }
-    rc = a3c_lstm_fwd_launch(P + L.off[T_LB], act_l3, st, B, s);
+    rc = L.lstm_prec == A3C_PREC_BF16 ? a3c_lstm_fwd_bf_launch(P + L.off[T_LB], act_l3, st, B, s)   // (st.wt: the bf16 prep)
+                                      : a3c_lstm_fwd_launch(P + L.off[T_LB], act_l3, st, B, s);
     if (rc) return rc;
     head_in = ls->h;
   }

@@ -16,6 +16,7 @@ accepted but the TF ps/worker cluster is replaced by one process per GPU under t
   python main.py --mode engine --dqn_type nature --precision bf16   the nature trunk's convolutions on single bf16 operands,
                  fp32 accumulation, parameters and activations
   python main.py --mode engine --dqn_type nature --precision bf16 --fc_precision bf16   ... and the fc's three GEMMs too
+  python main.py --mode engine --lstm true --lstm_precision bf16   the LSTM head's three matrix passes on bf16 operands
                  
   python main.py --mode engine --algo q --optimizer adam --env_name Catch-v0             shared Adam instead of RMSProp
   python main.py --mode engine --lstm true --env_name CatchMemory-v0   Catch that only a head with memory learns
@@ -131,6 +132,10 @@ def parse_flags(argv=None):
                  help="engine mode, --dqn_type nature: fp32 (the fc 3136 -> 512 and its backward as exact-fp32 GEMMs) or "
                       "bf16 (both operands of the three fc GEMMs rounded to bf16, fp32 accumulation; independent of "
                       "--precision; DESIGN §4p)")
+  p.add_argument('--lstm_precision', default='fp32',
+                 help="engine mode, --lstm true: fp32 (the LSTM head's cell forward, BPTT steps and gate-matrix gradient "
+                      "as exact-fp32 products) or bf16 (their operands rounded to bf16, fp32 accumulation, parameters "
+                      "and state; independent of the other two; DESIGN §4q)")
   # evaluation: --mode engine --is_train false (Agent.play, agent.py:351-391)
   p.add_argument('--n_episode', type=int, default=100, help='play: episodes (agent.py:351)')
   p.add_argument('--play_steps', type=int, default=10000, help="play: cap on an episode's env steps (agent.py:351 n_step)")
@@ -193,6 +198,11 @@ def engine_options(flags):
   if fc_precision == 'bf16' and flags.dqn_type != 'nature':
     raise ValueError('--fc_precision bf16 is the fc compute mode of the nature trunk (DESIGN §4p; the nips fc kernels '
                      'have none): use it with --dqn_type nature')
+  lstm_precision = getattr(flags, 'lstm_precision', 'fp32')
+  if lstm_precision not in ('fp32', 'bf16'):
+    raise ValueError("--lstm_precision must be fp32 or bf16 (got %r)" % (lstm_precision,))
+  if lstm_precision == 'bf16' and not flags.lstm:
+    raise ValueError('--lstm_precision bf16 is the compute mode of the LSTM head (DESIGN §4q): use it with --lstm true')
   first_screen = bool(getattr(flags, 'first_screen', False))
   if first_screen and game_kind(flags.env_name) != 'catch':
     raise ValueError('--first_screen is an option of the device game Catch (--env_name Catch-v0 or CatchMemory-v0, '
@@ -222,6 +232,8 @@ def engine_options(flags):
     kw['precision'] = precision
   if fc_precision != 'fp32':
     kw['fc_precision'] = fc_precision
+  if lstm_precision != 'fp32':
+    kw['lstm_precision'] = lstm_precision
   return kw
 
 
@@ -513,6 +525,9 @@ def main(argv=None):
                      'is the per-op loop in fp32')
   if flags.mode == 'agent' and flags.fc_precision != 'fp32':
     raise ValueError('--fc_precision is an engine option (the nature trunk of --mode engine, DESIGN §4p): --mode agent '
+                     'is the per-op loop in fp32')
+  if flags.mode == 'agent' and flags.lstm_precision != 'fp32':
+    raise ValueError('--lstm_precision is an engine option (the LSTM head of --mode engine, DESIGN §4q): --mode agent '
                      'is the per-op loop in fp32')
   if flags.mode == 'agent' and flags.first_screen:
     raise ValueError('--first_screen is an engine option: --mode agent is the reference loop (agent.py:59-67) as it stands')

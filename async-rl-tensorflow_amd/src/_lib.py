@@ -164,6 +164,9 @@ SIGNATURES = {
     'a3c_lstm_step': (c_int, [c_void_p] * 6 + [c_i64] + [c_void_p] * 6),
     'a3c_lstm_workspace_bytes': (c_int, [c_int, c_i64, ctypes.POINTER(c_i64)]),
     'a3c_lstm_bptt': (c_int, [c_void_p, c_int, c_i64] + [c_void_p] * 12),
+    'a3c_lstm_prepare': (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
+    'a3c_lstm_step_prec': (c_int, [c_void_p] * 6 + [c_i64] + [c_void_p] * 8 + [c_int, c_void_p]),
+    'a3c_lstm_bptt_prec': (c_int, [c_void_p, c_int, c_i64] + [c_void_p] * 11 + [c_int, c_void_p]),
     'a3c_env_create': (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_u64, c_int, ctypes.POINTER(c_void_p)]),
     'a3c_env_create_ex': (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_u64, c_int, c_int,
                                   ctypes.POINTER(c_void_p)]),
@@ -188,6 +191,7 @@ SIGNATURES = {
     'a3c_engine_set_q_lambda': (c_int, [c_void_p, c_int, c_double]),
     'a3c_engine_set_precision': (c_int, [c_void_p, c_int]),
     'a3c_engine_set_fc_precision': (c_int, [c_void_p, c_int]),
+    'a3c_engine_set_lstm_precision': (c_int, [c_void_p, c_int]),
     'a3c_engine_reset': (c_int, [c_void_p, c_void_p, c_void_p]),
     'a3c_engine_rollout_grad': (c_int, [c_void_p, c_void_p]),
     'a3c_engine_apply': (c_int, [c_void_p, c_void_p]),
@@ -259,6 +263,8 @@ OPTIONAL_IN_OLD_BUILDS = MEASUREMENT_ONLY + ('a3c_engine_exchange_split', 'a3c_e
                                              'a3c_nature_forward_prec', 'a3c_nature_loss_backward_prec',
                                              'a3c_engine_set_precision', 'a3c_nature_forward_prec2',
                                              'a3c_nature_loss_backward_prec2', 'a3c_engine_set_fc_precision',
+                                             'a3c_lstm_prepare', 'a3c_lstm_step_prec', 'a3c_lstm_bptt_prec',
+                                             'a3c_engine_set_lstm_precision',
                                              'a3c_gemm_workspace_bytes', 'a3c_gemm_f32', 'a3c_gemm3_f32')
 
 # the nature trunk's conv compute modes (include/a3c_hip.h A3C_PREC_*)
@@ -279,6 +285,8 @@ KER_NAT = {'conv1_fwd': 7, 'conv2_fwd': 8, 'conv3_fwd': 9, 'fc_fwd': 10, 'conv3_
            'conv2_dx': 14, 'conv1_dw': 15}
 # the fc's two backward GEMMs, passes of their own (A3C_KER_NAT_FCW / _FCX)
 KER_NAT_FC_BWD = {'fc_dw': 16, 'fc_dx': 17}
+# the LSTM head's three matrix passes (A3C_KER_LSTM_*)
+KER_LSTM = {'lstm_fwd': 18, 'lstm_bptt': 19, 'lstm_dw': 20}
 
 _lib = None
 

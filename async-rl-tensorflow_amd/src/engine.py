@@ -57,7 +57,7 @@ class Engine:
     def __init__(self, num_envs=256, n_step=5, action_size=6, algo='a3c', start_lives=0, num_frames=None,
                  seed=123, env_id_base=0, world_size=1, use_graph=False, overlap=False, lstm=False,
                  external_env=False, dqn_type='nips', game='synth', catch_rules=None, first_screen=None, q_lambda=None,
-                 precision='fp32', fc_precision='fp32', **overrides):
+                 precision='fp32', fc_precision='fp32', lstm_precision='fp32', **overrides):
         """game: 'synth' (the synthetic Atari stand-in) or 'catch' (Catch-v0, DESIGN §4g: action_size 3,
         start_lives 0, device envs, raw RGB pool; random_start is ignored).  num_frames=None: 1024
         frames (Catch needs its 640: a smaller explicit value is rejected by the library).
@@ -87,7 +87,12 @@ class Engine:
         fc_precision='fp32' | 'bf16' ('fp32': no call is made): a3c_engine_set_fc_precision right
         after the create -- 'bf16' (dqn_type 'nature' only) runs the fc forward and its two backward GEMMs on one
         bf16 term per operand with fp32 accumulation, independently of ``precision``; kept as ``fc_precision``.
-        Not in the saved state either."""
+        Not in the saved state either.
+        lstm_precision='fp32' | 'bf16' ('fp32': no call is made): a3c_engine_set_lstm_precision right
+        after the create -- 'bf16' (lstm=True only) runs the LSTM head's cell forward, BPTT steps and gate-matrix
+        gradient on one bf16 term per operand with fp32 accumulation, independently of the other two; kept as
+        ``lstm_precision``.  Not in the saved state either."""
+        self.lstm_precision = self._check_lstm_precision(lstm_precision, lstm)
         self.precision = self._check_precision(precision, str(dqn_type).lower())
         self.fc_precision = self._check_fc_precision(fc_precision, str(dqn_type).lower())
         self.q_lambda = self._check_q_lambda(q_lambda, algo, overrides.get('q_nstep', 0))
@@ -173,6 +178,9 @@ class Engine:
         if self.fc_precision != 'fp32':
             check(lib().a3c_engine_set_fc_precision(h, _lib.PRECISIONS[self.fc_precision]),
                   'a3c_engine_set_fc_precision')
+        if self.lstm_precision != 'fp32':
+            check(lib().a3c_engine_set_lstm_precision(h, _lib.PRECISIONS[self.lstm_precision]),
+                  'a3c_engine_set_lstm_precision')
         b = _lib.EngineBuffers()
         check(lib().a3c_engine_get_buffers(h, ctypes.byref(b)), 'a3c_engine_get_buffers')
         self._b = b
@@ -256,6 +264,19 @@ class Engine:
         value = self._check_fc_precision(value, self.dqn_type)
         check(lib().a3c_engine_set_fc_precision(self._h, _lib.PRECISIONS[value]), 'a3c_engine_set_fc_precision')
         self.fc_precision = value
+
+    @staticmethod
+    def _check_lstm_precision(value, lstm):
+        _lib.precision_code(value, 'lstm_precision')
+        if value == 'bf16' and not lstm:
+            raise ValueError("lstm_precision 'bf16' is the LSTM head's compute mode (lstm=False has none)")
+        return value
+
+    def set_lstm_precision(self, value):
+        """a3c_engine_set_lstm_precision between iterations: no reset, the next rollout and gradient follow it."""
+        value = self._check_lstm_precision(value, self.lstm)
+        check(lib().a3c_engine_set_lstm_precision(self._h, _lib.PRECISIONS[value]), 'a3c_engine_set_lstm_precision')
+        self.lstm_precision = value
 
     def _slot_views(self, k):
         b = _lib.EngineBuffers()

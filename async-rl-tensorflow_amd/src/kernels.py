@@ -106,28 +106,47 @@ def param_names_shapes(action_size, algo='a3c', lstm=False, dqn_type='nips'):
     return out
 
 
-def lstm_step(w, b, x, h_src, c_src, prev_terms=None, save=True):
+def lstm_step(w, b, x, h_src, c_src, prev_terms=None, save=True, precision=None, fc_part=None, fc_bias=None):
     """One C5 LSTM cell step (a3c_lstm_step) for B envs: x [B,256], (h_src, c_src) [B,U] the previous
-    step's outputs (zeroed where prev_terms [B] u8 is set).  Returns dict h, c (+ hp, cp, gates)."""
-    B, U = int(x.shape[0]), _lib.A3C_LSTM_UNITS
-    for t, nm in ((w, 'w'), (b, 'b'), (x, 'x'), (h_src, 'h_src'), (c_src, 'c_src')):
+    step's outputs (zeroed where prev_terms [B] u8 is set).  Returns dict h, c (+ hp, cp, gates).
+    precision: None (a3c_lstm_transpose + a3c_lstm_step), or 'fp32' | 'bf16' (a3c_lstm_prepare +
+    a3c_lstm_step_prec).  With a precision the input may come as the fc's K-slice partials instead:
+    x None, fc_part [8,B,256] and fc_bias [256]; the folded rows are returned as ``l3``."""
+    B, U = int(h_src.shape[0]), _lib.A3C_LSTM_UNITS
+    for t, nm in ((w, 'w'), (b, 'b'), (h_src, 'h_src'), (c_src, 'c_src')) + (((x, 'x'),) if fc_part is None else
+                                                                              ((fc_part, 'fc_part'), (fc_bias, 'fc_bias'))):
         _dev(t, torch.float32, nm)
     if prev_terms is not None:
         _dev(prev_terms, torch.uint8, 'prev_terms')
-    new = lambda *s: torch.empty(s, dtype=torch.float32, device=x.device)  # noqa: E731
+    new = lambda *s: torch.empty(s, dtype=torch.float32, device=w.device)  # noqa: E731
     out = dict(h=new(B, U), c=new(B, U))
     if save:
         out.update(hp=new(B, U), cp=new(B, U), gates=new(B, 4 * U))
-    w_t = torch.empty((w.shape[1], w.shape[0]), dtype=torch.float32, device=x.device)
-    check(lib().a3c_lstm_transpose(ptr(w), ptr(w_t), stream_handle()), 'a3c_lstm_transpose')
-    check(lib().a3c_lstm_step(ptr(w_t), ptr(b), ptr(x), ptr(h_src), ptr(c_src), ptr(prev_terms), B,
-                              ptr(out.get('hp')), ptr(out.get('cp')), ptr(out.get('gates')), ptr(out['h']),
-                              ptr(out['c']), stream_handle()), 'a3c_lstm_step')
+    w_t = torch.empty((w.shape[1], w.shape[0]), dtype=torch.float32, device=w.device)
+    if precision is None:
+        if fc_part is not None:
+            raise ValueError('fc_part is an input of a3c_lstm_step_prec: give a precision')
+        check(lib().a3c_lstm_transpose(ptr(w), ptr(w_t), stream_handle()), 'a3c_lstm_transpose')
+        check(lib().a3c_lstm_step(ptr(w_t), ptr(b), ptr(x), ptr(h_src), ptr(c_src), ptr(prev_terms), B,
+                                  ptr(out.get('hp')), ptr(out.get('cp')), ptr(out.get('gates')), ptr(out['h']),
+                                  ptr(out['c']), stream_handle()), 'a3c_lstm_step')
+        return out
+    code = _lib.precision_code(precision)
+    if fc_part is not None:
+        if x is not None or tuple(fc_part.shape) != (8, B, FC):
+            raise ValueError('fc_part [8, B, 256] takes the place of x')
+        out['l3'] = new(B, FC)
+    check(lib().a3c_lstm_prepare(ptr(w), ptr(w_t), code, stream_handle()), 'a3c_lstm_prepare')
+    check(lib().a3c_lstm_step_prec(ptr(w_t), ptr(b), ptr(x), ptr(h_src), ptr(c_src), ptr(prev_terms), B,
+                                   ptr(out.get('hp')), ptr(out.get('cp')), ptr(out.get('gates')), ptr(out['h']),
+                                   ptr(out['c']), ptr(fc_part), ptr(fc_bias), ptr(out.get('l3')), code, stream_handle()),
+          'a3c_lstm_step_prec')
     return out
 
 
-def lstm_bptt(w, x, hp, cp, gates, c, terms, dh):
-    """Truncated BPTT (a3c_lstm_bptt) over [n,E,...] sequences; returns (dx masked by x > 0, dw, db)."""
+def lstm_bptt(w, x, hp, cp, gates, c, terms, dh, precision=None):
+    """Truncated BPTT (a3c_lstm_bptt) over [n,E,...] sequences; returns (dx masked by x > 0, dw, db).
+    precision: None, or 'fp32' | 'bf16' (a3c_lstm_prepare + a3c_lstm_bptt_prec)."""
     n, E = int(terms.shape[0]), int(terms.shape[1])
     for t, nm in ((w, 'w'), (x, 'x'), (hp, 'hp'), (cp, 'cp'), (gates, 'gates'), (c, 'c'), (dh, 'dh')):
         _dev(t, torch.float32, nm)
@@ -138,8 +157,17 @@ def lstm_bptt(w, x, hp, cp, gates, c, terms, dh):
     dx = torch.empty_like(x)
     dw = torch.empty_like(w)
     db = torch.empty(w.shape[-1], dtype=torch.float32, device=x.device)
-    check(lib().a3c_lstm_bptt(ptr(w), n, E, ptr(x), ptr(hp), ptr(cp), ptr(gates), ptr(c), ptr(terms), ptr(dh),
-                              ptr(dx), ptr(dw), ptr(db), ptr(ws), stream_handle()), 'a3c_lstm_bptt')
+    if precision is None:
+        check(lib().a3c_lstm_bptt(ptr(w), n, E, ptr(x), ptr(hp), ptr(cp), ptr(gates), ptr(c), ptr(terms), ptr(dh),
+                                  ptr(dx), ptr(dw), ptr(db), ptr(ws), stream_handle()), 'a3c_lstm_bptt')
+        return dx, dw, db
+    code = _lib.precision_code(precision)
+    wp = w
+    if code == _lib.PREC_BF16:
+        wp = torch.empty_like(w)
+        check(lib().a3c_lstm_prepare(ptr(w), ptr(wp), code, stream_handle()), 'a3c_lstm_prepare')
+    check(lib().a3c_lstm_bptt_prec(ptr(wp), n, E, ptr(x), ptr(hp), ptr(cp), ptr(gates), ptr(c), ptr(terms), ptr(dh),
+                                   ptr(dx), ptr(dw), ptr(db), ptr(ws), code, stream_handle()), 'a3c_lstm_bptt_prec')
     return dx, dw, db
 
 

@@ -442,6 +442,30 @@ int a3c_lstm_bptt(const float* w, int n, int64_t E, const float* x, const float*
                   const float* gates, const float* c, const uint8_t* terms, const float* dh, float* dx,
                   float* dw, float* db, void* workspace, void* stream);
 
+/* The LSTM head's compute mode per call.  precision A3C_PREC_FP32: the entries above, bit for bit.
+ * A3C_PREC_BF16: the three matrix passes on gfx950's bf16 matrix cores, every operand rounded to nearest
+ * even, one product per K step, fp32 accumulation:
+ *    a_t = rn([x_t, keep h_{t-1}]) rn(W) + b       d[x, hp]_{t+1} = rn(da_{t+1}) rn(W)^T
+ *    dw  = rn([x, hp])^T rn(da) over all n*E rows   db = column sums of the unrounded da
+ * with parameters, the carried and saved state, the elementwise cell update and backward, the masks and
+ * workspace sizes as in fp32.
+ *  a3c_lstm_prepare: w_prep (2 MB, 16-byte aligned) = what the forward and the BPTT read of w.  FP32: w^T
+ *    (a3c_lstm_transpose).  BF16: rn(w)^T [4U][256+U] bf16, then rn(w) [256+U][4U] bf16.
+ *  a3c_lstm_step_prec: a3c_lstm_step on w_prep, with the cell's input either x, or (x NULL) the fc layer's
+ *    A3C_LSTM_FC_PARTS K-slice partials fc_part [parts][B][256]: the kernel adds them in slice order, adds
+ *    fc_bias [256], applies the ReLU, and writes the rows (unrounded) to l3_out [B][256].
+ *  a3c_lstm_bptt_prec: a3c_lstm_bptt; w is the fp32 gate matrix (FP32) or a3c_lstm_prepare's block (BF16).
+ * A3C_ERR_INVALID: a precision that is neither constant, then the checks of the entries above. */
+#define A3C_LSTM_FC_PARTS 8
+int a3c_lstm_prepare(const float* w, void* w_prep, int precision, void* stream);
+int a3c_lstm_step_prec(const void* w_prep, const float* b, const float* x, const float* h_src, const float* c_src,
+                       const uint8_t* prev_terms, int64_t B, float* hp, float* cp, float* gates, float* h,
+                       float* c, const float* fc_part, const float* fc_bias, float* l3_out, int precision,
+                       void* stream);
+int a3c_lstm_bptt_prec(const void* w, int n, int64_t E, const float* x, const float* hp, const float* cp,
+                       const float* gates, const float* c, const uint8_t* terms, const float* dh, float* dx,
+                       float* dw, float* db, void* workspace, int precision, void* stream);
+
 /* K12  target sync (agent.py:342-344) / theta' <- theta (network.py:96-107). */
 int a3c_copy_params(float* dst, const float* src, int64_t n, void* stream);
 
@@ -709,6 +733,17 @@ int a3c_engine_set_precision(a3c_engine* eng, int precision);
  * computed gradient not yet applied.  Not in the checkpoint's state (a resumed run gives it again).
  * python async-rl-tensorflow_amd/main.py --mode engine --dqn_type nature --precision bf16 --fc_precision bf16 */
 int a3c_engine_set_fc_precision(a3c_engine* eng, int precision);
+/* lstm_precision: the compute mode of an engine's LSTM head, A3C_PREC_FP32 (the default: every
+ * launch is what it is without this call) or A3C_PREC_BF16 (the definition stands at a3c_lstm_step_prec),
+ * independent of the other two switches.  In BF16 the weight prep at the rollout start, the cell step of the
+ * rollout steps, the bootstrap state and play, and the gradient's BPTT steps and gate-matrix gradient run
+ * lstm_bf16.hip's kernels.  A setter with the rules of a3c_engine_set_precision: no reset, the next rollout
+ * and gradient follow it (the slots' prepared gate matrices are written again in the new mode), captured
+ * graphs are dropped.  A3C_ERR_INVALID, in this order: a precision that is neither constant, eng NULL, an
+ * engine without the LSTM head.  A3C_ERR_STATE: a computed gradient not yet applied.  Not in the
+ * checkpoint's state (a resumed run gives it again).
+ * python async-rl-tensorflow_amd/main.py --mode engine --lstm true --lstm_precision bf16 */
+int a3c_engine_set_lstm_precision(a3c_engine* eng, int precision);
 /* fill the frame pool, reset the envs (new_random_game, environment.py:35-40), fill each
  * history with 4 copies of the first screen (agent.py:37-38) and initialise params
  * from host memory (nullable -> keep), rms slot = 1, mom = 0 (Adam: m = v = 0, products = 1). */
@@ -1007,6 +1042,11 @@ int a3c_engine_play_buffers(a3c_engine* eng, a3c_play_buffers* out);
  * writes the fc weights' gradient again: A3C_ERR_STATE while a computed gradient is not yet applied. */
 #define A3C_KER_NAT_FCW 16     /* fc weight gradient l3^T dl4 into grads (+ the dl4 column sums) */
 #define A3C_KER_NAT_FCX 17     /* fc input gradient dl3 = (dl4 W4^T) * (l3 > 0)             */
+/* The LSTM head's three matrix passes in the engine's lstm mode: LSTM engines only
+ * (A3C_ERR_INVALID otherwise); the two backward passes after an applied iteration (A3C_ERR_STATE). */
+#define A3C_KER_LSTM_FWD 18    /* one cell step over B = E on act_l3 (the x form)            */
+#define A3C_KER_LSTM_BPTT 19   /* the BPTT chain: cell backward of step n-1 + n fused step launches */
+#define A3C_KER_LSTM_DW 20     /* gate-matrix gradient + db over n*E rows (fp32: two GEMMs + the column fold) */
 /* Live launch spans, recorded by the kernels themselves inside the engine's graphs (which 0:
  * k_conv_bwd, 1: k_head_screen_conv12): per launch, last workgroup end - first workgroup start
  * (s_memrealtime).  reset = 1 clears the records (before a timed region); otherwise returns the
