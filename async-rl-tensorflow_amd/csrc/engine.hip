@@ -1375,6 +1375,24 @@ extern "C" int a3c_engine_set_lstm_precision(a3c_engine* e, int precision) {
   return 0;
 }
 
+// conv_bwd_precision: the NIPS trunk's conv backward compute mode, the fourth switch: read from the
+// layout by a3c_conv_bwd_launch, the one site the three backward paths (and a3c_engine_time_kernel) launch it from.
+// The forward, the rollout and the saved activations do not see it.
+extern "C" int a3c_engine_set_conv_bwd_precision(a3c_engine* e, int precision) {
+  if (precision != A3C_PREC_FP32 && precision != A3C_PREC_BF16)
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_set_conv_bwd_precision", "precision: A3C_PREC_FP32 or A3C_PREC_BF16");
+  if (!e) return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_set_conv_bwd_precision", "null");
+  if (e->nat)
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_set_conv_bwd_precision",
+                         "conv_bwd_precision is the nips trunk's conv backward mode (the nature trunk has precision)");
+  if (e->grad_ready && !e->grad_applied)
+    return a3c_set_error(A3C_ERR_STATE, "a3c_engine_set_conv_bwd_precision", "a gradient is pending: apply it first");
+  A3C_CHECK(hipDeviceSynchronize());
+  e->L.cbwd_prec = precision;
+  drop_graphs(e);   // (they hold the other mode's kernel)
+  return 0;
+}
+
 extern "C" int a3c_engine_reset(a3c_engine* e, const float* host_params, void* stream) {
   if (!e) return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_reset", "null");
   hipStream_t s = (hipStream_t)stream;

@@ -45,6 +45,8 @@ struct NetLayout {
                             // the _prec2 entries)
   int lstm_prec;            // A3C_PREC_*: the LSTM head's compute mode, as prec (a3c_engine_set_lstm_precision,
                             // DESIGN §4q): lstm.hip's fp32 passes or lstm_bf16.hip's
+  int cbwd_prec;            // A3C_PREC_*: the NIPS conv backward's compute mode, as prec (a3c_engine_set_conv_bwd_precision,
+                            // a3c_loss_backward_prec): k_conv_bwd or conv_bwd_bf16.hip's k_conv_bwd_bf
   int nt;
   int64_t off[A3C_MAX_TENSORS], size[A3C_MAX_TENSORS];
   int64_t total;
@@ -75,6 +77,7 @@ inline int a3c_make_layout(const a3c_net_desc* d, NetLayout* L) {
   L->prec = A3C_PREC_FP32;
   L->fc_prec = A3C_PREC_FP32;
   L->lstm_prec = A3C_PREC_FP32;
+  L->cbwd_prec = A3C_PREC_FP32;
   if (nature) {   // l1..l3 conv [kh,kw,cin,cout] + bias, l4 [3136,512] + bias, p [512,A] + bias, q [512,1] + bias
     const int64_t ns[12] = {8 * 8 * HIST * 32, 32, 4 * 4 * 32 * 64, 64, 3 * 3 * 64 * 64, 64, 3136LL * 512, 512,
                             512LL * A, A, 512, 1};

@@ -166,6 +166,12 @@ int a3c_head_screen_conv12_launch(const NetLayout& L, const float* P, const floa
                                   const HeadSelect& sel, const Conv12Next& nx, hipStream_t s);
 int a3c_conv12_launch(const NetLayout& L, const float* P, const uint8_t* prep, const StateAddr& sa, int64_t B,
                       float* act_l1, float* act_l2, hipStream_t s, const LaunchMode& m, uint32_t* l2m = nullptr);
+// conv_bwd_bf16.hip (L.cbwd_prec BF16): k_conv_bwd_bf on the plan's grid, into the plan's slabs;
+// smem: its own CB_BF_SMEM bytes of dynamic LDS, or the solo reservation of a launch beside the rollout
+#define CB_BF_SMEM 81136
+int a3c_conv_bwd_bf_launch(const StateAddr& sa, int64_t B, const BwdPlan& p, const float* act_l1, const float* dl2,
+                           const float* W2, float* slab, int smem, hipStream_t s);
+void a3c_conv_bwd_bf_set_smem(int smem);
 int a3c_conv_bwd_launch(const NetLayout& L, const float* P, const StateAddr& sa, int64_t B, const float* act_l1,
                         const float* dl2, float* ws, hipStream_t s, const LaunchMode& m);
 

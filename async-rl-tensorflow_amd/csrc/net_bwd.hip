@@ -1359,6 +1359,10 @@ int a3c_conv_bwd_launch(const NetLayout& L, const float* P, const StateAddr& sa,
   static const bool ablate = getenv("A3C_ABL_CBWD") != nullptr;   // measurement only: no conv backward
   if (ablate) return 0;
 #endif
+  static_assert(CB_BF_SMEM <= CB_SMEM_SOLO, "k_conv_bwd_bf fits the solo reservation");
+  if (L.cbwd_prec == A3C_PREC_BF16)   // one 4-wave variant; beside the rollout it reserves what the compact kernels do
+    return a3c_conv_bwd_bf_launch(sa, B, p, act_l1, dl2, P + L.off[T_L2W], ws + p.cslab,
+                                  m.shared_gpu ? cb_smem(CB_BF_SMEM) : CB_BF_SMEM, s);
   // sync: the DMA-prefetching kernel at 8 waves (2 per SIMD) owns the GPU; overlap: the compact
   // 4-wave kernel leaves registers and LDS for the concurrent rollout (measured, tools/ab.sh)
   static const int env_nw = (int)A3C_AB_KNOB("A3C_CB_WAVES", 0);
@@ -1407,6 +1411,7 @@ void a3c_conv_bwd_set_smem() {
   (void)hipFuncSetAttribute((const void*)k_conv_bwd<false, 4, false>, (hipFuncAttribute)a, cb_smem(CB_SMEM_COMPACT));
   (void)hipFuncSetAttribute((const void*)k_conv_bwd<false, 4, true>, (hipFuncAttribute)a, cb_smem(CB_SMEM_COMPACT_LX));
   (void)hipFuncSetAttribute((const void*)k_conv_bwd<false, 8, true>, (hipFuncAttribute)a, cb_smem(CB_SMEM_COMPACT_LX));
+  a3c_conv_bwd_bf_set_smem(cb_smem(CB_BF_SMEM));
 }
 
 // ---------------------------------------------------------------------------------------

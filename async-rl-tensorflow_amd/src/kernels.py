@@ -327,7 +327,9 @@ class Net:
 
     # -- K8/K9 loss + backward ----------------------------------------------------------
     def loss_backward(self, params, states, fwd, actions, target, beta=0.01, literal_adv=False,
-                      grads=None, workspace=None):
+                      grads=None, workspace=None, conv_bwd_precision=None):
+        """conv_bwd_precision: None or 'fp32' (a3c_loss_backward), or 'bf16' (a3c_loss_backward_prec: the fused
+        conv backward on single bf16 operands; only l1_w, l1_b, l2_w and l2_b move)."""
         _dev(actions, torch.int32, 'actions')
         _dev(target, torch.float32, 'target')
         B = int(states.shape[0])
@@ -336,6 +338,12 @@ class Net:
             grads = torch.zeros(self.total, dtype=torch.float32, device=dev)
         loss = torch.zeros(4, dtype=torch.float32, device=dev)
         ws = workspace if workspace is not None else self.workspace(B, dev)
+        if conv_bwd_precision is not None and _lib.precision_code(conv_bwd_precision, 'conv_bwd_precision') != _lib.PREC_FP32:
+            check(lib().a3c_loss_backward_prec(ctypes.byref(self.desc), ptr(params), ptr(states), B, ptr(fwd['l1']),
+                                               ptr(fwd['l2']), ptr(fwd['l3']), ptr(fwd['z']), ptr(actions), ptr(target),
+                                               float(beta), 1 if literal_adv else 0, _lib.PREC_BF16, ptr(grads),
+                                               ptr(loss), ptr(ws), stream_handle()), 'a3c_loss_backward_prec')
+            return grads, loss
         check(lib().a3c_loss_backward(ctypes.byref(self.desc), ptr(params), ptr(states), B, ptr(fwd['l1']),
                                       ptr(fwd['l2']), ptr(fwd['l3']), ptr(fwd['z']), ptr(actions), ptr(target),
                                       float(beta), 1 if literal_adv else 0, ptr(grads), ptr(loss), ptr(ws),

@@ -322,6 +322,22 @@ int a3c_loss_backward(const a3c_net_desc* net, const float* params, const uint8_
                       int literal_adv, float* grads, float* loss_out, void* workspace,
                       void* stream);
 
+/* The conv backward's compute mode per call: a3c_loss_backward's argument list plus
+ * conv_bwd_precision.  A3C_PREC_FP32 is a3c_loss_backward, bit for bit (that entry is this one with FP32).
+ * A3C_PREC_BF16 replaces k_conv_bwd -- dW2 and dl1 on the fp32 MFMA, dW1 on bf16 with dl1 split into three
+ * terms -- by k_conv_bwd_bf: the three passes on gfx950's bf16 matrix cores, every operand rounded to
+ * nearest even once (rn), one product per K step, fp32 accumulation:
+ *    dW2 = patches(rn(l1))^T rn(dl2)      dl1 = col2im(rn(dl2) rn(W2)^T) * (l1 > 0)
+ *    dW1 = patches(x)^T rn(dl1) / 255     db2, db1 = sums of the unrounded dl2, dl1
+ * Only the gradients of l1_w, l1_b, l2_w move (l2_b in its summation order); every other tensor, the loss
+ * words and the workspace size are those of FP32.
+ * A3C_ERR_INVALID: a precision that is neither constant, then a3c_loss_backward's checks. */
+int a3c_loss_backward_prec(const a3c_net_desc* net, const float* params, const uint8_t* states,
+                           int64_t B, const float* act_l1, const float* act_l2, const float* act_l3,
+                           const float* z, const int32_t* actions, const float* target, float beta,
+                           int literal_adv, int conv_bwd_precision, float* grads, float* loss_out,
+                           void* workspace, void* stream);
+
 /* ----------------------------------------------------------------------------
  * K10+K11  per-tensor clip_by_norm (agent.py:316-319) + TF ApplyRMSProp
  *  (main.py:63-65, agent.py:321): ms += (g^2-ms)(1-rho); mom = mom*momentum +
@@ -744,6 +760,18 @@ int a3c_engine_set_fc_precision(a3c_engine* eng, int precision);
  * checkpoint's state (a resumed run gives it again).
  * python async-rl-tensorflow_amd/main.py --mode engine --lstm true --lstm_precision bf16 */
 int a3c_engine_set_lstm_precision(a3c_engine* eng, int precision);
+/* conv_bwd_precision: the compute mode of a nips-trunk engine's fused conv backward,
+ * A3C_PREC_FP32 (the default: every launch is what it is without this call) or A3C_PREC_BF16 (the definition
+ * stands at a3c_loss_backward_prec), independent of the other three switches.  Every backward path (one-pass,
+ * split exchange, LSTM, q) launches the conv backward from one site, which reads the mode; the forward, the
+ * rollout, the saved activations and the workspace do not depend on it.  a3c_engine_time_kernel(
+ * A3C_KER_CONV_BWD) and the live spans measure the kernel of the mode the engine is in.  A setter with the
+ * rules of a3c_engine_set_precision: valid between iterations, no reset, captured graphs are dropped.
+ * A3C_ERR_INVALID, in this order: a precision that is neither constant, eng NULL, a nature-trunk engine (the
+ * mode is the nips trunk's).  A3C_ERR_STATE: a computed gradient not yet applied.  Not in the checkpoint's
+ * state (a resumed run gives it again).
+ * python async-rl-tensorflow_amd/main.py --mode engine --conv_bwd_precision bf16 */
+int a3c_engine_set_conv_bwd_precision(a3c_engine* eng, int precision);
 /* fill the frame pool, reset the envs (new_random_game, environment.py:35-40), fill each
  * history with 4 copies of the first screen (agent.py:37-38) and initialise params
  * from host memory (nullable -> keep), rms slot = 1, mom = 0 (Adam: m = v = 0, products = 1). */

@@ -80,7 +80,51 @@ def r4_fmap(G):               # cb_fmap
     return 4 * (10 + 2 * (oy >> 3) + (rem >> 1)) + 2 * (rem & 1) + ((local >> 2) & 1)
 
 
+def bf16_report():
+    """k_conv_bwd_bf's operand reads (csrc/conv_bwd_bf16.hip): LDS-array cycles per wave and sample at the
+    strides the kernel uses against the unpadded ones.  ds_read_b64 is modelled as two 32-lane halves over the 64
+    banks (an assumption: the note this model rests on gives the b32 and b128 groupings only)."""
+    H64 = [range(0, 32), range(32, 64)]
+    lanes = [(l & 15, l >> 4) for l in range(64)]
+
+    def a_l1(ci_stride, kh):           # (a) A operand: 5 chunks x 2 parities x (b64, b64, b32)
+        tot = 0
+        for c in range(5):
+            for par in range(2):
+                base = [(i * ci_stride + (2 * (2 * min(2 * c + (j >> 1), 8) + kh) + par) * 24 + 16 * (j & 1)) // 4
+                        for i, j in lanes]
+                tot += 2 * cycles(base, H64, 64, 2) + cycles([b + 4 for b in base], H64, 32, 1)
+        return tot
+
+    def a_dl2t(row):                   # (a) B operand: 5 chunks x 2 halves of co, b128
+        return sum(cycles([((i + 16 * h) * row + 64 * c + 16 * j) // 4 for i, j in lanes], B128_GROUPS, 64, 4)
+                   for c in range(5) for h in range(2))
+
+    def b_dl2r(row):                   # (b) A operand: 7 tiles x 4 taps, b128, class-independent
+        tot = 0
+        for mt in range(7):
+            for dy in range(2):
+                for dx in range(2):
+                    addrs = []
+                    for i, j in lanes:
+                        ay, cx = divmod(min(16 * mt + i, 99), 10)
+                        v = (ay > 0 if dy else ay < 9) and (cx > 0 if dx else cx < 9)
+                        addrs.append((((ay - dy) * 9 + cx - dx if v else 81) * row + 16 * j) // 4)
+                    tot += cycles(addrs, B128_GROUPS, 64, 4)
+        return tot
+
+    print('k_conv_bwd_bf, LDS cycles per wave and sample (kernel stride / unpadded stride):')
+    print('  (a) l1p reads, waves kh 0..3:', [a_l1(976, k) for k in range(4)], '/', [a_l1(960, k) for k in range(4)])
+    print('  (a) dl2t reads:', a_dl2t(352), '/', a_dl2t(320), ' conflict-free: 40')
+    print('  (b) dl2r reads:', b_dl2r(80), '/', b_dl2r(64), ' conflict-free: 112')
+    print('  (c) dlb reads (one term, dlb_slot):', term_cycles(lambda c, j4: 4 * c + j4), ' conflict-free: 60')
+
+
 if __name__ == '__main__':
+    import sys
+    if '--bf16' in sys.argv:
+        bf16_report()
+        sys.exit(0)
     old = lambda c, j4: 4 * c + j4                                   # noqa: E731
     assert sorted(r4_block(c, j) for c in range(15) for j in range(4)) == list(range(60))
     assert all(r4_fmap(r4_block(c, j)) == 4 * c + j for c in range(15) for j in range(4))
