@@ -192,13 +192,15 @@ extern "C" int a3c_lambda_q_target(const float* rewards, const uint8_t* terminal
                                     lambda, target, (hipStream_t)stream);
 }
 
-extern "C" int a3c_loss_backward_prec(const a3c_net_desc* net, const float* params, const uint8_t* states, int64_t B,
-                                      const float* act_l1, const float* act_l2, const float* act_l3, const float* z,
-                                      const int32_t* actions, const float* target, float beta, int literal_adv,
-                                      int conv_bwd_precision, float* grads, float* loss_out, void* workspace,
-                                      void* stream) {
+extern "C" int a3c_loss_backward_prec2(const a3c_net_desc* net, const float* params, const uint8_t* states, int64_t B,
+                                       const float* act_l1, const float* act_l2, const float* act_l3, const float* z,
+                                       const int32_t* actions, const float* target, float beta, int literal_adv,
+                                       int conv_bwd_precision, int fc_bwd_precision, float* grads, float* loss_out,
+                                       void* workspace, void* stream) {
   if (conv_bwd_precision != A3C_PREC_FP32 && conv_bwd_precision != A3C_PREC_BF16)
-    return a3c_set_error(A3C_ERR_INVALID, "a3c_loss_backward_prec", "conv_bwd_precision: A3C_PREC_FP32 or A3C_PREC_BF16");
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_loss_backward_prec2", "conv_bwd_precision: A3C_PREC_FP32 or A3C_PREC_BF16");
+  if (fc_bwd_precision != A3C_PREC_FP32 && fc_bwd_precision != A3C_PREC_BF16)
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_loss_backward_prec2", "fc_bwd_precision: A3C_PREC_FP32 or A3C_PREC_BF16");
   NetLayout L;
   if (a3c_make_layout(net, &L) || L.lstm || L.trunk != A3C_TRUNK_NIPS || !params || !states || !act_l1 || !act_l2 || !act_l3 || !z || !actions ||
       !target || !grads || !workspace || B <= 0 || B > 0x7fffffff || (((uintptr_t)states) & 15))
@@ -209,7 +211,17 @@ extern "C" int a3c_loss_backward_prec(const a3c_net_desc* net, const float* para
   a.act_l1 = act_l1; a.act_l2 = act_l2; a.act_l3 = act_l3; a.z = z; a.actions = actions; a.target = target;
   a.beta = beta; a.literal = literal_adv; a.grads = grads; a.loss_out = loss_out; a.ws = align_ws(workspace);
   L.cbwd_prec = conv_bwd_precision;
+  L.fcbwd_prec = fc_bwd_precision;
   return a3c_backward_launch(L, a, (hipStream_t)stream, LAUNCH_ALONE);
+}
+
+extern "C" int a3c_loss_backward_prec(const a3c_net_desc* net, const float* params, const uint8_t* states, int64_t B,
+                                      const float* act_l1, const float* act_l2, const float* act_l3, const float* z,
+                                      const int32_t* actions, const float* target, float beta, int literal_adv,
+                                      int conv_bwd_precision, float* grads, float* loss_out, void* workspace,
+                                      void* stream) {
+  return a3c_loss_backward_prec2(net, params, states, B, act_l1, act_l2, act_l3, z, actions, target, beta, literal_adv,
+                                 conv_bwd_precision, A3C_PREC_FP32, grads, loss_out, workspace, stream);
 }
 
 extern "C" int a3c_loss_backward(const a3c_net_desc* net, const float* params, const uint8_t* states, int64_t B,

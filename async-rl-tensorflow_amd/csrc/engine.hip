@@ -1393,6 +1393,24 @@ extern "C" int a3c_engine_set_conv_bwd_precision(a3c_engine* e, int precision) {
   return 0;
 }
 
+// fc_bwd_precision: the NIPS trunk's two fc backward GEMMs' compute mode, the fifth switch: read from
+// the layout by a3c_bwd_plan and by the two launch sites of net_bwd.hip that every backward path goes through.  The
+// forward, the rollout, the saved activations and the workspace do not see it.
+extern "C" int a3c_engine_set_fc_bwd_precision(a3c_engine* e, int precision) {
+  if (precision != A3C_PREC_FP32 && precision != A3C_PREC_BF16)
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_set_fc_bwd_precision", "precision: A3C_PREC_FP32 or A3C_PREC_BF16");
+  if (!e) return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_set_fc_bwd_precision", "null");
+  if (e->nat)
+    return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_set_fc_bwd_precision",
+                         "fc_bwd_precision is the nips trunk's fc backward mode (the nature trunk has fc_precision)");
+  if (e->grad_ready && !e->grad_applied)
+    return a3c_set_error(A3C_ERR_STATE, "a3c_engine_set_fc_bwd_precision", "a gradient is pending: apply it first");
+  A3C_CHECK(hipDeviceSynchronize());
+  e->L.fcbwd_prec = precision;
+  drop_graphs(e);   // (they hold the other mode's kernels)
+  return 0;
+}
+
 extern "C" int a3c_engine_reset(a3c_engine* e, const float* host_params, void* stream) {
   if (!e) return a3c_set_error(A3C_ERR_INVALID, "a3c_engine_reset", "null");
   hipStream_t s = (hipStream_t)stream;

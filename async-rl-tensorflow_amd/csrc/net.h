@@ -47,6 +47,8 @@ struct NetLayout {
                             // DESIGN §4q): lstm.hip's fp32 passes or lstm_bf16.hip's
   int cbwd_prec;            // A3C_PREC_*: the NIPS conv backward's compute mode, as prec (a3c_engine_set_conv_bwd_precision,
                             // a3c_loss_backward_prec): k_conv_bwd or conv_bwd_bf16.hip's k_conv_bwd_bf
+  int fcbwd_prec;           // A3C_PREC_*: the NIPS fc backward GEMMs' compute mode, as prec (a3c_engine_set_fc_bwd_precision,
+                            // a3c_loss_backward_prec2): gemm.hip's fp32 MFMA or fc_bwd_bf16.hip's two kernels
   int nt;
   int64_t off[A3C_MAX_TENSORS], size[A3C_MAX_TENSORS];
   int64_t total;
@@ -78,6 +80,7 @@ inline int a3c_make_layout(const a3c_net_desc* d, NetLayout* L) {
   L->fc_prec = A3C_PREC_FP32;
   L->lstm_prec = A3C_PREC_FP32;
   L->cbwd_prec = A3C_PREC_FP32;
+  L->fcbwd_prec = A3C_PREC_FP32;
   if (nature) {   // l1..l3 conv [kh,kw,cin,cout] + bias, l4 [3136,512] + bias, p [512,A] + bias, q [512,1] + bias
     const int64_t ns[12] = {8 * 8 * HIST * 32, 32, 4 * 4 * 32 * 64, 64, 3 * 3 * 64 * 64, 64, 3136LL * 512, 512,
                             512LL * A, A, 512, 1};

@@ -172,6 +172,12 @@ int a3c_conv12_launch(const NetLayout& L, const float* P, const uint8_t* prep, c
 int a3c_conv_bwd_bf_launch(const StateAddr& sa, int64_t B, const BwdPlan& p, const float* act_l1, const float* dl2,
                            const float* W2, float* slab, int smem, hipStream_t s);
 void a3c_conv_bwd_bf_set_smem(int smem);
+// fc_bwd_bf16.hip (L.fcbwd_prec BF16): dWfc = rn(l2)^T rn(dl3) written whole with the column sums of the
+// unrounded dl3 in colsum [FC], and dl2 = (rn(dl3) rn(Wfc)^T) * (l2 > 0), the mask from l2bits (FLAT / 32 words a
+// row) when given, else from l2
+int a3c_fc_dw_bf_launch(const float* l2, const float* dl3, int64_t B, float* dW, float* colsum, hipStream_t s);
+int a3c_fc_dx_bf_launch(const float* dl3, const float* W, const float* l2, const uint32_t* l2bits, int64_t B, float* dl2,
+                        hipStream_t s);
 int a3c_conv_bwd_launch(const NetLayout& L, const float* P, const StateAddr& sa, int64_t B, const float* act_l1,
                         const float* dl2, float* ws, hipStream_t s, const LaunchMode& m);
 

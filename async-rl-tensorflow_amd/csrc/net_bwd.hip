@@ -1008,7 +1008,8 @@ BwdPlan a3c_bwd_plan(const NetLayout& L, int64_t B, bool wks) {
   // round trip through HBM, no fold kernel; else split-K slabs + k_reduce_slabs.  The slab and column
   // sum buffers are sized for the slab form either way, so the offsets do not depend on it.
   const int fc_split_slab = a3c_gemm_effective_split((int)B, a3c_gemm_plan_split(FLAT, FC, (int)B, 512));
-  p.fc_split = wks ? 1 : fc_split_slab;
+  // (L.fcbwd_prec BF16: k_fc_dw_bf writes dW whole and one column-sum slab)
+  p.fc_split = wks || L.fcbwd_prec == A3C_PREC_BF16 ? 1 : fc_split_slab;
   p.dz = take(B * L.zs);
   p.dh3 = take(B * FC);
   p.dl2 = take(B * FLAT);
@@ -1023,6 +1024,17 @@ BwdPlan a3c_bwd_plan(const NetLayout& L, int64_t B, bool wks) {
   p.cgroup = take((int64_t)16 * CB_SLAB);    // groups <= 16
   p.total = o;
   return p;
+}
+
+// The two fc backward passes' launch sites: L.fcbwd_prec FP32 launches the GemmArgs the caller built, as it built
+// them; BF16 launches fc_bwd_bf16.hip's kernel on the same operands, whatever the launch mode.
+static int fc_dw_launch(const NetLayout& L, const GemmArgs& gf, hipStream_t s) {
+  if (L.fcbwd_prec == A3C_PREC_BF16) return a3c_fc_dw_bf_launch(gf.A, gf.B, gf.K, gf.C, gf.colsum, s);
+  return a3c_gemm(false, true, gf, s);
+}
+static int fc_dx_launch(const NetLayout& L, const GemmArgs& gd, hipStream_t s) {
+  if (L.fcbwd_prec == A3C_PREC_BF16) return a3c_fc_dx_bf_launch(gd.A, gd.B, gd.mask, gd.maskbits, gd.M, gd.C, s);
+  return a3c_gemm(true, false, gd, s);
 }
 
 // The split backward (SplitBwd): head and fc weight GEMMs with their folds right behind them, the
@@ -1042,8 +1054,8 @@ static int backward_split(const NetLayout& L, const float* P, const StateAddr& s
   gf.defer_reduce = 0;
   gh.big = gf.big = gd.big = 0;
   int rc = a3c_gemm(false, true, gh, s);
-  if (!rc) rc = a3c_gemm(false, true, gf, s);
-  if (!rc) rc = a3c_gemm(true, false, gd, s);
+  if (!rc) rc = fc_dw_launch(L, gf, s);
+  if (!rc) rc = fc_dx_launch(L, gd, s);
   if (rc) return rc;
   auto segs = [&](FinalizeSegs& fs) {
     fs.dst = grads;
@@ -1159,7 +1171,10 @@ int a3c_backward_launch(const NetLayout& L, const BwdArgs& a, hipStream_t s, con
   // the one-phase backward of the same configuration takes (multi0 does not depend on sp), so the
   // two exchanges sum the fc weight gradient in one order and stay bit-identical
   // (test_gpu_multirank.py::test_split_exchange_equals_one_phase)
-  const bool wks = fc_wks_on(B) && !L.lstm && !multi0;
+  // L.fcbwd_prec BF16: one kernel form per fc pass in every mode -- no wks, no three-GEMM launch (the
+  // head weight GEMM goes alone through a3c_gemm, folded as the separate-launch path folds it)
+  const bool fc_bf = L.fcbwd_prec == A3C_PREC_BF16;
+  const bool wks = fc_wks_on(B) && !L.lstm && !multi0 && !fc_bf;
   const BwdPlan p = a3c_bwd_plan(L, B, wks);
   float* dz = ws + p.dz;
   float* dh3 = ws + p.dh3;
@@ -1250,8 +1265,8 @@ int a3c_backward_launch(const NetLayout& L, const BwdArgs& a, hipStream_t s, con
   static const int env_hfold_knob = (int)A3C_AB_KNOB("A3C_HEAD_FOLD", -1);
   const bool env_hfold = env_hfold_knob >= 0 ? env_hfold_knob != 0 : lb != nullptr;
   bool hfold = false;
-  const bool multi = multi0 && !wks;
-  const bool late = env_late >= 0 ? env_late != 0 : multi;
+  const bool multi = multi0 && !wks && !fc_bf;
+  const bool late = !fc_bf && (env_late >= 0 ? env_late != 0 : multi);
   if (multi || late) {
     // the weight-gradient split-K folds go after the conv backward (only the clip / apply read
     // them), so nothing but dl2 stands between the head and the conv
@@ -1260,8 +1275,8 @@ int a3c_backward_launch(const NetLayout& L, const BwdArgs& a, hipStream_t s, con
     } else {
       gh.defer_reduce = gf.defer_reduce = 1;
       rc = a3c_gemm(false, true, gh, s);
-      if (!rc) rc = a3c_gemm(false, true, gf, s);
-      if (!rc) rc = a3c_gemm(true, false, gd, s);
+      if (!rc) rc = fc_dw_launch(L, gf, s);
+      if (!rc) rc = fc_dx_launch(L, gd, s);
     }
     if (rc) return rc;
     rc = a3c_conv_bwd_launch(L, P, a.sa, B, act_l1, dl2, ws, s, m);
@@ -1282,10 +1297,10 @@ int a3c_backward_launch(const NetLayout& L, const BwdArgs& a, hipStream_t s, con
     rc = abl_gemm ? 0 : a3c_gemm(false, true, gh, s);
     if (rc) return rc;
     if (!dwfc_late) {
-      rc = abl_gemm ? 0 : a3c_gemm(false, true, gf, s);
+      rc = abl_gemm ? 0 : fc_dw_launch(L, gf, s);
       if (rc) return rc;
     }
-    rc = abl_gemm ? 0 : a3c_gemm(true, false, gd, s);
+    rc = abl_gemm ? 0 : fc_dx_launch(L, gd, s);
     if (rc) return rc;
 #ifdef A3C_MARKERS
     a3c_mark(4, s);
@@ -1296,7 +1311,7 @@ int a3c_backward_launch(const NetLayout& L, const BwdArgs& a, hipStream_t s, con
     a3c_mark(5, s);
 #endif
     if (dwfc_late) {
-      rc = abl_gemm ? 0 : a3c_gemm(false, true, gf, s);
+      rc = abl_gemm ? 0 : fc_dw_launch(L, gf, s);
       if (rc) return rc;
     }
   }

@@ -18,6 +18,7 @@ accepted but the TF ps/worker cluster is replaced by one process per GPU under t
   python main.py --mode engine --dqn_type nature --precision bf16 --fc_precision bf16   ... and the fc's three GEMMs too
   python main.py --mode engine --lstm true --lstm_precision bf16   the LSTM head's three matrix passes on bf16 operands
   python main.py --mode engine --conv_bwd_precision bf16   the nips trunk's fused conv backward on bf16 operands
+  python main.py --mode engine --fc_bwd_precision bf16   the nips trunk's two fc backward GEMMs on bf16 operands
                  
   python main.py --mode engine --algo q --optimizer adam --env_name Catch-v0             shared Adam instead of RMSProp
   python main.py --mode engine --lstm true --env_name CatchMemory-v0   Catch that only a head with memory learns
@@ -141,6 +142,10 @@ def parse_flags(argv=None):
                  help="engine mode, --dqn_type nips: fp32 (the fused conv backward as it stands) or bf16 (its three "
                       "passes on single bf16 operands, fp32 accumulation; the forward and the rollout are untouched; a "
                       "fourth, independent switch; DESIGN §4r)")
+  p.add_argument('--fc_bwd_precision', default='fp32',
+                 help="engine mode, --dqn_type nips: fp32 (the two fc backward GEMMs as they stand) or bf16 (dWfc and "
+                      "dl2 on single bf16 operands, fp32 accumulation; the forward and the rollout are untouched; a "
+                      "fifth, independent switch; DESIGN §4s)")
   # evaluation: --mode engine --is_train false (Agent.play, agent.py:351-391)
   p.add_argument('--n_episode', type=int, default=100, help='play: episodes (agent.py:351)')
   p.add_argument('--play_steps', type=int, default=10000, help="play: cap on an episode's env steps (agent.py:351 n_step)")
@@ -214,6 +219,12 @@ def engine_options(flags):
   if conv_bwd_precision == 'bf16' and flags.dqn_type != 'nips':
     raise ValueError('--conv_bwd_precision bf16 is the conv backward mode of the nips trunk (DESIGN §4r): with '
                      '--dqn_type nature use --precision bf16')
+  fc_bwd_precision = getattr(flags, 'fc_bwd_precision', 'fp32')
+  if fc_bwd_precision not in ('fp32', 'bf16'):
+    raise ValueError("--fc_bwd_precision must be fp32 or bf16 (got %r)" % (fc_bwd_precision,))
+  if fc_bwd_precision == 'bf16' and flags.dqn_type != 'nips':
+    raise ValueError('--fc_bwd_precision bf16 is the fc backward mode of the nips trunk (DESIGN §4s): with '
+                     '--dqn_type nature use --fc_precision bf16')
   first_screen = bool(getattr(flags, 'first_screen', False))
   if first_screen and game_kind(flags.env_name) != 'catch':
     raise ValueError('--first_screen is an option of the device game Catch (--env_name Catch-v0 or CatchMemory-v0, '
@@ -247,6 +258,8 @@ def engine_options(flags):
     kw['lstm_precision'] = lstm_precision
   if conv_bwd_precision != 'fp32':
     kw['conv_bwd_precision'] = conv_bwd_precision
+  if fc_bwd_precision != 'fp32':
+    kw['fc_bwd_precision'] = fc_bwd_precision
   return kw
 
 
@@ -544,6 +557,9 @@ def main(argv=None):
                      'is the per-op loop in fp32')
   if flags.mode == 'agent' and flags.conv_bwd_precision != 'fp32':
     raise ValueError('--conv_bwd_precision is an engine option (the conv backward of --mode engine, DESIGN §4r): '
+                     '--mode agent is the per-op loop in fp32')
+  if flags.mode == 'agent' and flags.fc_bwd_precision != 'fp32':
+    raise ValueError('--fc_bwd_precision is an engine option (the fc backward of --mode engine, DESIGN §4s): '
                      '--mode agent is the per-op loop in fp32')
   if flags.mode == 'agent' and flags.first_screen:
     raise ValueError('--first_screen is an engine option: --mode agent is the reference loop (agent.py:59-67) as it stands')

@@ -129,6 +129,11 @@ SIGNATURES = {
     'a3c_loss_backward_prec': (c_int, [ctypes.POINTER(NetDesc), c_void_p, c_void_p, c_i64, c_void_p, c_void_p,
                                        c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_int, c_void_p,
                                        c_void_p, c_void_p, c_void_p]),
+    'a3c_loss_backward_prec2': (c_int, [ctypes.POINTER(NetDesc), c_void_p, c_void_p, c_i64, c_void_p, c_void_p,
+                                        c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_int, c_int, c_void_p,
+                                        c_void_p, c_void_p, c_void_p]),
+    'a3c_fc_bwd_bf16': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p,
+                                c_void_p]),
     'a3c_nature_workspace_bytes': (c_int, [ctypes.POINTER(NetDesc), c_i64, ctypes.POINTER(c_i64)]),
     'a3c_nature_forward': (c_int, [ctypes.POINTER(NetDesc), c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p,
                                    c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -196,6 +201,7 @@ SIGNATURES = {
     'a3c_engine_set_fc_precision': (c_int, [c_void_p, c_int]),
     'a3c_engine_set_lstm_precision': (c_int, [c_void_p, c_int]),
     'a3c_engine_set_conv_bwd_precision': (c_int, [c_void_p, c_int]),
+    'a3c_engine_set_fc_bwd_precision': (c_int, [c_void_p, c_int]),
     'a3c_engine_reset': (c_int, [c_void_p, c_void_p, c_void_p]),
     'a3c_engine_rollout_grad': (c_int, [c_void_p, c_void_p]),
     'a3c_engine_apply': (c_int, [c_void_p, c_void_p]),
@@ -270,6 +276,7 @@ OPTIONAL_IN_OLD_BUILDS = MEASUREMENT_ONLY + ('a3c_engine_exchange_split', 'a3c_e
                                              'a3c_lstm_prepare', 'a3c_lstm_step_prec', 'a3c_lstm_bptt_prec',
                                              'a3c_engine_set_lstm_precision',
                                              'a3c_loss_backward_prec', 'a3c_engine_set_conv_bwd_precision',
+                                             'a3c_loss_backward_prec2', 'a3c_engine_set_fc_bwd_precision', 'a3c_fc_bwd_bf16',
                                              'a3c_gemm_workspace_bytes', 'a3c_gemm_f32', 'a3c_gemm3_f32')
 
 # the nature trunk's conv compute modes (include/a3c_hip.h A3C_PREC_*)

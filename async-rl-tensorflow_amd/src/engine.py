@@ -57,7 +57,8 @@ class Engine:
     def __init__(self, num_envs=256, n_step=5, action_size=6, algo='a3c', start_lives=0, num_frames=None,
                  seed=123, env_id_base=0, world_size=1, use_graph=False, overlap=False, lstm=False,
                  external_env=False, dqn_type='nips', game='synth', catch_rules=None, first_screen=None, q_lambda=None,
-                 precision='fp32', fc_precision='fp32', lstm_precision='fp32', conv_bwd_precision='fp32', **overrides):
+                 precision='fp32', fc_precision='fp32', lstm_precision='fp32', conv_bwd_precision='fp32',
+                 fc_bwd_precision='fp32', **overrides):
         """game: 'synth' (the synthetic Atari stand-in) or 'catch' (Catch-v0, DESIGN §4g: action_size 3,
         start_lives 0, device envs, raw RGB pool; random_start is ignored).  num_frames=None: 1024
         frames (Catch needs its 640: a smaller explicit value is rejected by the library).
@@ -95,7 +96,12 @@ class Engine:
         conv_bwd_precision='fp32' | 'bf16' ('fp32': no call is made): a3c_engine_set_conv_bwd_precision
         right after the create -- 'bf16' (dqn_type 'nips' only) runs the fused conv backward's three passes on one
         bf16 term per operand with fp32 accumulation; the forward and the rollout are untouched; kept as
-        ``conv_bwd_precision``.  Not in the saved state either."""
+        ``conv_bwd_precision``.  Not in the saved state either.
+        fc_bwd_precision='fp32' | 'bf16' ('fp32': no call is made): a3c_engine_set_fc_bwd_precision right
+        after the create -- 'bf16' (dqn_type 'nips' only) runs the two fc backward GEMMs (dWfc and dl2) on one bf16
+        term per operand with fp32 accumulation, independently of the other four; the forward and the rollout are
+        untouched; kept as ``fc_bwd_precision``.  Not in the saved state either."""
+        self.fc_bwd_precision = self._check_fc_bwd_precision(fc_bwd_precision, str(dqn_type).lower())
         self.conv_bwd_precision = self._check_conv_bwd_precision(conv_bwd_precision, str(dqn_type).lower())
         self.lstm_precision = self._check_lstm_precision(lstm_precision, lstm)
         self.precision = self._check_precision(precision, str(dqn_type).lower())
@@ -189,6 +195,9 @@ class Engine:
         if self.conv_bwd_precision != 'fp32':
             check(lib().a3c_engine_set_conv_bwd_precision(h, _lib.PRECISIONS[self.conv_bwd_precision]),
                   'a3c_engine_set_conv_bwd_precision')
+        if self.fc_bwd_precision != 'fp32':
+            check(lib().a3c_engine_set_fc_bwd_precision(h, _lib.PRECISIONS[self.fc_bwd_precision]),
+                  'a3c_engine_set_fc_bwd_precision')
         b = _lib.EngineBuffers()
         check(lib().a3c_engine_get_buffers(h, ctypes.byref(b)), 'a3c_engine_get_buffers')
         self._b = b
@@ -300,6 +309,20 @@ class Engine:
         check(lib().a3c_engine_set_conv_bwd_precision(self._h, _lib.PRECISIONS[value]),
               'a3c_engine_set_conv_bwd_precision')
         self.conv_bwd_precision = value
+
+    @staticmethod
+    def _check_fc_bwd_precision(value, dqn_type):
+        _lib.precision_code(value, 'fc_bwd_precision')
+        if value == 'bf16' and dqn_type != 'nips':
+            raise ValueError("fc_bwd_precision 'bf16' is the nips trunk's fc backward mode (dqn_type %r has "
+                             "fc_precision)" % (dqn_type,))
+        return value
+
+    def set_fc_bwd_precision(self, value):
+        """a3c_engine_set_fc_bwd_precision between iterations: no reset, the next gradient follows it."""
+        value = self._check_fc_bwd_precision(value, self.dqn_type)
+        check(lib().a3c_engine_set_fc_bwd_precision(self._h, _lib.PRECISIONS[value]), 'a3c_engine_set_fc_bwd_precision')
+        self.fc_bwd_precision = value
 
     def _slot_views(self, k):
         b = _lib.EngineBuffers()

@@ -327,9 +327,11 @@ class Net:
 
     # -- K8/K9 loss + backward ----------------------------------------------------------
     def loss_backward(self, params, states, fwd, actions, target, beta=0.01, literal_adv=False,
-                      grads=None, workspace=None, conv_bwd_precision=None):
+                      grads=None, workspace=None, conv_bwd_precision=None, fc_bwd_precision=None):
         """conv_bwd_precision: None or 'fp32' (a3c_loss_backward), or 'bf16' (a3c_loss_backward_prec: the fused
-        conv backward on single bf16 operands; only l1_w, l1_b, l2_w and l2_b move)."""
+        conv backward on single bf16 operands; only l1_w, l1_b, l2_w and l2_b move).
+        fc_bwd_precision: None or 'fp32', or 'bf16' (a3c_loss_backward_prec2: the two fc backward GEMMs on single
+        bf16 operands; fc_w, fc_b and the four conv tensors move); independent of the other."""
         _dev(actions, torch.int32, 'actions')
         _dev(target, torch.float32, 'target')
         B = int(states.shape[0])
@@ -338,6 +340,13 @@ class Net:
             grads = torch.zeros(self.total, dtype=torch.float32, device=dev)
         loss = torch.zeros(4, dtype=torch.float32, device=dev)
         ws = workspace if workspace is not None else self.workspace(B, dev)
+        if fc_bwd_precision is not None and _lib.precision_code(fc_bwd_precision, 'fc_bwd_precision') != _lib.PREC_FP32:
+            cb = _lib.PREC_FP32 if conv_bwd_precision is None else _lib.precision_code(conv_bwd_precision, 'conv_bwd_precision')
+            check(lib().a3c_loss_backward_prec2(ctypes.byref(self.desc), ptr(params), ptr(states), B, ptr(fwd['l1']),
+                                                ptr(fwd['l2']), ptr(fwd['l3']), ptr(fwd['z']), ptr(actions), ptr(target),
+                                                float(beta), 1 if literal_adv else 0, cb, _lib.PREC_BF16, ptr(grads),
+                                                ptr(loss), ptr(ws), stream_handle()), 'a3c_loss_backward_prec2')
+            return grads, loss
         if conv_bwd_precision is not None and _lib.precision_code(conv_bwd_precision, 'conv_bwd_precision') != _lib.PREC_FP32:
             check(lib().a3c_loss_backward_prec(ctypes.byref(self.desc), ptr(params), ptr(states), B, ptr(fwd['l1']),
                                                ptr(fwd['l2']), ptr(fwd['l3']), ptr(fwd['z']), ptr(actions), ptr(target),
@@ -545,6 +554,32 @@ def gemm3(descs, workspaces):
     eff = (ctypes.c_int * 3)()
     check(lib().a3c_gemm3_f32(d, ws, nb, eff, stream_handle()), 'a3c_gemm3_f32')
     return [int(e) for e in eff]
+
+
+def fc_bwd_bf16(l2, dl3, Wfc, mask=None, maskbits=None, out=None):
+    """The nips trunk's two fc backward passes on bf16 operands (a3c_fc_bwd_bf16): l2 [B, 2592], dl3
+    [B, 256], Wfc [2592, 256] -> (dW [2592, 256], colsum [256], dl2 [B, 2592]).  Exactly one of ``mask`` (the fp32
+    l2) and ``maskbits`` (int32 [B, 81]: the ReLU bits of l2); ``out``: the three result tensors to write -- (dW,
+    colsum, None) runs the dW pass alone (no mask then), (None, None, dl2) the dX pass alone."""
+    for t, name in ((l2, 'l2'), (dl3, 'dl3'), (Wfc, 'Wfc')):
+        _dev(t, torch.float32, name)
+    B = int(l2.shape[0])
+    if tuple(l2.shape) != (B, 2592) or tuple(dl3.shape) != (B, 256) or tuple(Wfc.shape) != (2592, 256):
+        raise ValueError('expected l2 [B, 2592], dl3 [B, 256] and Wfc [2592, 256]')
+    if maskbits is not None:
+        _dev(maskbits, torch.int32, 'maskbits')
+        if tuple(maskbits.shape) != (B, 81):
+            raise ValueError('maskbits: expected shape [B, 81]')
+    if mask is not None:
+        _dev(mask, torch.float32, 'mask')
+        if tuple(mask.shape) != (B, 2592):
+            raise ValueError('mask: expected shape [B, 2592]')
+    dW, colsum, dl2 = out if out is not None else (torch.empty((2592, 256), dtype=torch.float32, device=l2.device),
+                                                   torch.empty(256, dtype=torch.float32, device=l2.device),
+                                                   torch.empty((B, 2592), dtype=torch.float32, device=l2.device))
+    check(lib().a3c_fc_bwd_bf16(ptr(l2), ptr(dl3), ptr(Wfc), ptr(mask), ptr(maskbits), B, ptr(dW), ptr(colsum), ptr(dl2),
+                                stream_handle()), 'a3c_fc_bwd_bf16')
+    return dW, colsum, dl2
 
 
 def copy_params(dst, src):

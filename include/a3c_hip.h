@@ -338,6 +338,36 @@ int a3c_loss_backward_prec(const a3c_net_desc* net, const float* params, const u
                            int literal_adv, int conv_bwd_precision, float* grads, float* loss_out,
                            void* workspace, void* stream);
 
+/* ... and the fc backward's compute mode per call: a3c_loss_backward_prec's argument list plus
+ * fc_bwd_precision behind conv_bwd_precision; a3c_loss_backward_prec is this entry with A3C_PREC_FP32 for it,
+ * bit for bit.  A3C_PREC_BF16 replaces the two fc backward GEMMs of gemm.hip's exact-fp32 MFMA by
+ * a3c_fc_bwd_bf16's two kernels (the definition stands there), the mask from the fp32 act_l2; the head weight
+ * GEMM then runs alone, folded by the finalize.  Only the gradients of fc_w (rounded products), fc_b
+ * (summation order) and the four conv tensors (they read the new dl2) move; the head tensors, the loss words
+ * and the workspace size are those of FP32.  The two modes are independent.
+ * A3C_ERR_INVALID: either precision neither constant, then a3c_loss_backward's checks. */
+int a3c_loss_backward_prec2(const a3c_net_desc* net, const float* params, const uint8_t* states,
+                            int64_t B, const float* act_l1, const float* act_l2, const float* act_l3,
+                            const float* z, const int32_t* actions, const float* target, float beta,
+                            int literal_adv, int conv_bwd_precision, int fc_bwd_precision, float* grads,
+                            float* loss_out, void* workspace, void* stream);
+
+/* The nips trunk's two fc backward passes alone on gfx950's bf16 matrix cores (what
+ * a3c_gemm_f32 is to the fp32 GEMM: tests and tools/fc_bwd_precision_throughput.py call it).  rn rounds to
+ * nearest even to bf16, once per operand, from the fp32 value; one v_mfma_f32_16x16x32_bf16 per K step,
+ * fp32 accumulation, no atomics, one summation order per B:
+ *    dW[2592][256]  = rn(l2)^T rn(dl3)                 written whole (K = B, split over the workgroup's waves)
+ *    colsum[256]    = column sums of the unrounded dl3
+ *    dl2[B][2592]   = (rn(dl3) rn(Wfc)^T) * (l2 > 0)   Wfc [2592][256] rounded from fp32 where it is staged
+ * l2 [B][2592], dl3 [B][256].  The mask: exactly one of mask_f32 (the fp32 l2 itself, [B][2592]) and
+ * maskbits (the forward's ReLU bits: bit n & 31 of word [b * 81 + (n >> 5)]); both give the same dl2.
+ * One pass alone (the timing tool): dl2 NULL runs the dW pass only (then no mask), dW and colsum both NULL
+ * the dX pass only.
+ * A3C_ERR_INVALID: a null matrix, both masks or neither, B < 1 or B * 2592 > INT_MAX, a matrix not 16-byte
+ * aligned. */
+int a3c_fc_bwd_bf16(const float* l2, const float* dl3, const float* Wfc, const float* mask_f32,
+                    const uint32_t* maskbits, int64_t B, float* dW, float* colsum, float* dl2, void* stream);
+
 /* ----------------------------------------------------------------------------
  * K10+K11  per-tensor clip_by_norm (agent.py:316-319) + TF ApplyRMSProp
  *  (main.py:63-65, agent.py:321): ms += (g^2-ms)(1-rho); mom = mom*momentum +
@@ -772,6 +802,18 @@ int a3c_engine_set_lstm_precision(a3c_engine* eng, int precision);
  * state (a resumed run gives it again).
  * python async-rl-tensorflow_amd/main.py --mode engine --conv_bwd_precision bf16 */
 int a3c_engine_set_conv_bwd_precision(a3c_engine* eng, int precision);
+/* fc_bwd_precision: the compute mode of a nips-trunk engine's two fc backward GEMMs,
+ * A3C_PREC_FP32 (the default: every launch is what it is without this call) or A3C_PREC_BF16 (the definition
+ * stands at a3c_fc_bwd_bf16; the mask is the forward's ReLU bits where the engine keeps them), independent of
+ * the other four switches.  Every backward path (one-pass, split exchange, LSTM, q) launches each of the two
+ * passes from one site, which reads the mode; in BF16 the head weight GEMM runs alone in every launch mode.
+ * The forward, the rollout, the saved activations and the workspace do not depend on it.  A setter with the
+ * rules of a3c_engine_set_precision: valid between iterations, no reset, captured graphs are dropped.
+ * A3C_ERR_INVALID, in this order: a precision that is neither constant, eng NULL, a nature-trunk engine (the
+ * mode is the nips trunk's).  A3C_ERR_STATE: a computed gradient not yet applied.  Not in the checkpoint's
+ * state (a resumed run gives it again).
+ * python async-rl-tensorflow_amd/main.py --mode engine --fc_bwd_precision bf16 */
+int a3c_engine_set_fc_bwd_precision(a3c_engine* eng, int precision);
 /* fill the frame pool, reset the envs (new_random_game, environment.py:35-40), fill each
  * history with 4 copies of the first screen (agent.py:37-38) and initialise params
  * from host memory (nullable -> keep), rms slot = 1, mom = 0 (Adam: m = v = 0, products = 1). */
